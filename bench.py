@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- training-step audio-seconds/second of the tiny-audio projector-training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON line (`value`, `ms_per_step` = milliseconds of one
+timed step, ...); every other leg below (the extra timed legs, roofline, cpu_baseline / parity, and at N > 1 the replica check
+and the other all-reduce mode) runs only under `--full`, and the line holds null for it otherwise.  `--dump-outputs DIR` writes
+what the last timed step computed as float32 / float64 .npy files (see dump_outputs): the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.  In the default configuration (MLP projector, frozen LM) the step has no
+order-dependent sums and two runs of one build dump the same bits; the other projectors, --lora and --full-ft may still add some
+gradients with float atomics, and there two runs agree to rounding.
 
 N > 1: one rank per GPU over RCCL.  The driver launches the ranks itself (python -m torch.distributed.run ... bench.py
 --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment); a plain `python bench.py --gpus N`
 re-launches itself the same way.  The line then carries `n_gpus` = N, `rccl_ranks` (counted by an actual all-reduce),
-`allreduce` (bytes, exposed ms per step in the overlapped mode AND -- a second short leg of the same invocation -- in the
-synchronous mode) and `replicas` (weight checksum / optimizer step count min == max over the ranks, per-rank ms_per_step,
-RCCL version, transports named in RCCL's own NCCL_DEBUG log): the run validates itself.  An exception on ANY rank prints one
-JSON line with an "error" field and the process exits non-zero.
+`allreduce` (bytes, exposed ms per step in the overlapped mode AND -- with --full, a second short leg of the same invocation --
+in the synchronous mode) and, with --full, `replicas` (weight checksum / optimizer step count min == max over the ranks, per-rank
+ms_per_step, RCCL version, transports named in RCCL's own NCCL_DEBUG log): the run validates itself.  An exception on ANY rank
+prints one JSON line with an "error" field and the process exits non-zero.
 
 One "step" = one full optimizer step of BASELINE.json configs[1]: B synthetic 10 s / 16 kHz clips per GPU ->
 GPU log-mel -> frozen GLM-ASR encoder (32 layers) -> MLP projector (H=D=1024) -> frozen Qwen3-0.6B (28 layers,
@@ -17,7 +25,7 @@ L=192 tokens, 125 <audio> placeholders, 36 label tokens) -> shifted CE -> backwa
 projector (dW) -> flat gradient all-reduce (RCCL, N>1) -> global-norm clip + AdamW.  Inputs (waveforms, token
 ids) are resident in HBM before the timed region; random-init weights at the true shapes (no checkpoints offline).
 
-The single JSON line carries `roofline` (dominant kernel = the MFMA GEMM, timed in situ with HIP events on
+With --full the single JSON line also carries `roofline` (dominant kernel = the MFMA GEMM, timed in situ with HIP events on
 its launch stream), `host_inputs` (the same step fed from pinned host memory: the PCIe-inclusive rate, never `value`),
 `logits_full` (the same step with the reference's [B, L, V] logits materialised, timed in the same
 run), `streams_other` (the same step with the residual streams stored in the OTHER dtype: `--streams`) and, at N=1,
@@ -48,7 +56,7 @@ import torch.distributed as dist
 
 # Round 6: the headline runs in the storage mode of the benchmarked RECIPE -- configs/config.yaml:14-18
 # `model_dtype: float32` + production.yaml:49 `bf16: true` = fp32 modules under bf16 autocast, i.e. fp32 residual streams.  The
-# bf16-module regime (ASRConfig's own default model_dtype, ~7 % faster) is timed in the same line as `streams_other`.
+# bf16-module regime (ASRConfig's own default model_dtype, ~7 % faster) is timed in the same --full line as `streams_other`.
 DEFAULT_STREAMS = "f32"
 PEAK_BF16_DENSE_TFLOPS = 2500.0      # MI355X_MICROARCH.md: ~2.5 PF dense bf16 (2:1-sparse marketing figure is 5 PF)
 
@@ -65,8 +73,8 @@ def parse():
                          "'labelled' computes the loss head only on label positions (identical loss and gradients)")
     ap.add_argument("--streams", choices=["bf16", "f32"], default=DEFAULT_STREAMS,
                     help="storage dtype of the encoder / LM residual streams (ASRConfig.model_dtype): f32 = the training recipe's "
-                         "fp32 modules under bf16 autocast, bf16 = bf16 modules (ASRConfig's default).  The other mode is timed as "
-                         "`streams_other` in the same line")
+                         "fp32 modules under bf16 autocast, bf16 = bf16 modules (ASRConfig's default).  With --full the other mode is timed "
+                         "as `streams_other` in the same line")
     ap.add_argument("--dropout", type=float, default=0.10, help="audio_token_dropout (configs/config.yaml:32)")
     ap.add_argument("--projector", choices=["mlp", "moe", "qformer", "mosa"], default="mlp",
                     help="mlp = BASELINE configs[1]/[2]; moe = configs[3] (shared + 4 routed experts, top-2, jitter on)")
@@ -78,6 +86,12 @@ def parse():
     ap.add_argument("--full-ft", action="store_true",
                     help="full decoder fine-tuning (configs/experiments/embedded.yaml): freeze_language_model=False, MLP projector "
                          "H=2048, decoder lr 1e-4; every LM weight trains (0.6 B fp32 masters, AdamW, bf16 W / W^T images rebuilt per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: logits_full, streams_other, host_inputs, roofline, cpu_baseline + "
+                         "parity, and at N > 1 the replica check and the other all-reduce mode (each --no-* flag still drops its leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (loss, grad norm, trainable parameters, "
+                         "their gradients) to DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-logits-full", action="store_true", help="skip the two extra timed legs: materialised outputs.logits, and inputs fed from pinned host memory")
     ap.add_argument("--sync-allreduce", action="store_true", help="N > 1: all-reduce synchronously on the compute stream")
@@ -373,10 +387,12 @@ def run(a):
     loss = trainer.last_loss()
     ms = dt / a.steps * 1e3
     value = world * B * 10.0 * a.steps / dt
+    if a.dump_outputs and rank == 0:                              # before any --full leg steps the trainer on
+        dump_outputs(a.dump_outputs, trainer)
     # N > 1: (i) are the replicas still identical (weights, step count), who was slow; (ii) the other all-reduce mode in the same
     # invocation (a short leg): what the deferred update buys
     replicas, ar_other = None, None
-    if world > 1:
+    if world > 1 and a.full:
         kr = max(2, min(a.steps, 4))
         sync(); t_local = time.perf_counter()                     # this rank's own clock, no barrier: who is slow
         for _ in range(kr):
@@ -394,7 +410,7 @@ def run(a):
 
     # the same step with the reference's materialised outputs.logits [B, L, V] (bf16), on record beside the default line
     logits_full = None
-    if not full and not a.no_logits_full:
+    if a.full and not full and not a.no_logits_full:
         k2 = max(1, a.steps)
         dt2 = timed(k2, max(2, a.warmup), full_logits=True)       # warm-ups: the 1.9 GB logits buffer is first-touched outside the timed region
         logits_full = {"ms_per_step": round(dt2 / k2 * 1e3, 3), "value": round(world * B * 10.0 * k2 / dt2, 1), "steps": k2,
@@ -404,7 +420,7 @@ def run(a):
 
     # the same step with the residual streams stored in the OTHER dtype (config.model_dtype is read at every forward)
     streams_other = None
-    if not a.no_logits_full and not dry:
+    if a.full and not a.no_logits_full and not dry:
         other = "f32" if a.streams == "bf16" else "bf16"
         cfg.model_dtype = mdt[other]
         k5 = max(1, a.steps)
@@ -418,7 +434,7 @@ def run(a):
     # the same step fed from HOST buffers (20.5 MB of f32 waveforms + the token tensors per step over PCIe, pinned, same stream):
     # what the boundary costs when the dataloader hands over host memory.  Never `value`.
     host_inputs = None
-    if not a.no_logits_full and not dry:
+    if a.full and not a.no_logits_full and not dry:
         host.update(wav=wav.cpu().pin_memory(), ids=ids_d.cpu().pin_memory(), att=att_d.cpu().pin_memory(),
                     lab=lab_d.cpu().pin_memory(), cnt=counts_d.cpu().pin_memory())
         k3 = max(1, a.steps)
@@ -429,7 +445,7 @@ def run(a):
         host.clear()
 
     roofline = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # EVERY rank runs the two extra (untimed) steps -- they contain the gradient all-reduce -- but only rank 0
         # records: HIP events around each GEMM launch on the launch stream (csrc/gemm.hip: ta_profile_gemm).
         import ctypes as C
@@ -470,7 +486,7 @@ def run(a):
                         "hbm_kernels": hbm_kernel_rates(B, L, cfg, fe, wav, lens, a.streams)}
 
     cpu, parity = None, None
-    if not a.no_cpu_baseline and rank == 0 and world == 1 and a.projector == "mlp" and not a.lora and a.proj_hidden == 1024 and a.lm == "0.6b" and not a.full_ft:
+    if a.full and not a.no_cpu_baseline and rank == 0 and world == 1 and a.projector == "mlp" and not a.lora and a.proj_hidden == 1024 and a.lm == "0.6b" and not a.full_ft:
         # Untimed: clip 0 alone through the GPU path with the frame dropout off (the timed steps drop 10 % of the frames with a
         # device RNG the oracle cannot replay), against the oracle's loss for the same clip and weights (cpu_baseline computes it).
         # The trainer has updated the projector since step 0: both sides read the CURRENT weights.
@@ -535,6 +551,35 @@ def run(a):
             raise RuntimeError(f"data-parallel replicas diverged: {replicas}")
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMENTS = 7_000_000       # per large array: 28 MB of float32, so parameters + gradients stay under 64 MB in all
+
+
+def dump_outputs(out_dir, trainer):
+    """--dump-outputs: what the last timed optimizer step hands its caller, as DIR/<name>.npy.  `loss` / `grad_norm` (float64):
+    the global mean CE and the pre-clip gradient norm of that step (trainer.last_loss / last_grad_norm); `trainable_params`
+    (float32): the flat fp32 master buffer after its update; `grads` (float32): the flat gradient buffer that update read (not
+    written when the deferred all-reduce mode has already cleared it for the next step).  A buffer longer than
+    DUMP_MAX_ELEMENTS is written as the elements at a fixed, seeded, sorted sample of positions (the same positions on every
+    run of the same configuration)."""
+    os.makedirs(out_dir, exist_ok=True)
+    f = trainer.flat
+    arrays = {"loss": np.array([trainer.last_loss()], dtype=np.float64),
+              "grad_norm": np.array([trainer.last_grad_norm()], dtype=np.float64)}
+    big = {"trainable_params": f.flat_p}
+    if not trainer.overlap_allreduce:
+        big["grads"] = f.grads
+    for name, t in big.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMENTS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 * 10 ** 6, f"--dump-outputs would write {total} bytes"
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def numerics_contract(streams):

@@ -444,6 +444,20 @@ def test_label_rows_and_cross_entropy():
     assert abs(float(loss_b) - float(ref_b)) < 1e-4 * float(ref_b)
 
 
+def test_cross_entropy_loss_is_deterministic():
+    """The loss is the per-row nll summed in row order by one workgroup: the same bits on every call (the bench's 1152 label rows)."""
+    n, V, Vp = 1152, 4093, 4096
+    logits = rnd(n, Vp, seed=21, scale=3.0).to(BF16)
+    tg = torch.randint(0, V, (n,), generator=torch.Generator().manual_seed(22)).to(DEV)
+    runs = [ops.cross_entropy(logits, tg, V, 1.0 / n) for _ in range(3)]
+    for loss, nll, dl in runs[1:]:
+        assert torch.equal(loss, runs[0][0]) and torch.equal(nll, runs[0][1]) and torch.equal(dl, runs[0][2])
+    ref = float(runs[0][1].double().sum() / n)
+    assert abs(float(runs[0][0]) - ref) < 1e-5 * ref
+    ref_t = torch.nn.functional.cross_entropy(logits[:, :V].float(), tg, reduction="sum") / n
+    assert abs(float(runs[0][0]) - float(ref_t)) < 1e-4 * float(ref_t)
+
+
 def test_adamw_and_clip():
     n = 10007
     p0, g = rnd(n, seed=1), rnd(n, seed=2, scale=3.0)

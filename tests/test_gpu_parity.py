@@ -89,6 +89,48 @@ def test_mlp_projector_vs_golden(golden):
         assert relmax(npy(prm.grad), g["g." + k]) < 4e-2, k
 
 
+def test_mlp_projector_backward_full_shape_values_and_bits():
+    """The projector backward at the benchmark's shape (B = 32 clips of 500 encoder frames: 4000 rows, so the norm-weight gradients
+    take the 512-block slab path with several row groups per block): every gradient against an fp32 autograd reference of the same
+    math, and the same bits on every call (the slabs are added in a fixed order)."""
+    E, D, H, B, S = 1280, 1024, 1024, 32, 500
+    cfg = ASRConfig(projector_hidden_dim=H)
+    assert (cfg.encoder_dim, cfg.llm_dim) == (E, D)
+    p = MLPAudioProjector(cfg).to(DEV)
+    w = OW.init_mlp_projector(E, D, H)
+    rng = np.random.RandomState(5)
+    for k in ("norm.weight", "norm_2.weight"):
+        w[k] = (w[k] * (1 + 0.1 * rng.randn(*w[k].shape))).astype(np.float32)
+    p.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()})
+    g = torch.Generator(device="cpu").manual_seed(6)
+    x = torch.randn(B, S, E, generator=g).to(DEV).to(torch.bfloat16)
+    dy = torch.randn(B, S // 4, D, generator=g).to(DEV)
+    runs = []
+    for _ in range(3):
+        for prm in p.parameters():
+            prm.grad = None
+        y = p(x)
+        y.backward(dy)
+        runs.append((y.detach().clone(), {k: prm.grad.detach().clone() for k, prm in p.named_parameters()}))
+    for y, gr in runs[1:]:
+        assert torch.equal(y, runs[0][0])
+        for k in gr:
+            assert torch.equal(gr[k], runs[0][1][k]), k
+    ref = {k: torch.from_numpy(v).to(DEV).requires_grad_(True) for k, v in w.items()}
+
+    def rms(h, wt):
+        return wt * h * torch.rsqrt(h.square().mean(-1, keepdim=True) + 1e-6)
+
+    h1 = x.float().reshape(B, S // 4, 4 * E) @ ref["linear_1.weight"].T
+    a1 = torch.nn.functional.gelu(rms(h1, ref["norm.weight"]))
+    yr = rms(a1 @ ref["linear_2.weight"].T, ref["norm_2.weight"])
+    yr.backward(dy)
+    assert relmax(npy(runs[0][0]), npy(yr)) < 2e-2
+    for k, gk in runs[0][1].items():
+        assert cosine(npy(gk), npy(ref[k].grad)) > 0.999, k
+        assert relmax(npy(gk), npy(ref[k].grad)) < 4e-2, k
+
+
 def test_asr_model_vs_golden(golden):
     g = golden("asr_small.npz")
     S = R.SMALL

@@ -572,7 +572,7 @@ def test_bench_two_ranks_real_kernels_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--share-gpu", "--steps", "4",
-                        "--warmup", "2", "--no-cpu-baseline", "--no-logits-full", "--no-roofline"], capture_output=True, text=True, timeout=600,
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--no-logits-full", "--no-roofline"], capture_output=True, text=True, timeout=600,
                        cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, (r.returncode, r.stdout[-800:], r.stderr[-800:])
@@ -587,6 +587,25 @@ def test_bench_two_ranks_real_kernels_on_one_gpu():
     assert ar["collectives_per_step"] == 1.0
 
 
+def test_bench_dump_outputs_identical_across_runs(tmp_path):
+    """Two runs of `bench.py --dump-outputs` with the same arguments: seeded inputs, and a timed path without order-dependent sums,
+    so every dumped array (loss, gradient norm, parameters after the update, gradients) has the same bits."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, (r.stdout[-800:], r.stderr[-800:])
+        outs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert sorted(outs[0]) == ["grad_norm.npy", "grads.npy", "loss.npy", "trainable_params.npy"]
+    for f, a in outs[0].items():
+        assert np.isfinite(a).all(), f
+        np.testing.assert_array_equal(a, outs[1][f], err_msg=f)
+
+
 @pytest.mark.parametrize("flags,elements", [(["--projector", "moe"], None), (["--lora"], 5046272 + 2),
                                              (["--full-ft", "--batch", "8"], None)], ids=["moe", "lora", "fullft"])
 def test_bench_two_ranks_other_configs_on_one_gpu(flags, elements):
@@ -597,7 +616,7 @@ def test_bench_two_ranks_other_configs_on_one_gpu(flags, elements):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--share-gpu", "--steps", "3",
-                        "--warmup", "2", "--no-cpu-baseline", "--no-logits-full", "--no-roofline", *flags], capture_output=True, text=True,
+                        "--warmup", "2", "--full", "--no-cpu-baseline", "--no-logits-full", "--no-roofline", *flags], capture_output=True, text=True,
                        timeout=900, cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, (r.returncode, r.stdout[-800:], r.stderr[-800:])

@@ -780,7 +780,7 @@ def test_bench_dry_run_two_ranks_end_to_end():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ); env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -791,3 +791,34 @@ def test_bench_dry_run_two_ranks_end_to_end():
     ar = rec["allreduce"]
     assert ar["bytes"] == 4 * ar["elements"] and ar["other_mode"]["mode"] == "synchronous" and ar["other_mode"]["steps"] >= 2
     assert "error" not in rec
+
+
+def test_bench_dry_run_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs the headline only (every other leg is behind --full and null in the
+    line); --dump-outputs writes the last timed step's results as float32 / float64 .npy, at most 64 MB in all.  --full brings the
+    extra legs back (under --dry-run: logits_full; the others need a GPU)."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1",
+                            *extra], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    rec = run("--dump-outputs", str(tmp_path / "out"))
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and "error" not in rec
+    assert all(k in rec for k in ("metric", "value", "unit", "higher_is_better", "dtype"))
+    for k in ("logits_full", "streams_other", "host_inputs", "roofline", "cpu_baseline", "parity", "replicas"):
+        assert rec[k] is None, k
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["grad_norm.npy", "grads.npy", "loss.npy", "trainable_params.npy"]
+    arrs = {f: np.load(tmp_path / "out" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 10 ** 6
+    assert arrs["trainable_params.npy"].shape == arrs["grads.npy"].shape and arrs["trainable_params.npy"].size > 0
+    full = run("--full")
+    assert full["logits_full"] is not None and full["logits_full"]["steps"] == 3

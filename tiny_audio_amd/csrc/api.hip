@@ -127,7 +127,7 @@ MlpTape mlp_tape(const ta_mlp_weights* w, int B, int S, void* base) {
   t.bytes = c.total();
   return t;
 }
-struct MlpBwdWs { float *dh2, *da1, *skws; bf16_t *dh2b, *dh2T, *a1T, *dh1b, *dh1T, *xsT; size_t bytes; };
+struct MlpBwdWs { float *dh2, *da1, *skws, *dgws; bf16_t *dh2b, *dh2T, *a1T, *dh1b, *dh1T, *xsT; size_t bytes; };
 MlpBwdWs mlp_bwd_ws(const ta_mlp_weights* w, int B, int S, void* base) {
   const int N = (S - w->k) / w->k + 1, Hd = w->hidden, D = w->llm_dim, In = w->k * w->enc_dim;
   const long Mp = (long)B * N; const int Kp = pad64((int)Mp);
@@ -144,6 +144,7 @@ MlpBwdWs mlp_bwd_ws(const ta_mlp_weights* w, int B, int S, void* base) {
   const int s1 = pick_splits(Hd, In, Kp), s2 = pick_splits(D, Hd, Kp);
   const size_t sk1 = (size_t)ta_gemm_splitk_ws_bytes(Hd, In, s1), sk2 = (size_t)ta_gemm_splitk_ws_bytes(D, Hd, s2);
   s.skws = c.take<float>((sk1 > sk2 ? sk1 : sk2) / 4 + 4);
+  s.dgws = c.take<float>((size_t)ta_i_rmsnorm_bwd_ws_floats((int)Mp, Hd > D ? Hd : D));   // dg1 / dg2 block slabs, one after the other
   s.bytes = c.total();
   return s;
 }
@@ -183,14 +184,14 @@ extern "C" int ta_mlp_projector_backward(const ta_mlp_weights* w, const void* x,
   if (hipMemsetAsync(dg1, 0, (size_t)Hd * 4, st) != hipSuccess) return TA_ERR_LAUNCH;
   if (hipMemsetAsync(dg2, 0, (size_t)D * 4, st) != hipSuccess) return TA_ERR_LAUNCH;
   // norm_2 backward -> dH2 ; dW2 = dH2^T A1 ; dA1 = dH2 W2
-  RC(ta_rmsnorm_bwd(dy, t.h2, t.r2, w->g2, nullptr, nullptr, s.dh2b, dg2, Mp, D, 0, st));
+  RC(ta_i_rmsnorm_bwd(dy, t.h2, t.r2, w->g2, nullptr, nullptr, s.dh2b, dg2, s.dgws, Mp, D, 0, st));
   RC(ta_transpose_to_bf16(s.dh2b, 0, D, 0, 0, s.dh2T, Kp, Mp, D, st));
   RC(ta_transpose_to_bf16(t.a1, 0, Hd, 0, 0, s.a1T, Kp, Mp, Hd, st));
   const int s2 = pick_splits(D, Hd, Kp);
   RC(ta_gemm_bf16_nt(s.dh2T, s.a1T, dW2, D, Hd, Kp, Kp, 0, 0, Hd, 0, 0, 0, nullptr, nullptr, 0, 0, s2, s.skws, st));
   RC(gemm(s.dh2b, w->w2_t, s.da1, Mp, Hd, D, nullptr, nullptr, 0, 0, st));
   // GELU' + norm backward -> dH1 ; dW1 = dH1^T Xs
-  RC(ta_rmsnorm_bwd(s.da1, t.h1, t.r1, w->g1, nullptr, nullptr, s.dh1b, dg1, Mp, Hd, 1, st));
+  RC(ta_i_rmsnorm_bwd(s.da1, t.h1, t.r1, w->g1, nullptr, nullptr, s.dh1b, dg1, s.dgws, Mp, Hd, 1, st));
   RC(ta_transpose_to_bf16(s.dh1b, 0, Hd, 0, 0, s.dh1T, Kp, Mp, Hd, st));
   RC(ta_transpose_to_bf16(x, 0, In, (long)S * E, N, s.xsT, Kp, Mp, In, st));
   const int s1 = pick_splits(Hd, In, Kp);

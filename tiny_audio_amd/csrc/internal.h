@@ -26,6 +26,12 @@ struct LoraReduceDesc { float* out[8]; long out_ls[8]; long size[8]; long part_o
 int ta_i_lora_reduce_parts(const LoraReduceDesc& d, int layers, hipStream_t st);
 int ta_i_lora_skinny_nt(const void* X, int K, const void* W, void* out, int M, int R, hipStream_t st);   // out[M,64] = X[M,K] W[64,K]^T; rows >= R of W are zero
 
+// ta_rmsnorm_bwd with the weight gradient's per-block slabs in dw_ws (ta_i_rmsnorm_bwd_ws_floats(M, H) floats, no initial contents
+// required): dw_accum += the slabs' sum, in a fixed order (the same bits on every run).  dw_ws null: atomics, as ta_rmsnorm_bwd
+long ta_i_rmsnorm_bwd_ws_floats(int M, int H);
+int ta_i_rmsnorm_bwd(const float* dy, const float* x, const float* rstd, const float* w, const float* dres, float* dx_f32,
+                     void* dx_bf16, float* dw_accum, float* dw_ws, int M, int H, int act_gelu, hipStream_t st);
+
 // fused decode-step kernels for batch <= 32 (csrc/decode_fused.hip); TA_ERR_ARG = outside the envelope, take the unfused path
 bool ta_i_dec_fused_serves(int B, int D, int F, int bq, int Hq, int Hkv, int Lmax);
 // what the NEXT kernel of the step streams, fetched one kernel early by `wgs` extra workgroups (0 = 96): a contiguous range

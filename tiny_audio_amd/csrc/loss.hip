@@ -117,18 +117,40 @@ __global__ __launch_bounds__(1024) void label_rows_kernel(const long* __restrict
   if (tid == 0) n_out[0] = carry;
 }
 
+// loss_accum[0] += scale * sum(nll[0..n)), the rows added in index order by one workgroup: the same loss bits on every run (a float
+// atomicAdd per row sums in whatever order the row blocks finish)
+__global__ __launch_bounds__(1024) void nll_sum_kernel(const float* __restrict__ nll, int n, float scale, float* __restrict__ loss_accum) {
+  __shared__ float red[16];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 1024) s += nll[i] * scale;
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int w = 0; w < 16; ++w) t += red[w];
+    loss_accum[0] += t;
+  }
+}
+
 extern "C" int ta_cross_entropy(const void* logits, int logits_bf16, long ldl, const int* rows, const long* targets,
                                 int n, int V, float scale, float* nll, float* loss_accum, void* dlogits_bf16, long ldd,
                                 hipStream_t st) {
   if (n <= 0) return TA_OK;
   if ((ldl % 4) || (dlogits_bf16 && (ldd % 4))) return TA_ERR_ARG;
+  // with an nll buffer the loss is summed from it in row order (nll_sum_kernel); without one, each row adds itself atomically
+  float* atomic_loss = nll ? nullptr : loss_accum;
   if (logits_bf16)
     TA_LAUNCH((ce_fwd_bwd_kernel<bf16_t>), dim3(n), dim3(256), 0, st, (const bf16_t*)logits, ldl, rows, targets, V,
-                       scale, nll, loss_accum, (bf16_t*)dlogits_bf16, ldd);
+                       scale, nll, atomic_loss, (bf16_t*)dlogits_bf16, ldd);
   else
     TA_LAUNCH((ce_fwd_bwd_kernel<float>), dim3(n), dim3(256), 0, st, (const float*)logits, ldl, rows, targets, V,
-                       scale, nll, loss_accum, (bf16_t*)dlogits_bf16, ldd);
+                       scale, nll, atomic_loss, (bf16_t*)dlogits_bf16, ldd);
   TA_CHECK_LAUNCH();
+  if (loss_accum && nll) {
+    TA_LAUNCH(nll_sum_kernel, dim3(1), dim3(1024), 0, st, nll, n, scale, loss_accum);
+    TA_CHECK_LAUNCH();
+  }
   return TA_OK;
 }
 

@@ -332,23 +332,34 @@ __global__ __launch_bounds__(256) void rmsnorm_fwd_kernel(const float* __restric
 // Backward of y = act(w * x * rstd):
 //   dn = dy * act'(n)           (ACT==1, n = w*x*rstd recomputed)
 //   dx = rstd * (dn*w - xh * mean(dn*w*xh)),  xh = x*rstd        (+ dres if given)
-//   dw += sum_rows dn * xh      (if dw != null; LDS partials + one atomicAdd per column per block)
+// DWM (weight gradient mode):
+//   1 if dw != null: dw += sum_rows dn * xh with LDS partials + one atomicAdd per column per block (every launch without a workspace,
+//     the exported ta_rmsnorm_bwd among them; the order of the float additions, hence the last bits, may change from run to run);
+//   2 dw[block][:] = sum over the block's rows of dn * xh, then rmsnorm_dw_fold_kernel adds the blocks' slabs in order.  A lane keeps
+//     its columns' sums in registers over the rows of its wave and the 4 waves fold through LDS in wave order: no float atomics, the
+//     same bits on every run (the projector backward, which lends the slabs from its workspace).
 // DRES_BF16 (round 4): the residual gradient `dres` is bf16 and may BE the output image dxb (in place: a lane reads its four
 // elements before it writes them) -- the LM's d(x) stream kept in bf16, the dtype the reference's bf16 model back-propagates in
-template <int MAXV, int ACT, bool X_BF16 = false, bool DY_BF16 = false, bool DRES_BF16 = false>
+template <int MAXV, int ACT, bool X_BF16 = false, bool DY_BF16 = false, bool DRES_BF16 = false, int DWM = 1>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                           const float* __restrict__ rstd_in,
                                                           const float* __restrict__ w, const float* dres,
                                                           float* dxf, bf16_t* dxb,
                                                           float* __restrict__ dw, int M, int H) {
-  extern __shared__ float dw_part[];   // [H] when dw != null
+  extern __shared__ float dw_lds[];   // [H] when dw != null
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int nv = H >> 2;
-  if (dw) {
-    for (int i = threadIdx.x; i < H; i += 256) dw_part[i] = 0.f;
+  constexpr int NA = DWM == 2 ? MAXV : 1;
+  float4 dwa[NA];
+  if constexpr (DWM == 2) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) dwa[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if (DWM == 1 && dw) {
+    for (int i = threadIdx.x; i < H; i += 256) dw_lds[i] = 0.f;
     __syncthreads();
   }
-  // each block handles rows_per_block consecutive groups of 4 rows (grid-stride) so dw atomics stay few
+  // each block handles rows_per_block consecutive groups of 4 rows (grid-stride) so dw atomics / slabs stay few
   for (int row0 = blockIdx.x * 4; row0 < M; row0 += gridDim.x * 4) {
     const int row = row0 + wv;
     if (row < M) {
@@ -374,9 +385,12 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restric
             d.x *= gelu_erf_grad(xh[i].x * ww.x); d.y *= gelu_erf_grad(xh[i].y * ww.y);
             d.z *= gelu_erf_grad(xh[i].z * ww.z); d.w *= gelu_erf_grad(xh[i].w * ww.w);
           }
-          if (dw) {
-            atomicAdd(&dw_part[c * 4 + 0], d.x * xh[i].x); atomicAdd(&dw_part[c * 4 + 1], d.y * xh[i].y);
-            atomicAdd(&dw_part[c * 4 + 2], d.z * xh[i].z); atomicAdd(&dw_part[c * 4 + 3], d.w * xh[i].w);
+          if (DWM == 1 && dw) {
+            atomicAdd(&dw_lds[c * 4 + 0], d.x * xh[i].x); atomicAdd(&dw_lds[c * 4 + 1], d.y * xh[i].y);
+            atomicAdd(&dw_lds[c * 4 + 2], d.z * xh[i].z); atomicAdd(&dw_lds[c * 4 + 3], d.w * xh[i].w);
+          }
+          if constexpr (DWM == 2) {
+            dwa[i].x += d.x * xh[i].x; dwa[i].y += d.y * xh[i].y; dwa[i].z += d.z * xh[i].z; dwa[i].w += d.w * xh[i].w;
           }
           dn[i] = make_float4(d.x * ww.x, d.y * ww.y, d.z * ww.z, d.w * ww.w);
           dot += dn[i].x * xh[i].x + dn[i].y * xh[i].y + dn[i].z * xh[i].z + dn[i].w * xh[i].w;
@@ -408,9 +422,48 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const float* __restric
       }
     }
   }
-  if (dw) {
+  if (DWM == 1 && dw) {
     __syncthreads();
-    for (int i = threadIdx.x; i < H; i += 256) atomicAdd(&dw[i], dw_part[i]);
+    for (int i = threadIdx.x; i < H; i += 256) atomicAdd(&dw[i], dw_lds[i]);
+  }
+  if constexpr (DWM == 2) {
+    for (int v = 0; v < 4; ++v) {       // wave 0 stores, waves 1..3 add, in this order
+      if (wv == v) {
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+          const int c = lane + i * 64;
+          if (c < nv) {
+            float4* p = (float4*)dw_lds + c;
+            if (v == 0) *p = dwa[i];
+            else { float4 q = *p; q.x += dwa[i].x; q.y += dwa[i].y; q.z += dwa[i].z; q.w += dwa[i].w; *p = q; }
+          }
+        }
+      }
+      __syncthreads();
+    }
+    for (int i = threadIdx.x; i < H; i += 256) dw[(long)blockIdx.x * H + i] = dw_lds[i];
+  }
+}
+
+// dw[c] += sum over the G slabs of rmsnorm_bwd_kernel<..., DWM = 2>, in slab order: 16 slab groups x 16 float4 columns per workgroup,
+// group g adds slabs g, g + 16, ... and the 16 groups fold through LDS in group order
+__global__ __launch_bounds__(256) void rmsnorm_dw_fold_kernel(const float* __restrict__ part, int G, int H, float* __restrict__ dw) {
+  __shared__ float4 red[16][16];
+  const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int c4 = blockIdx.x * 16 + q, nv = H >> 2;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c4 < nv)
+    for (int b = g; b < G; b += 16) {
+      const float4 v = ((const float4*)(part + (long)b * H))[c4];
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  red[g][q] = s;
+  __syncthreads();
+  if (g == 0 && c4 < nv) {
+    float4 t = red[0][q];
+    for (int k = 1; k < 16; ++k) { t.x += red[k][q].x; t.y += red[k][q].y; t.z += red[k][q].z; t.w += red[k][q].w; }
+    float* o = dw + c4 * 4;
+    o[0] += t.x; o[1] += t.y; o[2] += t.z; o[3] += t.w;
   }
 }
 
@@ -649,24 +702,41 @@ extern "C" int ta_rmsnorm_bwd_dyb(const void* dy_bf16, const float* x, const flo
   return TA_OK;
 }
 
+// rows of 4 per block; with a weight gradient at most 512 blocks (DWM = 2: each storing one slab of dw_ws)
+static int rmsnorm_bwd_blocks(int M, bool dw) {
+  const int blocks = ta_cdiv(M, 4);
+  return dw && blocks > 512 ? 512 : blocks;
+}
+long ta_i_rmsnorm_bwd_ws_floats(int M, int H) { return M > 0 ? (long)rmsnorm_bwd_blocks(M, true) * H : 0; }
+
+int ta_i_rmsnorm_bwd(const float* dy, const float* x, const float* rstd, const float* w, const float* dres, float* dx_f32,
+                     void* dx_bf16, float* dw_accum, float* dw_ws, int M, int H, int act_gelu, hipStream_t st) {
+  if (M <= 0) return TA_OK;
+  if ((H & 3) || H > 64 * 4 * MAXV_LIMIT) return TA_ERR_ARG;
+  const int blocks = rmsnorm_bwd_blocks(M, dw_accum != nullptr);
+  const size_t lds = dw_accum ? (size_t)H * 4 : 0;
+#define RB_LAUNCH(V, A, MODE, DWP) \
+  TA_LAUNCH((rmsnorm_bwd_kernel<V, A, false, false, false, MODE>), dim3(blocks), dim3(256), lds, st, dy, x, rstd, w, dres, dx_f32, \
+            (bf16_t*)dx_bf16, DWP, M, H)
+#define RB_CALL(V)                                                                            \
+  if (dw_accum && dw_ws) { if (act_gelu) RB_LAUNCH(V, 1, 2, dw_ws); else RB_LAUNCH(V, 0, 2, dw_ws); }          \
+  else { if (act_gelu) RB_LAUNCH(V, 1, 1, dw_accum); else RB_LAUNCH(V, 0, 1, dw_accum); }
+  DISPATCH_MAXV(H, RB_CALL);
+#undef RB_CALL
+#undef RB_LAUNCH
+  TA_CHECK_LAUNCH();
+  if (dw_accum && dw_ws) {
+    TA_LAUNCH(rmsnorm_dw_fold_kernel, dim3(ta_cdiv(H / 4, 16)), dim3(256), 0, st, (const float*)dw_ws, blocks, H, dw_accum);
+    TA_CHECK_LAUNCH();
+  }
+  return TA_OK;
+}
+
+// The exported form has no workspace in its ABI: its weight gradient is accumulated with atomics (DWM = 1)
 extern "C" int ta_rmsnorm_bwd(const float* dy, const float* x, const float* rstd, const float* w,
                               const float* dres, float* dx_f32, void* dx_bf16, float* dw_accum,
                               int M, int H, int act_gelu, hipStream_t st) {
-  if (M <= 0) return TA_OK;
-  if ((H & 3) || H > 64 * 4 * MAXV_LIMIT) return TA_ERR_ARG;
-  int blocks = ta_cdiv(M, 4);
-  if (dw_accum && blocks > 512) blocks = 512;
-  const size_t lds = dw_accum ? (size_t)H * 4 : 0;
-#define RB_CALL(V)                                                                                             \
-  if (act_gelu)                                                                                                \
-    TA_LAUNCH((rmsnorm_bwd_kernel<V, 1>), dim3(blocks), dim3(256), lds, st, dy, x, rstd, w, dres,     \
-                       dx_f32, (bf16_t*)dx_bf16, dw_accum, M, H);                                              \
-  else                                                                                                         \
-    TA_LAUNCH((rmsnorm_bwd_kernel<V, 0>), dim3(blocks), dim3(256), lds, st, dy, x, rstd, w, dres,     \
-                       dx_f32, (bf16_t*)dx_bf16, dw_accum, M, H);
-  DISPATCH_MAXV(H, RB_CALL);
-  TA_CHECK_LAUNCH();
-  return TA_OK;
+  return ta_i_rmsnorm_bwd(dy, x, rstd, w, dres, dx_f32, dx_bf16, dw_accum, nullptr, M, H, act_gelu, st);
 }
 
 
