@@ -343,6 +343,39 @@ int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const int* kmask,
                    const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wgrads, const long* ids, const void* tape, void* ws,
                    long ws_bytes, hipStream_t st);
 
+/* ---- LoRA dropout (peft LoraLayer with lora_dropout = p > 0; tiny_audio/asr_modeling.py:289-301 forwards config.lora_dropout
+ * to LoraConfig).  In TRAINING mode every adapted linear j has its own nn.Dropout(p) on the adapter's input:
+ *     y_j = W_j x + s B_j A_j (x (.) K_j / (1 - p)),    s = alpha / r,  K_j ~ Bernoulli(1 - p) per element of x,
+ * so the members of the q|k|v and gate|up groups see the same x under three / two independent masks.  The backward uses the
+ * forward's masks: dB_j = dy_j^T xa_j (xa already holds the dropped product), dA_j = s (dy_j B_j)^T (x (.) K_j / (1 - p)) and
+ * d(x) += sum_j (s (dy_j B_j) A_j) (.) K_j / (1 - p).  Evaluation and decoding never apply dropout (no descriptor there).
+ *
+ * Masks are never stored: the keep decision of element (m, c) of linear j (peft order q, k, v, o, gate, up, down = 0..6) in
+ * decoder layer l, m the row of the [B*L] row space, is a pure function of (seed, offset, l, j, m, c) -- Philox4x32-10 with
+ *     counter = ((8 l + j) << 20 | c >> 3,  m,  lo32(offset),  hi32(offset)),   key = (lo32(seed), hi32(seed)),
+ * 16-bit half (c & 1) (low half first) of output word (c & 7) >> 1 = u16;  keep <=> u16 >= round(p * 65536).
+ * One call decides 8 consecutive columns; the DROP probability is p rounded to a multiple of 2^-16 (the kept values are scaled by
+ * 1 / (1 - p) with p as given).  Valid for in_features < 2^23 and n_layers < 512.  The backward regenerates what its forward drew,
+ * so it must get the SAME descriptor; ta_lm_tape_bytes does not depend on it.  tiny_audio_amd/lora_dropout.py is a numpy twin. */
+typedef struct ta_lora_dropout {
+  float p;                          /* 0 <= p < 1; 0 = off */
+  unsigned long long seed;          /* Philox key */
+  unsigned long long offset;        /* Philox counter words 2-3: a fresh value per training forward (and per rank) */
+} ta_lora_dropout;
+/* ta_lm_forward_loss / ta_lm_backward with LoRA dropout: drop NULL or drop->p == 0 is exactly the plain call (the plain entry
+ * points are these with NULL).  drop->p > 0 needs w->lora_rank > 0. */
+int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                          const int* kmask, const int* pos, int B, int L, const int* label_rows,
+                          const long* label_targets, int n_label_rows, float loss_scale, float* loss,
+                          float* nll_rows, void* logits_out, void* tape, void* ws, long ws_bytes,
+                          const ta_lora_dropout* drop, hipStream_t st);
+int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
+                      const int* label_rows, int n_label_rows, float* d_audio, long n_audio_rows, float* d_embeds,
+                      const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wgrads, const long* ids, const void* tape, void* ws,
+                      long ws_bytes, const ta_lora_dropout* drop, hipStream_t st);
+/* The keep mask of linear `linear` (0..6, peft order) in layer `layer` over M rows x in columns: out u8 [M, in] (1 = kept). */
+int ta_lora_dropout_keep(const ta_lora_dropout* drop, int layer, int linear, int M, int in, unsigned char* out, hipStream_t st);
+
 /* ============================================================================================
  * Primitive kernels (exported for the parity tests; also what the composites are built from)
  * ============================================================================================ */

@@ -85,6 +85,11 @@ class LmWeights(C.Structure):
                 ("lora_groups", C.c_int), ("res_f32", C.c_int), ("dx_f32", C.c_int)]
 
 
+class LoraDropout(C.Structure):
+    """ta_lora_dropout (include/ta355.h): p, Philox seed, Philox offset of one training forward and its backward."""
+    _fields_ = [("p", C.c_float), ("seed", C.c_ulonglong), ("offset", C.c_ulonglong)]
+
+
 class LmLayerWgrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dwqkv", "dwo", "dwgu", "dwd", "dln_in", "dln_post", "dqn", "dkn")]
 

@@ -356,7 +356,7 @@ extern "C" long ta_lm_workspace_bytes(const ta_lm_weights* w, int B, int L, int 
 // tape (generation keeps them across decode steps); kcache/vcache: see ta_lm_prefill.
 static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int L, const int* kmask, const int* pos,
                              LmLayerTape* store, bool alias, float* x_final, LmWs& s, const ta_i_lora_layer_imgs* ext,
-                             bf16_t* kcache, bf16_t* vcache, int Lmax, hipStream_t st) {
+                             bf16_t* kcache, bf16_t* vcache, int Lmax, hipStream_t st, const LoraDropDev* drop = nullptr) {
   const int M = (int)d.M;
   const float scale = 1.0f / sqrtf((float)d.hd);
   const bool lora = w->lora_rank > 0;
@@ -365,8 +365,10 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
   const int lgm = lora ? (w->lora_groups ? w->lora_groups : 15) : 0;      // groups that carry an adapter (1 qkv, 2 o, 4 gate|up, 8 down)
   // y = x W^T + xa Bext^T with xa = x (s Acat)^T: one skinny GEMM for xa, then the frozen GEMM runs one extra K-tile
   ta_gemm_opts kx = opts_none();                     // K extension of the NEXT frozen GEMM (consumed and cleared by it)
-  auto lora_fwd = [&](const bf16_t* x, int in, const LoraImg& g, bf16_t* xa, int members) -> int {
-    RC(ta_i_lora_skinny_nt(x, in, g.a, xa, M, members * r, st));
+  // LoRA dropout (training forwards only): xa = (x (.) K_j / (1 - p)) (s A_j)^T per member j = linear lj0 + j; the K extension is unchanged
+  auto lora_fwd = [&](const bf16_t* x, int in, const LoraImg& g, bf16_t* xa, int members, int lj0) -> int {
+    if (drop) RC(ta_i_lora_skinny_nt_drop(x, in, g.a, xa, M, LoraDrop{*drop, (unsigned)lj0, r, members}, st));
+    else RC(ta_i_lora_skinny_nt(x, in, g.a, xa, M, members * r, st));
     kx = opts_kext(xa, g.b);
     return TA_OK;
   };
@@ -434,7 +436,7 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
       return gemm_opt(A, Wm, out, M, d.D, K, nullptr, res, 0, 0, o, st);
     };
     RC(norm(p.x_in, Lw.ln_in_w, xn, p.r_in));
-    if (lgm & 1) RC(lora_fwd(xn, d.D, p.i_qkv, p.xa_qkv, 3));
+    if (lgm & 1) RC(lora_fwd(xn, d.D, p.i_qkv, p.xa_qkv, 3, 8 * l + 0));
     RC(gemm_opt(xn, Lw.wqkv, p.qkv0, M, d.NQKV, d.D, nullptr, nullptr, 0, 1, take_ext(), st));
     // short causal sequences: QK-norm + RoPE + head split ride in the attention kernel's staging; longer ones take two kernels
     const bool fused_fwd = lm_attn_fused(d, L);
@@ -453,15 +455,15 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
         return TA_ERR_LAUNCH;
     }
     if (!fused_fwd) RC(ta_attention_fwd(p.q, p.k, p.vt, p.ao, p.lse, kmask, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
-    if (lgm & 2) RC(lora_fwd(p.ao, d.nq * d.hd, p.i_o, p.xa_o, 1));
+    if (lgm & 2) RC(lora_fwd(p.ao, d.nq * d.hd, p.i_o, p.xa_o, 1, 8 * l + 3));
     RC(res_gemm(p.ao, Lw.wo, p.x1, d.nq * d.hd, p.x_in));
     bf16_t* xn2 = keep ? p.xn2_s : s.xn;
     bf16_t* act = keep ? p.act_s : s.act;
     RC(norm(p.x1, Lw.ln_post_w, xn2, p.r_post));
-    if (lgm & 4) RC(lora_fwd(xn2, d.D, p.i_gu, p.xa_gu, 2));
+    if (lgm & 4) RC(lora_fwd(xn2, d.D, p.i_gu, p.xa_gu, 2, 8 * l + 4));
     RC(gemm_opt(xn2, Lw.wgu, p.gu, M, 2 * d.F, d.D, nullptr, nullptr, 0, 1, take_ext(), st));
     RC(ta_swiglu_fwd(p.gu, act, M, d.F, st));
-    if (lgm & 8) RC(lora_fwd(act, d.F, p.i_d, p.xa_d, 1));
+    if (lgm & 8) RC(lora_fwd(act, d.F, p.i_d, p.xa_d, 1, 8 * l + 6));
     RC(res_gemm(act, Lw.wd, x_next, d.F, p.x1));
   }
   return TA_OK;
@@ -471,6 +473,27 @@ extern "C" int ta_lm_forward_loss(const ta_lm_weights* w, const long* ids, const
                                   const int* kmask, const int* pos, int B, int L, const int* label_rows,
                                   const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
                                   void* logits_out, void* tape, void* ws, long ws_bytes, hipStream_t st) {
+  return ta_lm_forward_loss_ex(w, ids, src_row, audio, kmask, pos, B, L, label_rows, label_targets, n_lab, loss_scale, loss, nll_rows,
+                               logits_out, tape, ws, ws_bytes, nullptr, st);
+}
+// LoRA dropout descriptor -> device form (nullptr = off); TA_ERR_ARG for p outside [0, 1) or p > 0 without adapters
+static int lm_lora_drop(const ta_lm_weights* w, const ta_lora_dropout* drop, LoraDropDev* dd, const LoraDropDev** out) {
+  *out = nullptr;
+  if (!drop) return TA_OK;
+  if (!(drop->p >= 0.f) || !(drop->p < 1.f) || w->n_layers >= 512 || w->ffn >= (1 << 23) || w->hidden >= (1 << 23)) return TA_ERR_ARG;
+  if (!ta_i_lora_drop_dev(drop, dd)) return TA_OK;
+  if (w->lora_rank <= 0 || w->train_base) return TA_ERR_ARG;
+  *out = dd;
+  return TA_OK;
+}
+extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                                     const int* kmask, const int* pos, int B, int L, const int* label_rows,
+                                     const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
+                                     void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
+                                     hipStream_t st) {
+  LoraDropDev dd;
+  const LoraDropDev* dp = nullptr;
+  RC(lm_lora_drop(w, drop, &dd, &dp));
   if (B <= 0 || L <= 0) return TA_OK;
   if (w->n_layers > MAX_LM_LAYERS || w->head_dim != 128 || w->hidden % 128 || w->ffn % 64 || w->vocab_pad % 128 ||
       w->vocab > w->vocab_pad || L > w->max_pos)
@@ -485,7 +508,7 @@ extern "C" int ta_lm_forward_loss(const ta_lm_weights* w, const long* ids, const
   // inputs_embeds = embed_tokens(ids) with the <audio> rows replaced by projector rows (asr_modeling.py:498,511-515)
   if (lm_res_bf16(w)) RC(ta_embed_scatter(ids, src_row, w->embed_f32, audio, nullptr, x, M, d.D, w->vocab, st));
   else RC(ta_embed_scatter(ids, src_row, w->embed_f32, audio, x, nullptr, M, d.D, w->vocab, st));
-  RC(lm_layers_forward(w, d, B, L, kmask, pos, store, false, t.x_final, s, nullptr, nullptr, nullptr, 0, st));
+  RC(lm_layers_forward(w, d, B, L, kmask, pos, store, false, t.x_final, s, nullptr, nullptr, nullptr, 0, st, dp));
   if (lm_res_bf16(w)) RC(ta_rmsnorm_fwd_bf16(t.x_final, w->norm_w, t.hn, nullptr, t.r_f, M, d.D, w->eps, st));
   else RC(ta_rmsnorm_fwd(t.x_final, w->norm_w, t.hn, nullptr, t.r_f, M, d.D, w->eps, 0, st));
   if (logits_out)   // the reference's outputs.logits (bf16 under autocast), all positions
@@ -553,6 +576,16 @@ extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const 
                               const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
                               const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
                               void* ws, long ws_bytes, hipStream_t st) {
+  return ta_lm_backward_ex(w, src_row, kmask, pos, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids, tape,
+                           ws, ws_bytes, nullptr, st);
+}
+extern "C" int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
+                                 const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                                 const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                                 void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
+  LoraDropDev dd;
+  const LoraDropDev* dp = nullptr;
+  RC(lm_lora_drop(w, drop, &dd, &dp));
   if (B <= 0 || L <= 0) return TA_OK;
   if (w->n_layers > MAX_LM_LAYERS) return TA_ERR_ARG;
   const bool lora = w->lora_rank > 0;
@@ -611,18 +644,37 @@ extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const 
   //   dx  = dy W + dyB (sAcat) (K extension of the dX GEMM) dAcat = s (dyB)^T x
   // `arm` only prepares the K extension; the caller then issues the frozen dX GEMM.
   ta_gemm_opts kx = opts_none();                     // K extension of the NEXT frozen dX GEMM
+  // LoRA dropout: the masked rank-space term sum_j K_j (.) (dyB_j s A_j) / (1 - p) cannot be a K extension (the mask is on the GEMM's
+  // output side); it is added in place to the frozen dX GEMM's bf16 output right after that GEMM (dx_drop_term)
+  LoraDrop pend{};
+  const bf16_t* pend_at = nullptr;
   auto lora_bwd = [&](const bf16_t* dy, int N, const bf16_t* x, int in, const bf16_t* xa, const LoraImg& g, float* dla,
                       float* dlb, int members, int b0, int b1, int layer, int grp) -> int {
+    static const int lj_base[4] = {0, 3, 4, 6};          // peft order q, k, v, o, gate, up, down of each group's first member
     RC(ta_i_lora_skinny_nt(dy, N, g.bt, s.dyB, M, members * r, st));
     // dB = dy^T xa and dA = s (dy B)^T x in ONE launch (round 3); per-chunk partial sums when the gradients are stacked (round 4)
     float* pb = lora_parts ? s.lora_part + (long)layer * s.lp_layer + s.lp_off[2 * grp + 1] : nullptr;
     float* pa = lora_parts ? s.lora_part + (long)layer * s.lp_layer + s.lp_off[2 * grp] : nullptr;
+    if (dp) {
+      // dA = s / (1 - p) (dy B)^T (x (.) K_j): the forward's masks, regenerated
+      pend = LoraDrop{*dp, (unsigned)(8 * layer + lj_base[grp]), r, members};
+      RC(ta_i_lora_skinny_tn2(dy, N, xa, members * r, dlb, r, 1, 1.0f, r, b0, b1, x, in, s.dyB, members * r, dla, 1, in,
+                              w->lora_scale * dp->inv_keep, 0, 0, 0, M, pb, s.lp_size[2 * grp + 1], pa, s.lp_size[2 * grp], st, &pend));
+      pend_at = g.at;
+      return TA_OK;
+    }
     RC(ta_i_lora_skinny_tn2(dy, N, xa, members * r, dlb, r, 1, 1.0f, r, b0, b1, x, in, s.dyB, members * r, dla, 1, in, w->lora_scale,
                             0, 0, 0, M, pb, s.lp_size[2 * grp + 1], pa, s.lp_size[2 * grp], st));
     kx = opts_kext(s.dyB, g.at);
     return TA_OK;
   };
   auto take_ext = [&]() { const ta_gemm_opts o = kx; kx = opts_none(); return o; };
+  auto dx_drop_term = [&](void* out, int in) -> int {     // after the frozen dX GEMM whose adapter group ran lora_bwd under dropout
+    if (!pend_at) return TA_OK;
+    const bf16_t* at = pend_at;
+    pend_at = nullptr;
+    return ta_i_lora_dx_drop(s.dyB, at, out, M, in, pend, st);
+  };
   // d hidden (labelled rows) = dlogits x E   (split-K over the vocabulary), scattered back to all positions
   const int sp = pick_splits(n_lab, d.D, w->vocab_pad);
   RC(ta_gemm_bf16_nt(t.dlogits, w->embed_t_bf16, s.dhl, n_lab, d.D, w->vocab_pad, w->vocab_pad, 0, 0, d.D, 0, 0, 0, nullptr,
@@ -685,16 +737,19 @@ extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const 
     // (Fusing the SwiGLU backward into this GEMM's epilogue measured 0.4 ms per step SLOWER -- at one workgroup per CU nothing overlaps
     // an epilogue, so bytes moved there cost more than the separate streaming kernel at 6 TB/s; the form left the library in round 5.)
     RC(gemm_opt(s.dxb, Lw.wd_t, s.dact, M, d.F, d.D, nullptr, nullptr, 0, 1, take_ext(), st));
+    RC(dx_drop_term(s.dact, d.F));
     RC(ta_swiglu_bwd(s.dact, p.gu, s.dgu, M, d.F, st));
     if (lgm & 4) RC(lora_bwd(s.dgu, 2 * d.F, p.xn2_s, d.D, p.xa_gu, p.i_gu, lora_grads[l].dla_gu, lora_grads[l].dlb_gu, 2, d.F, 1 << 30, l, 2));
     if (g) RC(wgrad(s.dgu, 2 * d.F, p.xn2_s, d.D, g->dwgu));
     RC(gemm_opt(s.dgu, Lw.wgu_t, s.dxn, M, d.D, 2 * d.F, nullptr, nullptr, 0, gb, take_ext(), st));
+    RC(dx_drop_term(s.dxn, d.D));
     if (g && g->dln_post) RC(ta_rmsnorm_dw(s.dxn, gb, p.x1, lm_res_bf16(w), p.r_post, g->dln_post, M, d.D, st));
     RC(norm_bwd(s.dxn, gb, p.x1, p.r_post, Lw.ln_post_w, dx, dx_alt));
     // ---- attention: x1 = x + o_proj(attn)
     if (lgm & 2) RC(lora_bwd(s.dxb, d.D, p.ao, bq, p.xa_o, p.i_o, lora_grads[l].dla_o, lora_grads[l].dlb_o, 1, 1 << 30, 1 << 30, l, 1));
     if (g) RC(wgrad(s.dxb, d.D, p.ao, bq, g->dwo));
     RC(gemm_opt(s.dxb, Lw.wo_t, s.dao, M, d.nq * d.hd, d.D, nullptr, nullptr, 0, 1, take_ext(), st));
+    RC(dx_drop_term(s.dao, d.nq * d.hd));
     // frozen q_norm / k_norm: the q|k|v post-processing backward rides in the attention backward's epilogue; trainable norms (full
     // fine-tuning) take head-major dQ / dK / dV + ta_lm_qkv_post_bwd, which also produces d(q_norm) / d(k_norm).
     // (Round 4 built two more forms and removed them in round 5 after measuring them slower: one workgroup per (clip, kv head) with
@@ -713,6 +768,7 @@ extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const 
     if (g) RC(wgrad(s.dqkv, d.NQKV, p.xn_s, d.D, g->dwqkv));
     if (lgm & 1) RC(lora_bwd(s.dqkv, d.NQKV, p.xn_s, d.D, p.xa_qkv, p.i_qkv, lora_grads[l].dla_qkv, lora_grads[l].dlb_qkv, 3, bq, bk, l, 0));
     RC(gemm_opt(s.dqkv, Lw.wqkv_t, s.dxn, M, d.D, d.NQKV, nullptr, nullptr, 0, gb, take_ext(), st));
+    RC(dx_drop_term(s.dxn, d.D));
     if (g && g->dln_in) RC(ta_rmsnorm_dw(s.dxn, gb, p.x_in, lm_res_bf16(w), p.r_in, g->dln_in, M, d.D, st));
     RC(norm_bwd(s.dxn, gb, p.x_in, p.r_in, Lw.ln_in_w, dx_alt, dx, l == 0));
   }

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include "host_util.h"
 #include "internal.h"
+#include "philox.h"
 
 static bool read_decode_fused() { const char* e = getenv("TA355_DECODE_FUSED"); return !(e && *e == '0'); }
 static bool g_decode_fused = read_decode_fused();                 // read at load; ta_gemm_reload_knobs() re-reads it (the tests compare both sequences)
@@ -581,15 +582,8 @@ extern "C" int ta_logits_warp(float* logits, long ld, int V, int B, float temper
 
 // Philox4x32-10 (Salmon et al. 2011): counter (step, row, 0, 0), key = the 64-bit seed -> one uniform in [0, 1) per row and step
 __device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigned step, unsigned row) {
-  unsigned c0 = step, c1 = row, c2 = 0u, c3 = 0u, k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return (float)(c0 >> 8) * (1.0f / 16777216.0f);
+  const uint4 w = philox4x32_10(step, row, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32));
+  return (float)(w.x >> 8) * (1.0f / 16777216.0f);
 }
 // out[b] ~ softmax(logits[b, :V]) (multinomial, one draw): inverse CDF in INDEX order -- thread t owns the contiguous chunk
 // [t * per, (t + 1) * per), an exclusive scan of the chunk masses finds the chunk, its owner walks it.

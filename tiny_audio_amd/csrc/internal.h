@@ -19,12 +19,21 @@ int ta_i_lora_skinny_tn(const void* X, int Cn, const void* Y, int ldy, int R, fl
 int ta_i_lora_skinny_tn2(const void* X0, int Cn0, const void* Y0, int R0, float* out0, long so_c0, long so_j0, float post0, int r0,
                          int b00, int b10, const void* X1, int Cn1, const void* Y1, int R1, float* out1, long so_c1, long so_j1,
                          float post1, int r1, int b01, int b11, int M, float* part0, long part_cs0, float* part1, long part_cs1,
-                         hipStream_t st);   // two TN products, one launch; part != NULL: row chunk c stores at part + c * part_cs (no atomics)
+                         hipStream_t st, const struct LoraDrop* drop = nullptr);   // two TN products, one launch; part != NULL: row chunk c stores at part + c * part_cs (no atomics); drop: problem 1 is dA under LoRA dropout
 int ta_i_lora_tn2_rows(int M, int Cn0, int Cn1);   // rows per chunk of such a launch (chunks = ceil(M / rows))
 // the second level of the adapter-gradient reduction: 8 gradient kinds x layers in one launch
 struct LoraReduceDesc { float* out[8]; long out_ls[8]; long size[8]; long part_off[8]; int chunks[8]; const float* part; long part_ls; };
 int ta_i_lora_reduce_parts(const LoraReduceDesc& d, int layers, hipStream_t st);
 int ta_i_lora_skinny_nt(const void* X, int K, const void* W, void* out, int M, int R, hipStream_t st);   // out[M,64] = X[M,K] W[64,K]^T; rows >= R of W are zero
+// LoRA dropout (csrc/philox.h defines the masks; include/ta355.h ta_lora_dropout): one adapter group's masks and scale
+#include "philox.h"
+struct LoraDrop { LoraDropDev d; unsigned lj0; int r, nmem; };   // linears lj0 .. lj0 + nmem - 1 (lj = 8 layer + peft index), rank r
+struct ta_lora_dropout;
+bool ta_i_lora_drop_dev(const ta_lora_dropout* desc, LoraDropDev* out);   // false: dropout off (NULL or p == 0)
+// xa = (x (.) K_j / (1 - p)) (s A_j)^T per member j (W = the s*Acat image as for ta_i_lora_skinny_nt)
+int ta_i_lora_skinny_nt_drop(const void* X, int K, const void* W, void* out, int M, const LoraDrop& dp, hipStream_t st);
+// out[M, in] (bf16, in place) += sum_j K_j (.) (U_j (s A_j)) / (1 - p);  U = dY Bext [M, 64], AT = (s Acat)^T [in, 64]
+int ta_i_lora_dx_drop(const void* U, const void* AT, void* out, int M, int in, const LoraDrop& dp, hipStream_t st);
 
 // ta_rmsnorm_bwd with the weight gradient's per-block slabs in dw_ws (ta_i_rmsnorm_bwd_ws_floats(M, H) floats, no initial contents
 // required): dw_accum += the slabs' sum, in a fixed order (the same bits on every run).  dw_ws null: atomics, as ta_rmsnorm_bwd

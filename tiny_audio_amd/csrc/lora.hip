@@ -9,6 +9,8 @@
 #include <type_traits>
 #include "common.h"
 #include "internal.h"
+#include "philox.h"
+#include "../../include/ta355.h"
 
 // The fp32 MASTERS keep the exact peft parameter count: la_g [members*r, in_g] (member A's stacked on rows) and
 // lb_g [N_g, r] (member B's stacked on rows).  The 64-wide bf16 images are rebuilt from them every forward.
@@ -61,13 +63,26 @@ __device__ __forceinline__ lbf16x4 tr_read(const bf16_t* p) {
 }
 typedef __attribute__((ext_vector_type(4))) float lf32x4;
 
+// zero the bf16 elements e of v (8 packed in 4 words, element 2w in the low half of word w) whose keep bit e is clear
+__device__ __forceinline__ uint4 lora_mask8(uint4 v, unsigned bits) {
+  auto w = [&](unsigned x, int e) {
+    const unsigned keep = (((bits >> e) & 1u) ? 0x0000ffffu : 0u) | (((bits >> (e + 1)) & 1u) ? 0xffff0000u : 0u);
+    return x & keep;
+  };
+  return make_uint4(w(v.x, 0), w(v.y, 2), w(v.z, 4), w(v.w, 6));
+}
 // part != NULL (round 4): row chunk `by` STORES its partial sums at part + by * part_cs (same [c, j] layout as out) and a second kernel
 // adds the chunks in a fixed order -- no float atomics: the result does not depend on the order workgroups finish in, and a workgroup's
 // last instructions are plain stores instead of 256 x R device-scope atomics that its exit waits for
 struct LoraTnArgs { const bf16_t* X; int Cn; const bf16_t* Y; int R; float* out; long so_c, so_j; float post; int r, b0, b1, rows, gx, gy; float* part; long part_cs; };
+// DROP (LoRA dropout, the dA side): row j of the output belongs to member j / dp.r, whose input is x (.) K_member (philox.h).  The
+// tile is staged once per member with that member's mask applied (sx holds dp.nmem copies of 32 x 256) and each 16-row block of
+// the output multiplies only the copies of the members it holds (A-operand lanes of other members zeroed).
+template <bool DROP = false>
 __device__ __forceinline__ void lora_tn_body(bf16_t* sx, bf16_t* sy, const bf16_t* __restrict__ X, int Cn, const bf16_t* __restrict__ Y,
                                              int R, float* __restrict__ out, long so_c, long so_j, int M, float post, int r, int b0,
-                                             int b1, int rows_per_chunk, int bx, int by, float* __restrict__ part = nullptr, long part_cs = 0) {
+                                             int b1, int rows_per_chunk, int bx, int by, float* __restrict__ part = nullptr, long part_cs = 0,
+                                             const LoraDrop& dp = LoraDrop{}) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
   const int c0 = bx * 256;
   const int m_begin = by * rows_per_chunk, m_end = min(M, m_begin + rows_per_chunk);
@@ -91,12 +106,18 @@ __device__ __forceinline__ void lora_tn_body(bf16_t* sx, bf16_t* sy, const bf16_
     const int row = tid >> 3, ch = tid & 7, m = m0 + row;
     py[st_] = m < m_end ? *(const uint4*)(Y + (long)m * 64 + ch * 8) : make_uint4(0, 0, 0, 0);
   };
-  auto stash = [&](int st_) {
+  auto stash = [&](int st_, int m0) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int id = tid + q * 256, row = id >> 5, ch = id & 31;
       const int sg = (ch >> 1) ^ (row & 3);
-      *(uint4*)(sx + row * 256 + sg * 16 + (ch & 1) * 8) = px[st_][q];
+      if constexpr (DROP) {
+        for (int jm = 0; jm < dp.nmem; ++jm)
+          *(uint4*)(sx + jm * (32 * 256) + row * 256 + sg * 16 + (ch & 1) * 8) =
+              lora_mask8(px[st_][q], lora_keep8(dp.d, dp.lj0 + jm, (unsigned)(c0 + ch * 8) >> 3, (unsigned)(m0 + row)));
+      } else {
+        *(uint4*)(sx + row * 256 + sg * 16 + (ch & 1) * 8) = px[st_][q];
+      }
     }
     const int row = tid >> 3, ch = tid & 7;
     const int sg = (ch >> 1) ^ (row & 3);
@@ -105,7 +126,7 @@ __device__ __forceinline__ void lora_tn_body(bf16_t* sx, bf16_t* sy, const bf16_
   auto tile = [&](int m0, auto stage_tag) {
     constexpr int S_ = decltype(stage_tag)::value;
     __syncthreads();                     // previous tile fully consumed
-    stash(S_);
+    stash(S_, m0);
     __syncthreads();
     if (m0 + 64 < m_end) fetch(m0 + 64, S_);   // refill this stage: two tiles ahead
     // transposed fragments with ds_read_b64_tr_b16: within a 16-lane group, lane n points at the 4-element chunk
@@ -123,12 +144,27 @@ __device__ __forceinline__ void lora_tn_body(bf16_t* sx, bf16_t* sy, const bf16_
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
       const int cg = wave * 4 + cb;
-      const lbf16x4 lo = tr_read(sx + trow * 256 + ((cg ^ (trow & 3)) * 16) + tcol);
-      const lbf16x4 hi = tr_read(sx + (trow + 4) * 256 + ((cg ^ ((trow + 4) & 3)) * 16) + tcol);
-      const lbf16x8 b = (lbf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      if constexpr (DROP) {
+        for (int jm = 0; jm < dp.nmem; ++jm) {
+          const bf16_t* sxm = sx + jm * (32 * 256);
+          const lbf16x4 lo = tr_read(sxm + trow * 256 + ((cg ^ (trow & 3)) * 16) + tcol);
+          const lbf16x4 hi = tr_read(sxm + (trow + 4) * 256 + ((cg ^ ((trow + 4) & 3)) * 16) + tcol);
+          const lbf16x8 b = (lbf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-      for (int jb = 0; jb < 4; ++jb)
-        if (jb < jblocks) acc[jb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[jb], b, acc[jb][cb], 0, 0, 0);
+          for (int jb = 0; jb < 4; ++jb)
+            if (jb < jblocks && jm * dp.r < jb * 16 + 16 && (jm + 1) * dp.r > jb * 16) {      // member jm has rows in block jb
+              const lbf16x8 am = (jb * 16 + i) / dp.r == jm ? a[jb] : (lbf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+              acc[jb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b, acc[jb][cb], 0, 0, 0);
+            }
+        }
+      } else {
+        const lbf16x4 lo = tr_read(sx + trow * 256 + ((cg ^ (trow & 3)) * 16) + tcol);
+        const lbf16x4 hi = tr_read(sx + (trow + 4) * 256 + ((cg ^ ((trow + 4) & 3)) * 16) + tcol);
+        const lbf16x8 b = (lbf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb)
+          if (jb < jblocks) acc[jb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[jb], b, acc[jb][cb], 0, 0, 0);
+      }
     }
   };
   fetch(m_begin, 0);
@@ -178,6 +214,22 @@ __global__ __launch_bounds__(256) void lora_tn_dual_kernel(const LoraTnArgs p0, 
   const LoraTnArgs& p = second ? p1 : p0;
   if (second) b -= n0;
   lora_tn_body(sx, sy, p.X, p.Cn, p.Y, p.R, p.out, p.so_c, p.so_j, M, p.post, p.r, p.b0, p.b1, p.rows, b % p.gx, b / p.gx, p.part, p.part_cs);
+}
+// The same pair with LoRA dropout: problem 0 (dB = dY^T xa: xa already holds the dropped product) as above, problem 1 (dA) stages
+// x (.) K_j per member j of the group (up to 3 copies of the X tile in LDS)
+__global__ __launch_bounds__(256) void lora_tn_dual_drop_kernel(const LoraTnArgs p0, const LoraTnArgs p1, int M, const LoraDrop dp) {
+  __shared__ __attribute__((aligned(16))) bf16_t sx[3 * 32 * 256];
+  __shared__ __attribute__((aligned(16))) bf16_t sy[32 * 64];
+  const int n0 = p0.gx * p0.gy;
+  int b = blockIdx.x;
+  if (b < n0) {
+    lora_tn_body(sx, sy, p0.X, p0.Cn, p0.Y, p0.R, p0.out, p0.so_c, p0.so_j, M, p0.post, p0.r, p0.b0, p0.b1, p0.rows, b % p0.gx, b / p0.gx,
+                 p0.part, p0.part_cs);
+  } else {
+    b -= n0;
+    lora_tn_body<true>(sx, sy, p1.X, p1.Cn, p1.Y, p1.R, p1.out, p1.so_c, p1.so_j, M, p1.post, p1.r, p1.b0, p1.b1, p1.rows, b % p1.gx,
+                       b / p1.gx, p1.part, p1.part_cs, dp);
+  }
 }
 
 // out[M, 64] (bf16) = X[M, K] W[64, K]^T : the rank-space projections xa = x (sAcat)^T and dyB = dy Bext.
@@ -267,6 +319,176 @@ __global__ __launch_bounds__(SK_WAVES * 64) void lora_skinny_nt_kernel(const bf1
     if (m0 + row < M) out[(long)(m0 + row) * 64 + col] = f2bf(v);
   }
 }
+// lora_skinny_nt_kernel under LoRA dropout (the forward xa = (x (.) K_j / (1 - p)) (s A_j)^T of every member j): each lane's X fragment is 8 consecutive
+// columns of one row -- exactly one Philox call per member (philox.h) -- and is multiplied once per member present in a 16-column
+// block of W, with the W lanes of the other members zeroed.  X is still read once; 1 / (1 - p) is applied with the final sum.
+template <int NCB, int RB>
+__device__ __forceinline__ void lora_skinny_nt_drop_body(const bf16_t* __restrict__ X, int K, const bf16_t* __restrict__ W,
+                                                    bf16_t* __restrict__ out, int M, const LoraDrop& dp) {
+  __shared__ float red[SK_WAVES][16 * RB][NCB * 16 + 1];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.x * (16 * RB);
+  lf32x4 acc[RB][NCB];
+#pragma unroll
+  for (int a = 0; a < RB; ++a)
+#pragma unroll
+    for (int b = 0; b < NCB; ++b) acc[a][b] = (lf32x4){0.f, 0.f, 0.f, 0.f};
+  const int ra = min(m0 + i, M - 1), rb = min(m0 + (RB - 1) * 16 + i, M - 1);       // clamped rows are never stored
+  const bf16_t* xa = X + (long)ra * K + g * 8;
+  const bf16_t* xb = X + (long)rb * K + g * 8;
+  // W is stored in k-step-major blocks [K/32][64][32]: the four fragment loads of one k-step read 4 KB contiguously.
+  // (Row-major [64, K] put all 64 rows of a k-step K*2 bytes apart -- a multiple of 4 KB for every K of the model, i.e.
+  // on ONE L2 channel, with every workgroup asking for the same lines at the same time.)
+  const bf16_t* wp = W + (long)i * 32 + g * 8;
+  // Every workgroup walks its k-steps from a different starting point (rot): X rows are K*2 bytes apart too, so
+  // workgroups in lock step would all sit on the same two L2 channels.
+  const int nsteps = K / 32;
+  const int ns = nsteps > wave ? (nsteps - wave + SK_WAVES - 1) / SK_WAVES : 0;      // k-steps of this wave
+  const int rot = ns ? (int)((blockIdx.x * 7u) % (unsigned)ns) : 0;
+  auto kof = [&](int sidx) { int q = sidx + rot; if (q >= ns) q -= ns; return (wave + SK_WAVES * q) * 32; };
+  constexpr int PF = 3;
+  lbf16x8 xr[PF][RB], wr[PF][NCB];
+#pragma unroll
+  for (int p = 0; p < PF; ++p)
+    if (p < ns) {
+      const int kp = kof(p);
+      xr[p][0] = *(const lbf16x8*)(xa + kp); if (RB > 1) xr[p][RB - 1] = *(const lbf16x8*)(xb + kp);
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) wr[p][cb] = *(const lbf16x8*)(wp + ((long)(kp >> 5) * 64 + cb * 16) * 32);
+    }
+  for (int s0 = 0; s0 < ns; s0 += PF) {
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+      const int sc = s0 + p;
+      if (sc < ns) {                                 // wave-uniform
+        const lbf16x8 a0 = xr[p][0], a1 = xr[p][RB - 1];
+        lbf16x8 b[NCB];
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) b[cb] = wr[p][cb];
+        if (sc + PF < ns) {                          // refill this ring slot
+          const int kf = kof(sc + PF);
+          xr[p][0] = *(const lbf16x8*)(xa + kf); if (RB > 1) xr[p][RB - 1] = *(const lbf16x8*)(xb + kf);
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) wr[p][cb] = *(const lbf16x8*)(wp + ((long)(kf >> 5) * 64 + cb * 16) * 32);
+        }
+        const unsigned c8 = (unsigned)(kof(sc) + g * 8) >> 3;
+        for (int jm = 0; jm < dp.nmem; ++jm) {
+          const lbf16x8 m0_ = __builtin_bit_cast(lbf16x8, lora_mask8(__builtin_bit_cast(uint4, a0), lora_keep8(dp.d, dp.lj0 + jm, c8, ra)));
+          lbf16x8 m1_ = m0_;
+          if (RB > 1) m1_ = __builtin_bit_cast(lbf16x8, lora_mask8(__builtin_bit_cast(uint4, a1), lora_keep8(dp.d, dp.lj0 + jm, c8, rb)));
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb)
+            if (jm * dp.r < cb * 16 + 16 && (jm + 1) * dp.r > cb * 16) {        // member jm has columns in block cb
+              const lbf16x8 bm = (cb * 16 + i) / dp.r == jm ? b[cb] : (lbf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+              acc[0][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m0_, bm, acc[0][cb], 0, 0, 0);
+              if (RB > 1) acc[RB - 1][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m1_, bm, acc[RB - 1][cb], 0, 0, 0);
+            }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int rbk = 0; rbk < RB; ++rbk)
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) red[wave][rbk * 16 + g * 4 + q][cb * 16 + i] = acc[rbk][cb][q];
+  __syncthreads();
+  for (int e = tid; e < 16 * RB * 64; e += SK_WAVES * 64) {
+    const int row = e >> 6, col = e & 63;
+    float v = 0.f;
+    if (col < NCB * 16) {
+#pragma unroll
+      for (int w = 0; w < SK_WAVES; ++w) v += red[w][row][col];
+    }
+    v *= dp.d.inv_keep;
+    if (m0 + row < M) out[(long)(m0 + row) * 64 + col] = f2bf(v);
+  }
+}
+template <int NCB, int RB>
+__global__ __launch_bounds__(SK_WAVES * 64) void lora_skinny_nt_drop_kernel(const bf16_t* __restrict__ X, int K,
+                                                                            const bf16_t* __restrict__ W,
+                                                                            bf16_t* __restrict__ out, int M, const LoraDrop dp) {
+  lora_skinny_nt_drop_body<NCB, RB>(X, K, W, out, M, dp);
+}
+
+// The masked rank-space share of d(x) under LoRA dropout, added IN PLACE to the bf16 output of the frozen dX GEMM:
+//   out[m, c] += sum_j K_j[m, c] / (1 - p) * sum_{k < r} U[m, j r + k] AT[c, j r + k]      (U = dY Bext [M, 64], AT = (s Acat)^T [in, 64])
+// With p = 0 this term is the GEMM's K extension; a mask on the OUTPUT side cannot ride there.  Per member j it is an MFMA product with
+// K = the 64-wide rank space (lanes outside member j's r columns of AT zeroed).  D[c, m] = AT U^T on 16x16 blocks: the A-operand rows
+// of the two blocks t = 0, 1 of a wave's 32 columns are permuted (block row 4 g' + q' <-> column 8 g' + 4 t + q') so that lane (i, g)
+// ends up holding the 8 CONSECUTIVE columns 8 g .. 8 g + 7 of row i -- one Philox call per member, one 16-B load / store of out.
+// Wave w of a workgroup owns columns [32 (4 bx + w), + 32) and loops over the workgroup's DX_ROWS rows, 16 at a time.
+constexpr int DX_ROWS = 64;
+__global__ __launch_bounds__(256) void lora_dx_drop_kernel(const bf16_t* __restrict__ U, const bf16_t* __restrict__ AT, bf16_t* __restrict__ out,
+                                                           int M, int in, const LoraDrop dp) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 15, g = lane >> 4;
+  const int cw = (blockIdx.x * 4 + wave) * 32;
+  if (cw >= in) return;                                          // wave-uniform; no barriers below
+  // A fragments: block t, k-step ks (32 of the 64 rank columns), member jm
+  lbf16x8 a[3][2][2];
+  const lbf16x8 z = (lbf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int c = cw + 8 * (i >> 2) + 4 * t + (i & 3);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int k0 = ks * 32 + g * 8;
+      const lbf16x8 v = c < in ? *(const lbf16x8*)(AT + (long)c * 64 + k0) : z;
+#pragma unroll
+      for (int jm = 0; jm < 3; ++jm) {
+        lbf16x8 vm = v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (k0 + e < jm * dp.r || k0 + e >= (jm + 1) * dp.r) vm[e] = 0;
+        a[jm][t][ks] = vm;
+      }
+    }
+  }
+  const int c8 = cw + 8 * g;                                     // this lane's 8 output columns
+  const int m_end = min(M, (int)(blockIdx.y + 1) * DX_ROWS);
+  for (int mt = blockIdx.y * DX_ROWS; mt < m_end; mt += 16) {
+    const int mb = mt + i;                                       // B-operand row (= output row of this lane)
+    lbf16x8 b[2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) b[ks] = mb < M ? *(const lbf16x8*)(U + (long)mb * 64 + ks * 32 + g * 8) : z;
+    float tot[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int jm = 0; jm < 3; ++jm) {
+      if (jm >= dp.nmem) break;
+      lf32x4 acc[2] = {(lf32x4){0.f, 0.f, 0.f, 0.f}, (lf32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        if (jm * dp.r < ks * 32 + 32 && (jm + 1) * dp.r > ks * 32)
+#pragma unroll
+          for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[jm][t][ks], b[ks], acc[t], 0, 0, 0);
+      const unsigned bits = lora_keep8(dp.d, dp.lj0 + jm, (unsigned)c8 >> 3, (unsigned)mb);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if ((bits >> e) & 1u) tot[e] += acc[e >> 2][e & 3];
+    }
+    if (mb < M && c8 < in) {
+      uint4* po = (uint4*)(out + (long)mb * in + c8);
+      const uint4 o = *po;
+      const unsigned ow[4] = {o.x, o.y, o.z, o.w};
+      unsigned nw[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        nw[q] = pack2bf(bf2f((bf16_t)(ow[q] & 0xffffu)) + tot[2 * q] * dp.d.inv_keep, bf2f((bf16_t)(ow[q] >> 16)) + tot[2 * q + 1] * dp.d.inv_keep);
+      *po = make_uint4(nw[0], nw[1], nw[2], nw[3]);
+    }
+  }
+}
+
+// keep[m, c] of linear lj (the mask definition of philox.h, materialised for tests)
+__global__ __launch_bounds__(256) void lora_keep_kernel(const LoraDropDev d, unsigned lj, int M, int in, uint8_t* __restrict__ out) {
+  const int n8 = (in + 7) >> 3;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)M * n8) return;
+  const int m = (int)(idx / n8), c8 = (int)(idx % n8);
+  const unsigned bits = lora_keep8(d, lj, (unsigned)c8, (unsigned)m);
+  for (int e = 0; e < 8 && c8 * 8 + e < in; ++e) out[(long)m * in + c8 * 8 + e] = (uint8_t)((bits >> e) & 1u);
+}
 
 int ta_i_lora_pack_a(const float* in, float scale, void* out, void* outT, int R, int Cn, int layers, long in_ls, long out_ls,
                      hipStream_t st) {
@@ -337,7 +559,8 @@ int ta_i_lora_reduce_parts(const LoraReduceDesc& d, int layers, hipStream_t st) 
 int ta_i_lora_skinny_tn2(const void* X0, int Cn0, const void* Y0, int R0, float* out0, long so_c0, long so_j0, float post0, int r0,
                          int b00, int b10, const void* X1, int Cn1, const void* Y1, int R1, float* out1, long so_c1, long so_j1,
                          float post1, int r1, int b01, int b11, int M, float* part0, long part_cs0, float* part1, long part_cs1,
-                         hipStream_t st) {
+                         hipStream_t st, const LoraDrop* drop) {
+  if (drop && (r1 != 0 || drop->nmem < 1 || drop->nmem > 3 || drop->r < 1 || drop->nmem * drop->r != R1)) return TA_ERR_ARG;
   if (R0 > 64 || R0 <= 0 || R1 > 64 || R1 <= 0 || (Cn0 % 8) || (Cn1 % 8)) return TA_ERR_ARG;
   if (M <= 0) return TA_OK;
   LoraTnArgs p0 = {(const bf16_t*)X0, Cn0, (const bf16_t*)Y0, R0, out0, so_c0, so_j0, post0, r0, b00, b10, lora_tn_rows(M, Cn0), 0, 0, part0, part_cs0};
@@ -357,7 +580,8 @@ int ta_i_lora_skinny_tn2(const void* X0, int Cn0, const void* Y0, int R0, float*
   }
   p0.gy = ta_cdiv(M, p0.rows);
   p1.gy = ta_cdiv(M, p1.rows);
-  TA_LAUNCH(lora_tn_dual_kernel, dim3(p0.gx * p0.gy + p1.gx * p1.gy), dim3(256), 0, st, p0, p1, M);
+  if (drop) TA_LAUNCH(lora_tn_dual_drop_kernel, dim3(p0.gx * p0.gy + p1.gx * p1.gy), dim3(256), 0, st, p0, p1, M, *drop);
+  else TA_LAUNCH(lora_tn_dual_kernel, dim3(p0.gx * p0.gy + p1.gx * p1.gy), dim3(256), 0, st, p0, p1, M);
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
@@ -371,6 +595,53 @@ int ta_i_lora_skinny_nt(const void* X, int K, const void* W, void* out, int M, i
 #define SKNT(NCB_, RB_) TA_LAUNCH((lora_skinny_nt_kernel<NCB_, RB_>), grid, blk, 0, st, (const bf16_t*)X, K, (const bf16_t*)W, (bf16_t*)out, M)
   if (ncb == 1) SKNT(1, 2); else if (ncb == 2) SKNT(2, 2); else if (ncb == 3) SKNT(3, 2); else SKNT(4, 2);
 #undef SKNT
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// LoRA dropout (philox.h): the masked forms of the two launches above, and the masked d(x) term
+int ta_i_lora_skinny_nt_drop(const void* X, int K, const void* W, void* out, int M, const LoraDrop& dp, hipStream_t st) {
+  const int R = dp.nmem * dp.r;
+  if (K % 32 || K <= 0 || dp.nmem < 1 || dp.nmem > 3 || dp.r < 1 || R > 64) return TA_ERR_ARG;
+  if (M <= 0) return TA_OK;
+  const int ncb = (R + 15) / 16;
+  const dim3 grid(ta_cdiv(M, 32)), blk(SK_WAVES * 64);
+#define SKNT(NCB_, RB_) TA_LAUNCH((lora_skinny_nt_drop_kernel<NCB_, RB_>), grid, blk, 0, st, (const bf16_t*)X, K, (const bf16_t*)W, (bf16_t*)out, M, dp)
+  if (ncb == 1) SKNT(1, 2); else if (ncb == 2) SKNT(2, 2); else if (ncb == 3) SKNT(3, 2); else SKNT(4, 2);
+#undef SKNT
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+int ta_i_lora_dx_drop(const void* U, const void* AT, void* out, int M, int in, const LoraDrop& dp, hipStream_t st) {
+  if (in % 8 || in <= 0 || dp.nmem < 1 || dp.nmem > 3 || dp.r < 1 || dp.nmem * dp.r > 64) return TA_ERR_ARG;
+  if (M <= 0) return TA_OK;
+  TA_LAUNCH(lora_dx_drop_kernel, dim3(ta_cdiv(in, 128), ta_cdiv(M, DX_ROWS)), dim3(256), 0, st, (const bf16_t*)U, (const bf16_t*)AT,
+            (bf16_t*)out, M, in, dp);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+// descriptor -> device form; false when dropout is off (NULL or p == 0)
+bool ta_i_lora_drop_dev(const ta_lora_dropout* desc, LoraDropDev* out) {
+  if (!desc || !(desc->p > 0.f)) return false;
+  const double p = desc->p;
+  long thr = (long)(p * 65536.0 + 0.5);
+  out->thr = (unsigned)(thr > 65535 ? 65535 : thr);
+  out->inv_keep = (float)(1.0 / (1.0 - p));
+  out->k0 = (unsigned)desc->seed; out->k1 = (unsigned)(desc->seed >> 32);
+  out->o0 = (unsigned)desc->offset; out->o1 = (unsigned)(desc->offset >> 32);
+  return true;
+}
+extern "C" int ta_lora_dropout_keep(const ta_lora_dropout* desc, int layer, int linear, int M, int in, unsigned char* out, hipStream_t st) {
+  if (!desc || !(desc->p >= 0.f) || !(desc->p < 1.f) || layer < 0 || layer >= 512 || linear < 0 || linear > 6 || in <= 0 ||
+      in >= (1 << 23) || !out)
+    return TA_ERR_ARG;
+  if (M <= 0) return TA_OK;
+  LoraDropDev d;
+  if (!ta_i_lora_drop_dev(desc, &d)) {                       // p == 0: every element kept
+    if (hipMemsetAsync(out, 1, (size_t)M * in, st) != hipSuccess) return TA_ERR_LAUNCH;
+    return TA_OK;
+  }
+  TA_LAUNCH(lora_keep_kernel, dim3((unsigned)ta_cdiv((long)M * ((in + 7) / 8), 256)), dim3(256), 0, st, d, (unsigned)(8 * layer + linear), M, in, out);
   TA_CHECK_LAUNCH();
   return TA_OK;
 }

@@ -41,6 +41,9 @@ class Qwen3MI355X(torch.nn.Module):
         self.lora_rank = 0
         self.lora_groups = 0
         self.lora_targets = set()
+        self.lora_dropout = 0.0
+        self.lora_drop_seed = 0
+        self.lora_drop_offset = 0        # Philox offset of the next training forward (ASRTrainer adds rank << 32 on DDP ranks)
         self._lora_bound = None
         self.train_base = False          # full decoder fine-tuning (freeze_language_model=False)
         self.want_train_base = False     # ... requested before the weights exist: enabled by _finalize
@@ -93,6 +96,9 @@ class Qwen3MI355X(torch.nn.Module):
         stacked group layout of include/ta355.h.
 
         ``rank``: any r with 3 r <= 64 (the q|k|v group's three adapters share one 64-wide K tile).
+        ``dropout``: peft's ``lora_dropout`` p, 0 <= p < 1: in training mode each adapted linear drops its adapter input with its
+        own mask (include/ta355.h ``ta_lora_dropout``; masks drawn per training forward from ``seed``); evaluation and decoding
+        never apply it.
         ``target_modules``: any subset of the 7 linears (peft suffix names).  A group none of whose members is targeted is
         switched off in the C library (``ta_lm_weights.lora_groups``); inside a live group the members that are not targeted
         keep A = B = 0, which makes both of their gradients exactly zero (dA = s (dy B)^T x, dB = dy^T (x A^T)), so AdamW
@@ -101,8 +107,9 @@ class Qwen3MI355X(torch.nn.Module):
             raise NotImplementedError("LoRA on top of a trainable base LM is not built")
         if not (1 <= int(rank) and 3 * int(rank) <= 64):
             raise NotImplementedError("lora_rank must satisfy 3 * rank <= 64 (one 64-wide K tile per adapter group)")
-        if dropout:
-            raise NotImplementedError("lora_dropout > 0 is not built (reference default 0.0, asr_config.py:74)")
+        dropout = float(dropout or 0.0)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"lora_dropout must satisfy 0 <= p < 1, got {dropout}")
         all_t = [t for _, ts in LORA_GROUPS for t in ts]
         if target_modules is None:
             targets = set(all_t)
@@ -128,9 +135,21 @@ class Qwen3MI355X(torch.nn.Module):
             setattr(self, f"lora_la_{g}", torch.nn.Parameter(a.to(dev)))
             setattr(self, f"lora_lb_{g}", torch.nn.Parameter(b.to(dev)))
         self.lora_rank, self.lora_alpha, self.lora_targets = rank, alpha, targets
+        self.lora_dropout = dropout
+        self.lora_drop_seed = (0x10DA_D809 * (int(seed) + 1)) & 0x7FFFFFFFFFFFFFFF
+        self.lora_drop_offset = 0
         self._lora_bound = None
         self._finalize_lora_scale()
         return self
+
+    def next_lora_dropout(self):
+        """(p, seed, offset) for the next forward: a fresh offset per TRAINING forward with p > 0; None otherwise (evaluation,
+        p == 0, no adapters).  The backward must be handed the same triple (the autograd node keeps it)."""
+        if not (self.lora_rank and self.lora_dropout > 0.0 and self.training):
+            return None
+        off = self.lora_drop_offset
+        self.lora_drop_offset += 1
+        return (float(self.lora_dropout), int(self.lora_drop_seed), int(off))
 
     def lora_param_count(self):
         """peft's trainable-parameter count: r (in + out) per targeted linear and layer (the stacked masters also hold the
@@ -477,8 +496,9 @@ class Qwen3MI355X(torch.nn.Module):
 
     # ------------------------------------------------------------------ raw forward / backward (no autograd)
     def forward_loss(self, input_ids, src_row, audio, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-                     want_logits=False, pos=None):
-        """Returns (loss[1] f32, nll[n] f32, logits or None, ctx) -- ctx feeds ``backward_from_ctx``."""
+                     want_logits=False, pos=None, lora_dropout=None):
+        """Returns (loss[1] f32, nll[n] f32, logits or None, ctx) -- ctx feeds ``backward_from_ctx``.
+        ``lora_dropout``: (p, seed, offset) of ``next_lora_dropout()`` or None; kept in ctx for the backward."""
         if self._w is None:
             raise _lib.Ta355Error("LM weights not loaded")
         L_ = _lib.lib()
@@ -493,12 +513,19 @@ class Qwen3MI355X(torch.nn.Module):
         loss = torch.zeros(1, device=dev, dtype=F32)
         nll = torch.empty(max(n_label_rows, 1), device=dev, dtype=F32)
         logits = torch.empty((B * L, self.vocab_pad), device=dev, dtype=BF16) if want_logits else None
-        _lib.check(L_.ta_lm_forward_loss(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos),
-                                         B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
-                                         ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), stream()),
-                   "ta_lm_forward_loss")
+        drop = _lora_drop_desc(lora_dropout)
+        if drop is None:
+            _lib.check(L_.ta_lm_forward_loss(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos),
+                                             B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
+                                             ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), stream()),
+                       "ta_lm_forward_loss")
+        else:
+            _lib.check(L_.ta_lm_forward_loss_ex(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos),
+                                                B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
+                                                ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), C.byref(drop), stream()),
+                       "ta_lm_forward_loss_ex")
         ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
-                   n_label_rows=n_label_rows, ids=input_ids)
+                   n_label_rows=n_label_rows, ids=input_ids, lora_dropout=lora_dropout)
         # The tape's residual-stream rows are in the storage dtype this handle carried NOW: the backward must read them as that even
         # if the owner flips ``res_f32`` in between.  Keyed by the tape's address, since the custom operator hands the backward only
         # tensors.
@@ -547,11 +574,19 @@ class Qwen3MI355X(torch.nn.Module):
         if recorded is not None and recorded != (int(w.res_f32), int(w.dx_f32)):
             w = _lib.LmWeights.from_buffer_copy(self._w)          # same pointers, the modes the forward ran in
             w.res_f32, w.dx_f32 = recorded
-        _lib.check(_lib.lib().ta_lm_backward(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]),
-                                             ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
-                                             ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
-                                             None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
-                                             ptr(ctx["ws"]), ctx["ws"].numel(), stream()), "ta_lm_backward")
+        drop = _lora_drop_desc(ctx.get("lora_dropout"))       # the descriptor its forward ran with
+        if drop is None:
+            _lib.check(_lib.lib().ta_lm_backward(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]),
+                                                 ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
+                                                 ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
+                                                 None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
+                                                 ptr(ctx["ws"]), ctx["ws"].numel(), stream()), "ta_lm_backward")
+        else:
+            _lib.check(_lib.lib().ta_lm_backward_ex(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]),
+                                                    ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
+                                                    ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
+                                                    None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
+                                                    ptr(ctx["ws"]), ctx["ws"].numel(), C.byref(drop), stream()), "ta_lm_backward_ex")
         del keep
         return d_audio, d_emb, lg
 
@@ -690,6 +725,13 @@ class Qwen3MI355X(torch.nn.Module):
         yield out_seq[:, :n_new]
 
 
+def _lora_drop_desc(d):
+    """(p, seed, offset) -> ta_lora_dropout, or None when dropout is off (None or p == 0: the plain entry points run)."""
+    if d is None or not float(d[0]) > 0.0:
+        return None
+    return _lib.LoraDropout(p=float(d[0]), seed=int(d[1]) & 0xFFFFFFFFFFFFFFFF, offset=int(d[2]) & 0xFFFFFFFFFFFFFFFF)
+
+
 class FrozenLMLoss:
     """loss = CE(frozen_LM(embed(ids) with <audio> rows := audio_embeds)) through ``torch.ops.ta355.lm_forward_loss``
     (torch_ops.py); grad flows to audio_embeds and to the trainable LM tensors passed as trailing inputs -- the LoRA masters
@@ -704,9 +746,15 @@ class FrozenLMLoss:
     def apply(audio_embeds, lm, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
               want_logits, *trainable, pos=None):
         from . import torch_ops
-        loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss(
-            audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
-            int(n_label_rows), float(loss_scale), bool(want_logits), pos)
+        drop = lm.next_lora_dropout()                 # training forwards of a p > 0 model only: a fresh Philox offset each
+        if drop is None:
+            loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss(
+                audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
+                int(n_label_rows), float(loss_scale), bool(want_logits), pos)
+        else:
+            loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss_drop(
+                audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
+                int(n_label_rows), float(loss_scale), bool(want_logits), pos, *drop)
         # a fresh tensor: the outputs of a multi-output custom op may not be modified in place, and HF Trainer does
         # `loss *= ...` on what the model returns (TF:trainer.py compute_loss)
         return loss.clone(), nll, logits

@@ -258,6 +258,10 @@ class ASRTrainer:
         # DDP ranks must not draw identical dropout patterns (the reference's per-process torch RNG): fold the rank in
         if _distributed(group) and hasattr(model, "_drop_seed"):
             model._drop_seed += 1000003 * dist.get_rank(group)
+        # ... and the LoRA dropout masks likewise: rank k draws its Philox offsets from k << 32 on (include/ta355.h ta_lora_dropout)
+        lm = getattr(model, "language_model", None)
+        if _distributed(group) and getattr(lm, "lora_rank", 0):
+            lm.lora_drop_offset += dist.get_rank(group) << 32
 
     def _invalidate(self):
         proj = getattr(self.model, "projector", None)
