@@ -20,16 +20,16 @@ import pytest
 from tiny_audio_amd import _lib
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
-# template arguments <BN2, ACT, OUT_BF16, HAS_RES, KEXT, LIFE, BM2> of the kernels behind the default step (profiles/r03_final2_kernel_steps.md)
-STEP_KERNELS = ["Li320ELi0ELb1ELb1ELb0ELb0ELi256E", "Li320ELi1ELb1ELb0ELb0ELb0ELi256E", "Li320ELi2ELb1ELb0ELb0ELb0ELi256E",
-                "Li320ELi0ELb1ELb0ELb0ELb0ELi256E", "Li256ELi0ELb1ELb0ELb0ELb0ELi192E", "Li256ELi0ELb1ELb0ELb0ELb0ELi256E",
-                "Li256ELi0ELb0ELb0ELb0ELb0ELi192E"]
+# template arguments <BN2, ACT, OUT_BF16, HAS_RES, BM2> of the kernels behind the default step (profiles/r03_final2_kernel_steps.md)
+STEP_KERNELS = ["Li320ELi0ELb1ELb1ELi256E", "Li320ELi1ELb1ELb0ELi256E", "Li320ELi2ELb1ELb0ELi256E",
+                "Li320ELi0ELb1ELb0ELi256E", "Li256ELi0ELb1ELb0ELi192E", "Li256ELi0ELb1ELb0ELi256E",
+                "Li256ELi0ELb0ELb0ELi192E"]
 
 
 def _gemm_isa():
     src = os.path.join(CSRC, "gemm.hip")
     out = os.path.join(CSRC, "build", "gemm_isa.s")
-    deps = [src] + [os.path.join(CSRC, h) for h in ("common.h", "internal.h", "gelu_lut.h")]
+    deps = [src] + [os.path.join(CSRC, h) for h in ("common.h", "internal.h", "gelu_lut.h", "gemm_common.h")]
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         cmd = [_lib.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-mllvm", "-amdgpu-mfma-vgpr-form", "--cuda-device-only",
@@ -48,6 +48,7 @@ def _kernels(isa):
 @pytest.mark.timeout(900)
 def test_persistent_gemm_has_no_scratch_traffic_around_its_dma_or_in_its_main_loop():
     isa = _gemm_isa()
+    assert "s_memtime" not in isa       # no cycle-counter experiment (stamps, delayed starts) is compiled into the library's GEMMs
     seen = set()
     for name, lines, vgprs, scratch in _kernels(isa):
         key = next((k for k in STEP_KERNELS if "kernel_v4I" + k in name), None)
@@ -81,10 +82,10 @@ def test_persistent_gemm_has_no_scratch_traffic_around_its_dma_or_in_its_main_lo
 
 @pytest.mark.timeout(900)
 def test_one_tile_per_cu_gemm_of_the_step_has_no_scratch():
-    """gemm_nt_kernel_v5<ACT = 0, bf16 out, +/- residual> (the LM's N = 1024 products; profiles/r04_final4_kernel_steps.md)."""
+    """gemm_nt_kernel_v5<ACT = 0, bf16 out, +/- residual, no K extension> (the LM's N = 1024 products; profiles/r04_final4_kernel_steps.md)."""
     isa = _gemm_isa()
     seen = 0
-    for m in re.finditer(r"^(_Z\d+gemm_nt_kernel_v5ILi0ELb1ELb[01]ELi0ELb0E[^\n:]*):.*?; ScratchSize: (\d+)", isa, re.S | re.M):
+    for m in re.finditer(r"^(_Z\d+gemm_nt_kernel_v5ILi0ELb1ELb[01]ELb0E[^\n:]*):.*?; ScratchSize: (\d+)", isa, re.S | re.M):
         seen += 1
         assert int(m.group(2)) == 0, m.group(1)
     assert seen == 2, seen

@@ -169,9 +169,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
 // Hazards: every wave drains its own DMA (vmcnt 0) at the end of L(t,1), i.e. before barrier 4t+3 (group 0) /
 // 4t+4 (group 1), and the first read of tile t+1 is after barrier 4t+4; the last reads of tile t-1 (group 1's
 // L(t-1,1)) retire (lgkmcnt 0) before barrier 4t, and the first DMA into that buffer is issued after it.
-// TIMING (experiments, variant 8): s_memtime stamps around the L / barrier / C / barrier phases of every interval; instead
-// of the epilogue every wave writes its five cycle sums {L, wait for barrier 1, C, wait for barrier 2, whole loop} to C.
-template <int BN2, int ACT, bool OUT_BF16, bool HAS_RES, bool PP, bool KEXT = false, bool TIMING = false>
+template <int BN2, int ACT, bool OUT_BF16, bool HAS_RES, bool PP, bool KEXT = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
   constexpr int BM2 = 256;
   constexpr int NT = BN2 / 64;                 // n-fragments per wave
@@ -181,9 +179,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int g = lane >> 4, l15 = lane & 15;
-  const bool life = TIMING && (p.dbg & 4);      // experiment: stamps of the workgroup's life (entry, first tile landed, loop end, stores issued / acknowledged)
-  unsigned long long lf[5] = {0, 0, 0, 0, 0};
-  if (life) lf[0] = __builtin_amdgcn_s_memtime();
 
   const int nwg = gridDim.x;
   int bid = blockIdx.x;
@@ -210,14 +205,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
   if (p.splits > 1) { kt_begin = (nkt * z) / p.splits; kt_end = (nkt * (z + 1)) / p.splits; }
   if (krp) { kt_begin = krp[0]; kt_end = krp[1]; }
   if (KEXT) kt_end = nkt + p.K2 / BK;
-  if (p.dbg & 2) kt_end = min(kt_end, kt_begin + 1);
   int Mact = p.M, rbase = 0;
   if (segp) { rbase = segp[0]; Mact = segp[1]; if (m0 >= Mact) return; }
-  if ((p.dbg >> 8) && blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {   // experiment: first-round workgroups of every other CU start late,
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();        // so that epilogues (HBM bursts) and main loops (MFMA) of the rounds interleave
-    const unsigned long long wait = (unsigned long long)(p.dbg >> 8) << 8;
-    while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(32);
-  }
 
   const int lr = tid >> 3;                                    // 0..63
   const int clog = (tid & 7) ^ ((lr >> 1) & 7);
@@ -271,12 +260,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
     for (int i = 0; i < NB; ++i) dma_w(lds_w, i);
   }
   __syncthreads();
-  if (life) lf[1] = __builtin_amdgcn_s_memtime();
   if constexpr (PP) {
     const int lag = __builtin_amdgcn_readfirstlane(wm);     // SGPR: scalar branches around the extra barriers
     if (lag) __builtin_amdgcn_s_barrier();
-    unsigned long long tL = 0, tB1 = 0, tC = 0, tB2 = 0, tAll = 0;
-    if (TIMING) tAll = __builtin_amdgcn_s_memtime();
     for (int kt = kt_begin; kt < kt_end; ++kt) {
       const int cur = (kt - kt_begin) & 1;
       const bool more = kt + 1 < kt_end;
@@ -286,8 +272,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
         const int ko = kk ? koff1 : koff0;
-        unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-        if (TIMING && !life) s0 = __builtin_amdgcn_s_memtime();
         // ---- L(t, kk)
 #pragma unroll
         for (int j = 0; j < NT; ++j) bfr[j] = *(const bf16x8*)(S + b_rd + j * 2048 + ko);
@@ -305,11 +289,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
         } else {
           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         }
-        if (TIMING && !life) { s1 = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (TIMING && !life) { s2 = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
         // ---- C(t, kk)
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -319,32 +301,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
-        if (TIMING && !life) { s3 = __builtin_amdgcn_s_memtime(); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (TIMING && !life) {
-          const unsigned long long s4 = __builtin_amdgcn_s_memtime();
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          tL += s1 - s0; tB1 += s2 - s1; tC += s3 - s2; tB2 += s4 - s3;
-        }
       }
-    }
-    if (TIMING && !life) {
-      tAll = __builtin_amdgcn_s_memtime() - tAll;
-      float sacc = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) sacc += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-      if (lane == 0) {
-        unsigned long long* o = (unsigned long long*)p.C + ((long)blockIdx.x * 8 + wave) * 8;
-        o[0] = tL; o[1] = tB1; o[2] = tC; o[3] = tB2; o[4] = tAll; o[5] = (unsigned long long)(kt_end - kt_begin);
-        o[6] = sacc == 1234.5678f;
-      }
-      return;
     }
     if (!lag) __builtin_amdgcn_s_barrier();
-    if (life) lf[2] = __builtin_amdgcn_s_memtime();
   } else {
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int cur = (kt - kt_begin) & 1;
@@ -384,18 +345,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
   const float2* lut = stage_gelu_lut<ACT, 512>(smem, p, tid, false);       // both wave groups are past their last LDS read
   if (res_init) epilogue_tile<8, NT, ACT, OUT_BF16, false>(acc, p, Cb, m0 + wm * 128 + l15, Mact, rbase, n0 + wn * (BN2 / 4), g, wide, biasp, lut);
   else epilogue_tile<8, NT, ACT, OUT_BF16, HAS_RES>(acc, p, Cb, m0 + wm * 128 + l15, Mact, rbase, n0 + wn * (BN2 / 4), g, wide, biasp, lut);
-  if (life) {                                   // behind the C matrix: [workgroup][wave group] x {5 stamps, HW_ID, XCC_ID, tile}
-    lf[3] = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lf[4] = __builtin_amdgcn_s_memtime();
-    if (lane == 0 && (wave & 3) == 0) {
-      unsigned long long* o = (unsigned long long*)((char*)p.C + (long)p.M * p.ldc * 2) + ((long)blockIdx.x * 2 + wm) * 8;
-      for (int i = 0; i < 5; ++i) o[i] = lf[i];
-      o[5] = __builtin_amdgcn_s_getreg(63492);  // HW_REG_HW_ID
-      o[6] = __builtin_amdgcn_s_getreg(63508);  // HW_REG_XCC_ID
-      o[7] = (unsigned long long)bid;
-    }
-  }
 }
 
 
@@ -418,12 +367,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
 //     more than the stores saved (10.3 k cycles per tile against 8.5 k), so it was removed.
 // Per tile of a K = 1280 GEMM: 0.7 k wait + 60.5 k main loop + 2.2 k next-tile set-up + ~8.5 k epilogue, against 90 k for v2.
 
-// LIFE (experiments, variant 9): s_memtime stamps of every tile {loop top, first K tile landed, loop end, next tile's DMA issued,
-// stores issued} + HW_ID / XCC_ID behind the C matrix (scripts/gemm_wg_life.py)
 // BM2 = 192 (round 3): the same kernel on a 192-row tile (each wave group owns 96 rows = 6 fragment rows).  M = 6144 (the LM at
 // B = 32) is 32 x 192: N = 2048 gives 256 tiles = ONE per CU and N = 4096 gives 512 = two full rounds, where 256-row tiles leave
 // a quarter of the chip idle (192 of 256 CUs; 1.5 rounds).
-template <int BN2, int ACT, bool OUT_BF16, bool HAS_RES, bool KEXT = false, bool LIFE = false, int BM2 = 256>
+template <int BN2, int ACT, bool OUT_BF16, bool HAS_RES, int BM2 = 256>
 __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
   constexpr int MI = BM2 / 32;                      // 16-row fragment rows per wave (two wave groups split the tile's rows)
   constexpr int NT = BN2 / 64;
@@ -441,8 +388,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
   const char* a_base; const char* w_base;
   unsigned a_off[NA], w_off[NB];
   const int w_step = p.w_blocked ? 8192 : BK * 2;
-  // experiment (TA355_GEMM_DEBUG bit 10, scripts/a_blocked_probe.py): A given as [M/64][K/64][64][64] blocks, like w_blocked
-  const bool a_blk = (p.dbg & 1024) != 0;
+  // A given as [M/64][K/64][64][64] blocks, like w_blocked (round 3 probe).  No entry point sets a_blocked; the branch stays because the
+  // register allocation of every instantiation hangs on it: without it the kernels of the step take 5-6 more VGPRs and the 256-VGPR
+  // o_proj / fc2 kernel <320, 0, true, true> gets 16 bytes of scratch (profiles/gemm_prune_isa.md)
+  const bool a_blk = p.a_blocked != 0;
   const int a_step = a_blk ? 8192 : BK * 2;
   // wave-uniform LDS byte address of this wave's 1-KB DMA window in stage 0
   const unsigned lds_w = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem + wave * 1024);
@@ -472,21 +421,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
   };
   // Offsets are relative to the tile's first row of each operand (the base carries the rest), so they stay far below 4 GB
   // whatever the operand's size; only A under a non-identity row map is addressed from the start of A (host: < 4 GB, no gather).
-  auto ext_switch = [&](const TileCtx& c, int tile) {            // call before staging K-tile `tile` of tile context c
-    if (KEXT && tile == nkt) {
-      // (thread index re-derived here: from threadIdx.x these nine offsets are loop-invariant, were hoisted out of the tile loop and
-      // pushed the regular ones into scratch -- reloaded between the DMA issues of every K tile, each reload behind a vmcnt(0))
-      const int te = fresh_tid(), lr = te >> 3, clog = (te & 7) ^ ((lr >> 1) & 7);
-      a_base = (const char*)(p.A2 + (long)(c.rbase + c.m0) * p.lda2);
-      w_base = (const char*)(p.W2 + (long)c.n0 * p.K2);
-#pragma unroll
-      for (int i = 0; i < NA; ++i)
-        a_off[i] = (unsigned)(((long)(min(c.m0 + i * 64 + lr, c.Mact - 1) - c.m0) * p.lda2 + clog * 8) * 2);
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-        w_off[i] = (unsigned)(((long)(min(c.n0 + i * 64 + lr, p.N - 1) - c.n0) * p.K2 + clog * 8) * 2);
-    }
-  };
   auto first_dma = [&](const TileCtx& c, int st) {              // sources of tile c + its first K tile into stage st
     const int te = fresh_tid(), lr = te >> 3, clog = (te & 7) ^ ((lr >> 1) & 7);
     if (a_blk) {
@@ -513,10 +447,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
                              : (unsigned)(((long)(gn - c.n0) * p.K + clog * 8) * 2);
     }
     w_base = (const char*)c.Wp + (p.w_blocked ? (((long)(c.n0 >> 6) * nkt) << 13) + (long)c.kb * 8192 : ((long)c.n0 * p.K + (long)c.kb * BK) * 2);
-    if (c.kb < c.ke) {
-      ext_switch(c, c.kb);
-      dma_tile(lds_w + st * STAGE);
-    }
+    if (c.kb < c.ke) dma_tile(lds_w + st * STAGE);
   };
   // The epilogue's constants of tile c into the stage whose wave window starts at `base` (see EPI_LDS_*): issued where the main
   // loop's LAST K tile would request its successor, waited for by that K tile's own vmcnt(0) + barriers.
@@ -528,7 +459,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
       const int n = c.n0 + te * 4;
       glds16_s(uniform_ptr((const char*)c.biasp), (unsigned)((n < p.N ? n : p.N - 4) * 4), base + EPI_LDS_BIAS);
     }
-    if (GELU && !(p.dbg & 8)) {
+    if (GELU && !p.gelu_erf) {
       static_assert(GELU_LUT_N * 8 == 512 * 16, "one 16-B piece per thread");
       glds16_s(uniform_ptr((const char*)kGeluLut), (unsigned)(te * 16), base + EPI_LDS_TAB);
     }
@@ -545,11 +476,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
 
   const bool res_init = residual_is_start<ACT, OUT_BF16, HAS_RES>(p);
   int h = blockIdx.x;
-  TileCtx cur = tile_ctx<BM2, BN2, KEXT>(p, h, total);
+  TileCtx cur = tile_ctx<BM2, BN2>(p, h, total);
   while (!cur.ok) {                                              // surplus tiles of a grouped launch
     h += gridDim.x;
     if (h >= total) return;
-    cur = tile_ctx<BM2, BN2, KEXT>(p, h, total);
+    cur = tile_ctx<BM2, BN2>(p, h, total);
   }
   int ph = 0;                                                    // the stage that receives the tile's first K tile
   first_dma(cur, ph);
@@ -564,17 +495,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
       zero_acc<MI, NT>(acc);
     }
 
-    unsigned long long lf[5] = {0, 0, 0, 0, 0};
-    if (LIFE) lf[0] = __builtin_amdgcn_s_memtime();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's share of the first K tile (and its last stores)
-    __syncthreads();
-    if (LIFE) lf[1] = __builtin_amdgcn_s_memtime();                                             // first K tile landed; every wave is past the previous epilogue's LDS reads
+    __syncthreads();                                             // every wave is past the previous epilogue's LDS reads
     // which tile comes next is scalar work (two divisions, the grouped launches' table look-ups): done HERE, where it shares the
     // issue slots with the main loop's first MFMAs, instead of between the main loop and the epilogue (~1 k cycles per tile)
     int hn = h + gridDim.x;
     TileCtx nx; nx.ok = 0;
     while (hn < total) {
-      nx = tile_ctx<BM2, BN2, KEXT>(p, hn, total);
+      nx = tile_ctx<BM2, BN2>(p, hn, total);
       if (nx.ok) break;
       hn += gridDim.x;
     }
@@ -599,7 +527,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
         for (int i = 0; i < MI; ++i) af[i] = *(const bf16x8*)(S + a_rd + i * 2048 + ko);
         if (kk == 0) {
           if (more) {
-            ext_switch(cur, kt + 1);
             dma_tile(nxt);
           } else {
             dma_epi(cur, nxt);
@@ -625,7 +552,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
     }
     if (!lag) __builtin_amdgcn_s_barrier();                      // both groups are past their last LDS read: both stages are free
 
-    if (LIFE) lf[2] = __builtin_amdgcn_s_memtime();
     // ---- the next tile of this workgroup (found before the main loop): its first K tile travels while the epilogue runs
     // the last K tile sat in stage `last`: free now, it takes the next tile's first K tile; the other one holds the epilogue's
     // constants until the next tile's SECOND K tile is requested (behind the next loop-top barrier, i.e. after this epilogue)
@@ -638,42 +564,28 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
       __syncthreads();
     }
     if (nx.ok) first_dma(nx, last);
-    if (LIFE) lf[3] = __builtin_amdgcn_s_memtime();
-    const float2* lut = (GELU && !(p.dbg & 8)) ? (const float2*)(els + EPI_LDS_TAB) : nullptr;   // (TA355_GELU_LUT=0: the arithmetic form)
+    const float2* lut = (GELU && !p.gelu_erf) ? (const float2*)(els + EPI_LDS_TAB) : nullptr;
 
     // ---- epilogue of `cur`.  Its index arithmetic starts from an opaque copy of the thread index: otherwise the compiler
     // hoists those loop-invariant values out of the tile loop and carries them, spilled, across the main loop.
-    if (!(p.dbg & 1)) {
-      const int te = fresh_tid();
-      const int e_l15 = te & 15, e_g = (te >> 4) & 3, e_wn = (te >> 6) & 3, e_wm = te >> 8;
-      char* Cb = (char*)p.C;
-      if (p.splits > 1) Cb += (long)cur.z * p.slab_stride * 4;
-      const bool wide = epilogue_wide_ok(p);
-      const int erow0 = e_wm * (BM2 / 2) + e_l15;
-      // full tiles (TA355_GEMM_DEBUG bit 11 switches this off): row-merged stores
-      const bool full = OUT_BF16 && wide && p.c_plain && (!HAS_RES || res_init) && ACT != 6 && cur.m0 + BM2 <= cur.Mact && cur.n0 + BN2 <= p.N &&
-                        !(p.dbg & 2048);
-      if constexpr (OUT_BF16 && ACT != 6) {
-        if (full) epilogue_tile_full<MI, NT, ACT, true>(acc, p, Cb, cur.m0 + erow0, cur.rbase, cur.n0 + e_wn * (BN2 / 4), e_g, cur.biasp, lut, els, cur.n0, erow0);
-      }
-      if (full) { }
-      else if (res_init)
-        epilogue_tile<MI, NT, ACT, OUT_BF16, false, 0, true>(acc, p, Cb, cur.m0 + erow0, cur.Mact, cur.rbase, cur.n0 + e_wn * (BN2 / 4), e_g,
-                                                             wide, cur.biasp, lut, els, cur.n0, erow0);
-      else
-        epilogue_tile<MI, NT, ACT, OUT_BF16, HAS_RES, ((BM2 == 192 || (HAS_RES && !OUT_BF16 && ACT == 0)) ? 1 : 0), true>(acc, p, Cb, cur.m0 + erow0, cur.Mact, cur.rbase,
-                                                                                  cur.n0 + e_wn * (BN2 / 4), e_g, wide, cur.biasp, lut, els, cur.n0, erow0);
+    const int te = fresh_tid();
+    const int e_l15 = te & 15, e_g = (te >> 4) & 3, e_wn = (te >> 6) & 3, e_wm = te >> 8;
+    char* Cb = (char*)p.C;
+    if (p.splits > 1) Cb += (long)cur.z * p.slab_stride * 4;
+    const bool wide = epilogue_wide_ok(p);
+    const int erow0 = e_wm * (BM2 / 2) + e_l15;
+    // full tiles: row-merged stores
+    const bool full = OUT_BF16 && wide && p.c_plain && (!HAS_RES || res_init) && cur.m0 + BM2 <= cur.Mact && cur.n0 + BN2 <= p.N;
+    if constexpr (OUT_BF16) {
+      if (full) epilogue_tile_full<MI, NT, ACT, true>(acc, p, Cb, cur.m0 + erow0, cur.rbase, cur.n0 + e_wn * (BN2 / 4), e_g, cur.biasp, lut, els, cur.n0, erow0);
     }
-    if (LIFE) {
-      lf[4] = __builtin_amdgcn_s_memtime();
-      if (lane == 0 && (wave & 3) == 0) {
-        unsigned long long* o = (unsigned long long*)((char*)p.C + (long)p.M * p.ldc * 2) + ((long)h * 2 + wm) * 8;
-        for (int q = 0; q < 5; ++q) o[q] = lf[q];
-        o[5] = __builtin_amdgcn_s_getreg(63492);
-        o[6] = __builtin_amdgcn_s_getreg(63508);
-        o[7] = (unsigned long long)blockIdx.x;
-      }
-    }
+    if (full) { }
+    else if (res_init)
+      epilogue_tile<MI, NT, ACT, OUT_BF16, false, 0, true>(acc, p, Cb, cur.m0 + erow0, cur.Mact, cur.rbase, cur.n0 + e_wn * (BN2 / 4), e_g,
+                                                           wide, cur.biasp, lut, els, cur.n0, erow0);
+    else
+      epilogue_tile<MI, NT, ACT, OUT_BF16, HAS_RES, ((BM2 == 192 || (HAS_RES && !OUT_BF16 && ACT == 0)) ? 1 : 0), true>(acc, p, Cb, cur.m0 + erow0, cur.Mact, cur.rbase,
+                                                                                cur.n0 + e_wn * (BN2 / 4), e_g, wide, cur.biasp, lut, els, cur.n0, erow0);
     if (!nx.ok) return;
     cur = nx; h = hn; ph = last;
   }
@@ -715,10 +627,9 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slabs, int splits
 //     per half-step against 400 with the DMA removed);
 //   * one barrier per K TILE: it publishes slot t+1 (every wave waited for its own share) and retires slot t-1.
 // Slot image: v2's ([rows][128 B], 16-B chunk index XOR (row >> 1 & 7), applied on the source side of the DMA).
-// EXP (experiments, wrong results): 1 no W fragment reads, 2 no A fragment reads, 3 neither, 4 no DMA after the prologue.
 template <int N> __device__ __forceinline__ void wait_vm_lgkm0_n() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 // KEXT: the K extension of ta_gemm_opts.a2 / w2 (LoRA): after the K tiles of A / W the groups continue over A2 / W2.
-template <int ACT, bool OUT_BF16, bool HAS_RES, int EXP = 0, bool KEXT = false>
+template <int ACT, bool OUT_BF16, bool HAS_RES, bool KEXT = false>
 __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
   constexpr int BM5 = 192, BN5 = 128, NS = 3;
   constexpr int A_BYTES = BM5 * 128, SLOT = (BM5 + BN5) * 128;
@@ -751,7 +662,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
   if (p.splits > 1) { kt_begin = (nkt * z) / p.splits; kt_end = (nkt * (z + 1)) / p.splits; }
   if (krp) { kt_begin = krp[0]; kt_end = krp[1]; }
   if (KEXT) kt_end = nkt + p.K2 / BK;              // host guarantees splits == 1, no krange
-  if (p.dbg & 2) kt_end = min(kt_end, kt_begin + 1);
   int Mact = p.M, rbase = 0;
   if (segp) { rbase = segp[0]; Mact = segp[1]; if (m0 >= Mact) return; }
 
@@ -789,14 +699,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
   const bool res_init = residual_is_start<ACT, OUT_BF16, HAS_RES>(p);
   if (res_init) residual_start<6, 4>(acc, p, m0 + wm * 96 + l15, Mact, rbase, n0 + wn * 64, g);
   else zero_acc<6, 4>(acc);
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
-  f32x16 acc32[6];                                    // EXP == 5 (timing only): the same tile as 6 blocks of 32x32, 12 MFMAs per half-step
-  if (EXP == 5) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc32[i][e] = 0.f;
-  }
 
   const int nt = kt_end - kt_begin;
   if (nt > 0) {
@@ -843,7 +745,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
     auto step = [&](auto first_tag, bf16x8* ca, bf16x8* cb, bf16x8* na, bf16x8* nb) {
       constexpr bool FIRST = decltype(first_tag)::value;
       const int nslot = rslot == NS - 1 ? 0 : rslot + 1;
-      if (FIRST || EXP == 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (FIRST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       else wait_vm_lgkm0_n<10>();
       // pass the fragments through an empty asm: the compiler's own wait for them lands HERE, not behind the reads issued below
 #pragma unroll
@@ -863,13 +765,10 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
 #pragma unroll
       for (int q = 0; q < 24; ++q) {
         const int i = q >> 2, j = q & 3;
-        if (EXP == 5) {                                         // every second slot: one 32x32x16 MFMA on arbitrary fragments (timing only)
-          if ((q & 1) == 0) acc32[q / 4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cb[j], ca[i], acc32[q / 4], 0, 0, 0);
-        } else
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cb[j], ca[i], acc[i][j], 0, 0, 0);
-        if (q < 4) { if (!(EXP & 1) || EXP == 4) nb[q] = *(const bf16x8*)(S + b_rd + q * 2048); }
-        else if (q < 10) { if (!(EXP & 2) || EXP == 4) na[q - 4] = *(const bf16x8*)(S + a_rd + (q - 4) * 2048); }
-        else if (FIRST && EXP != 4) {
+        if (q < 4) nb[q] = *(const bf16x8*)(S + b_rd + q * 2048);
+        else if (q < 10) na[q - 4] = *(const bf16x8*)(S + a_rd + (q - 4) * 2048);
+        else if (FIRST) {
           if (q < 16) glds16_s(ab, a_off[q - 10], base + (q - 10) * 4096);
           else if (q < 20) glds16_s(wb, w_off[q - 16], base + A_BYTES + (q - 16) * 4096);
         }
@@ -887,13 +786,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
 
   char* Cb = (char*)p.C;
   if (p.splits > 1) Cb += (long)z * p.slab_stride * 4;
-  if (p.dbg & 1) return;
-  if (EXP == 5) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][e] = (f32x4){acc32[i][4 * e], acc32[i][4 * e + 1], acc32[i][4 * e + 2], acc32[i][4 * e + 3]};
-  }
   const bool wide = epilogue_wide_ok(p);
   const float2* lut = stage_gelu_lut<ACT, 256>(smem, p, tid, true);
   if (res_init) epilogue_tile<6, 4, ACT, OUT_BF16, false>(acc, p, Cb, m0 + wm * 96 + l15, Mact, rbase, n0 + wn * 64, g, wide, biasp, lut);
@@ -913,30 +805,24 @@ bool g_log_on = false;
 std::vector<long> g_log;
 }  // namespace
 
-// The library carries the variants the launch-time model can choose (0-5, 10, 12).  Rounds 2-5 also had, behind an experiment build
-// flag, the ring form (6 / 7), stamped timing builds (8 / 9), the 32x32x16 form of v5 (11) and v5's timing experiments: all removed
-// in round 6 (scripts/attic/gemm_r05_with_experiments.hip.txt keeps the source, profiles/ the measurements).
+// The library carries the variants the launch-time model can choose (0-5, 10, 12).  Rounds 2-5 also had, in experiment builds,
+// the ring form (6 / 7), stamped timing builds (8 / 9), the 32x32x16 form of v5 (11) and v5's timing experiments: all removed
+// (scripts/attic/gemm_r05_with_experiments.hip.txt keeps the source, profiles/ the measurements).
 // Tile variant: 0 = 128x128 (4 waves, 2 WG/CU), 5 = 96x128 (same kernel), 1 = 256x256, 2 = 256x128 (8 waves, 1 WG/CU), 3 = 256x256 ping-pong,
 // 4 = 256x320 ping-pong (N = 1280 / 3840 / 5120 divide exactly: M = 16000 x N = 1280 is 252 tiles = ONE round of 256 CUs).
 // Model: time ~ rounds(tiles / resident slots) * tile area / relative rate; pick the cheapest.  The relative rates
-// come from scripts/gemm_bench.py on MI355X (see profiles/).  TA355_GEMM_VARIANT=0..3 forces one (experiments, tests).
+// come from scripts/gemm_bench.py on MI355X (see profiles/).  TA355_GEMM_VARIANT forces one (tests, microbenchmarks).
 #include <cstdlib>
-// Every environment knob of the GEMM launcher, read ONCE (round 4: they were 17 getenv calls PER LAUNCH, and a debug bit that aliased
-// an experimental build corrupted a reported A/B in round 3).  ta_gemm_reload_knobs() re-reads the environment: tests and the A/B
-// scripts that switch a knob between launches call it (tiny_audio_amd/ops.py does so when it sees one of them change).
+// The two environment knobs of the GEMM launcher, read ONCE (round 4: they were 17 getenv calls PER LAUNCH).
+// ta_gemm_reload_knobs() re-reads the environment: tests and the A/B scripts that switch a knob between launches call it
+// (tiny_audio_amd/ops.py does so when it sees one of them change).
 struct GemmKnobs {
-  int variant, no96, v5_mink, ring, persist_kext, m32, group_m, group_m_auto, epi_narrow, dbg, persist;
-  double r320, r10, r12;
+  int variant;    // TA355_GEMM_VARIANT: force one tile variant; -1 = the model's choice
+  int gelu_erf;   // TA355_GELU_LUT=0: arithmetic erf-GELU instead of the chord table (the tests compare both)
   void load() {
-    auto s = [](const char* n) -> const char* { const char* v = getenv(n); return (v && *v) ? v : nullptr; };
-    auto i = [&](const char* n, int d) { const char* v = s(n); return v ? atoi(v) : d; };
-    variant = i("TA355_GEMM_VARIANT", -1);        // force one tile variant (tests, microbenchmarks)
-    dbg = 0;
-    if (i("TA355_GELU_LUT", 1) == 0) dbg |= 8;    // arithmetic erf-GELU instead of the chord table (the tests compare both)
-    // The library has exactly these two run-time knobs.  Everything below is the measured default (rounds 1-5 read the environment
-    // for them in experiment builds).
-    no96 = 0; r320 = TA355_RATE_256x320_PP; r10 = TA355_RATE_192x128; r12 = TA355_RATE_192x256_PP; v5_mink = 2048; ring = 0;
-    persist_kext = 0; m32 = 0; group_m = 0; group_m_auto = 0; epi_narrow = 0; persist = 1;
+    auto i = [](const char* n, int d) { const char* v = getenv(n); return (v && *v) ? atoi(v) : d; };
+    variant = i("TA355_GEMM_VARIANT", -1);
+    gelu_erf = i("TA355_GELU_LUT", 1) == 0;
   }
 };
 static GemmKnobs& knobs() {
@@ -947,15 +833,12 @@ void ta_i_reload_decode_knobs();   // generate.hip: TA355_DECODE_FUSED
 extern "C" int ta_gemm_reload_knobs(void) { knobs().load(); ta_i_reload_decode_knobs(); return TA_OK; }
 
 static int pick_variant(int M, int N, int K, int splits) {
-  const GemmKnobs& kn = knobs();
-  const int forced = kn.variant;
+  const int forced = knobs().variant;
   if (forced >= 0 && forced <= 12 && !(forced >= 6 && forced <= 9) && forced != 11) return forced;
-  const bool no96 = kn.no96;
-  const double r320 = kn.r320;
-  const double rate[6] = {1.0, TA355_RATE_256x256, TA355_RATE_256x128, TA355_RATE_256x256_PP, r320, TA355_RATE_96x128};
+  const double rate[6] = {1.0, TA355_RATE_256x256, TA355_RATE_256x128, TA355_RATE_256x256_PP, TA355_RATE_256x320_PP, TA355_RATE_96x128};
   const int bm[6] = {128, 256, 256, 256, 256, 96}, bn[6] = {128, 256, 128, 256, 320, 128}, slots[6] = {512, 256, 256, 256, 256, 512};
   int best = 0; double best_t = 1e300;
-  for (int v = 0; v < (no96 ? 5 : 6); ++v) {
+  for (int v = 0; v < 6; ++v) {
     const long tiles = (long)ta_cdiv(M, bm[v]) * ta_cdiv(N, bn[v]) * splits;
     const double rounds = (double)((tiles + slots[v] - 1) / slots[v]);
     // a round of variant v costs (tile area / rate) per slot; variants 0 and 5 run two tiles per CU concurrently
@@ -963,19 +846,16 @@ static int pick_variant(int M, int N, int K, int splits) {
     if (t < best_t) { best_t = t; best = v; }
   }
   {                                                  // 10 = 192x128, one 4-wave workgroup per CU (v5)
-    const double r10 = kn.r10;
     const long tiles = (long)ta_cdiv(M, 192) * ta_cdiv(N, 128) * splits;
-    const double t = (double)((tiles + 255) / 256) * 192.0 * 128.0 / r10;
+    const double t = (double)((tiles + 255) / 256) * 192.0 * 128.0 / TA355_RATE_192x128;
     // only long contractions: with one workgroup per CU nothing overlaps its prologue and epilogue (K = 1280: 33 vs 28 us for 96x128)
-    const int mink = kn.v5_mink;
-    if (r10 > 0.0 && K / splits >= mink && t < best_t) { best_t = t; best = 10; }
+    if (TA355_RATE_192x128 > 0.0 && K / splits >= 2048 && t < best_t) { best_t = t; best = 10; }
   }
   {                                                  // 12 = 192x256 ping-pong, persistent (v4 with BM2 = 192)
-    const double r12 = kn.r12;
     const long tiles = (long)ta_cdiv(M, 192) * ta_cdiv(N, 256) * splits;
-    const double t = (double)((tiles + 255) / 256) * 192.0 * 256.0 / r12;
+    const double t = (double)((tiles + 255) / 256) * 192.0 * 256.0 / TA355_RATE_192x256_PP;
     // (the same minimum contraction length as for v5's own choice -- two K tiles -- so that tiny-K launches stay on the small tiles)
-    if (r12 > 0.0 && K / splits >= 128 && t < best_t) { best_t = t; best = 12; }
+    if (TA355_RATE_192x256_PP > 0.0 && K / splits >= 128 && t < best_t) { best_t = t; best = 12; }
   }
   // (Rounds 4-5 built two more kernel families on these tiles and removed them from the library after measuring them slower in the step:
   // gemm_v7 -- one 4-wave workgroup per CU, one wave per SIMD, 256 AGPR accumulators, 4-stage BK = 32 ring -- and its round-5
@@ -984,44 +864,50 @@ static int pick_variant(int M, int N, int K, int splits) {
   return best;
 }
 
+// The variant -> kernel map.  persist: variants 3 / 4 as persistent workgroups (v4, grid = one workgroup per CU at most) instead of one
+// workgroup per tile (v2); variant 12 exists in the persistent form only.  v4 has no K extension: the caller sends neither there with A2.
+template <int ACT, bool OUT_BF16, bool HAS_RES, bool KEXT>
+static void launch_variant(int variant, bool persist, int grid, int pgrid, const GemmArgs& a, hipStream_t st) {
+  if (variant == 0) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 128, KEXT>), dim3(grid), dim3(256), 0, st, a);
+  else if (variant == 5) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 96, KEXT>), dim3(grid), dim3(256), 0, st, a);
+  else if (variant == 1) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, false, KEXT>), dim3(grid), dim3(512), 0, st, a);
+  else if (variant == 12) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES, 192>), dim3(pgrid), dim3(512), 0, st, a);
+  else if (variant == 3 && persist) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
+  else if (variant == 4 && persist) TA_LAUNCH((gemm_nt_kernel_v4<320, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
+  else if (variant == 3) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, true, KEXT>), dim3(grid), dim3(512), 0, st, a);
+  else if (variant == 4) TA_LAUNCH((gemm_nt_kernel_v2<320, ACT, OUT_BF16, HAS_RES, true, KEXT>), dim3(grid), dim3(512), 0, st, a);
+  else if (variant == 10) TA_LAUNCH((gemm_nt_kernel_v5<ACT, OUT_BF16, HAS_RES, KEXT>), dim3(grid), dim3(256), 0, st, a);
+  else TA_LAUNCH((gemm_nt_kernel_v2<128, ACT, OUT_BF16, HAS_RES, false, KEXT>), dim3(grid), dim3(512), 0, st, a);
+}
+
 template <int ACT, bool OUT_BF16, bool HAS_RES>
 static int launch_gemm(GemmArgs a, hipStream_t st) {
-  const GemmKnobs& kn = knobs();
+  if (a.A2 && ACT != 0) return TA_ERR_ARG;          // the K extension exists for plain linears only (LoRA)
   int variant = pick_variant(a.M, a.N, a.K, a.splits);
   const bool a_far = !a.a_plain && ((long)(a.M / a.a_rpb + 1) * a.a_bs + a.lda * a.a_rpb) * 2 >= (1L << 32);   // row-mapped A is addressed from its start with 32-bit offsets
   if (variant == 10 && (a.w_blocked || a.a_idx || a_far)) variant = 5;     // v5: no gather, plain W only
-  // the 192-row tile exists in the persistent form only (TA355_GEMM_PERSIST=0 maps it back to the 256x256 tile on v2)
-  if (variant == 12 && (a.a_idx || a_far || (a.A2 && !kn.persist_kext) || kn.persist == 0)) variant = 3;
-  if (a.w_blocked && variant >= 6 && variant != 12) return TA_ERR_ARG;         // the ring kernel (and v5 / v6) stage plain [N, K] weights only
+  // the 192-row tile exists in the persistent form only: what that form does not take goes to the 256x256 tile
   if (variant == 12 && (a.a_idx || a_far || a.A2)) variant = 3;
   const int bm = variant == 0 ? 128 : (variant == 5 ? 96 : ((variant == 10 || variant == 12) ? 192 : 256));
   const int bn = variant == 4 ? 320 : ((variant == 1 || variant == 3 || variant == 12) ? 256 : 128);
   // rows-grouped launch: every group may end in a partial M tile, so the tile grid is an upper bound (surplus tiles exit)
   a.tiles_m = ta_cdiv(a.M, bm) + ((a.grp_n > 0 && a.seg) ? a.grp_n : 0); a.tiles_n = ta_cdiv(a.N, bn);
   const int grid = a.tiles_m * a.tiles_n * a.splits;
-  {
-    a.group_m = kn.group_m > 0 ? kn.group_m : (variant != 0 && a.tiles_m <= 8 ? a.tiles_m : 0);   // few M-tiles (LM head): one group, W panels read once per XCD (TA355_GROUP_M: experiments)
-    // 12 column tiles of 320 (the encoder's q | k | v GEMM, 3 rounds): groups of 16 row tiles instead of 4 -- an XCD's round is then
-    // 16 row tiles x 2 column tiles.  Cold operands (profiles/r03_c_gemm_enc_groupm_cold.txt): 146.3 us against 153.9 (g = 8:
-    // 148.1); N = 5120 / 1280 shapes are flat in g.  Experiment only (TA355_GROUP_M_AUTO=1): no gain in the step.
-    const bool gauto = kn.group_m_auto;       // opt-in: in the STEP it measured 42.85 vs 42.79 ms (profiles/r03_d_ab_groupm.txt)
-    if (kn.group_m <= 0 && gauto && variant == 4 && a.tiles_n == 12 && a.tiles_m >= 32) a.group_m = 16;
-    a.wide = (((long)a.N | a.ldc | a.c_off | a.c_bs) & 7) == 0 && !kn.epi_narrow;   // (TA355_EPI_WIDE=0: 8-B bf16 stores)
-    a.dbg = kn.dbg;
-  }
-  // ping-pong tiles as persistent workgroups (v4) unless TA355_GEMM_PERSIST=0; grid = one workgroup per CU at most
-  // gathered A rows stay on v2 (their offsets are not bounded by the tile); so does the K extension (LoRA): with its pointer switch
-  // the persistent form spills in the tile loop (LoRA step 54.5 ms against 53.6 with v2)
-  bool persist = (variant == 3 || variant == 4) && !a.a_idx && !a.A2;
+  // few M-tiles (LM head): one group, W panels read once per XCD; otherwise the kernel's own group height.
+  // (Round 3, measured and not kept: groups of 16 row tiles instead of 4 for the 12 column tiles of 320 of the encoder's q | k | v GEMM
+  // -- an XCD's round is then 16 row tiles x 2 column tiles.  Cold operands (profiles/r03_c_gemm_enc_groupm_cold.txt): 146.3 us against
+  // 153.9 (g = 8: 148.1); N = 5120 / 1280 shapes are flat in g; in the STEP 42.85 vs 42.79 ms (profiles/r03_d_ab_groupm.txt).)
+  a.group_m = (variant != 0 && a.tiles_m <= 8) ? a.tiles_m : 0;
+  a.wide = (((long)a.N | a.ldc | a.c_off | a.c_bs) & 7) == 0;
+  a.gelu_erf = knobs().gelu_erf;
+  // Ping-pong tiles run as persistent workgroups (v4).  Gathered A rows stay on v2 (their offsets are not bounded by the tile) and so
+  // does far row-mapped A.  So does the K extension (LoRA): its first persistent form hoisted the extension's nine DMA offsets out of
+  // the tile loop and spilled the regular ones (91.8 against 61.6 us per launch, profiles/r03_p_ab_lora.txt); with the offsets derived
+  // from a fresh thread index at the switch there was no scratch and the LoRA step was the same on both kernels (45.45 ms each,
+  // profiles/r03_r_ab_lora_persist_kext.txt), so v4 carries no extension.
+  // (variant 12 is always persistent; `persist`, which the launch log records, says which form variants 3 / 4 take)
+  const bool persist = (variant == 3 || variant == 4) && !a.a_idx && !a.A2 && !a_far;
   static const int ncu = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-  if (kn.persist == 0 || (kn.persist == 2 && grid <= ncu)) persist = false;   // TA355_GEMM_PERSIST: 0 never, 2 only launches of more than one round
-  if (a_far) persist = false;
-  // round 3: the K extension on the persistent kernel re-measured (TA355_GEMM_PERSIST_KEXT=1; default: v2 as in round 2).  First
-  // attempt: 91.8 against 61.6 us per launch (profiles/r03_p_ab_lora.txt) -- the extension's nine DMA offsets, loop-invariant from
-  // threadIdx.x, had been hoisted out of the tile loop and pushed the regular offsets into scratch, reloaded behind a vmcnt(0)
-  // between the DMA issues of every K tile.  With the offsets derived from a fresh thread index at the switch: no scratch, and the
-  // LoRA step is the same on both kernels (45.45 ms each, profiles/r03_r_ab_lora_persist_kext.txt)
-  const bool persist_kext = kn.persist_kext && a.A2 && !a.a_idx && !a_far && (variant == 3 || variant == 4 || variant == 12);
   const int pgrid = grid < ncu ? grid : ncu;
   ProfRec r;
   if (g_prof_on) {
@@ -1029,32 +915,10 @@ static int launch_gemm(GemmArgs a, hipStream_t st) {
     r.flops = 2.0 * (double)a.M * (double)a.N * (double)a.K;
     (void)hipEventRecord(r.a, st);
   }
-  if (a.A2) {
-    if constexpr (ACT == 0) {                     // the K extension exists for plain linears only (LoRA)
-      if (variant == 0) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 128, true>), dim3(grid), dim3(256), 0, st, a);
-      else if (variant == 5) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 96, true>), dim3(grid), dim3(256), 0, st, a);
-      else if (variant == 1) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, false, true>), dim3(grid), dim3(512), 0, st, a);
-      else if (variant == 12) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES, true, false, 192>), dim3(pgrid), dim3(512), 0, st, a);
-      else if (variant == 3 && persist_kext) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES, true>), dim3(pgrid), dim3(512), 0, st, a);
-      else if (variant == 4 && persist_kext) TA_LAUNCH((gemm_nt_kernel_v4<320, ACT, OUT_BF16, HAS_RES, true>), dim3(pgrid), dim3(512), 0, st, a);
-      else if (variant == 3) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, true, true>), dim3(grid), dim3(512), 0, st, a);
-      else if (variant == 4) TA_LAUNCH((gemm_nt_kernel_v2<320, ACT, OUT_BF16, HAS_RES, true, true>), dim3(grid), dim3(512), 0, st, a);
-      else if (variant == 10) TA_LAUNCH((gemm_nt_kernel_v5<ACT, OUT_BF16, HAS_RES, 0, true>), dim3(grid), dim3(256), 0, st, a);
-      else TA_LAUNCH((gemm_nt_kernel_v2<128, ACT, OUT_BF16, HAS_RES, false, true>), dim3(grid), dim3(512), 0, st, a);
-    } else {
-      return TA_ERR_ARG;
-    }
+  if constexpr (ACT == 0) {
+    if (a.A2) launch_variant<ACT, OUT_BF16, HAS_RES, true>(variant, persist, grid, pgrid, a, st);
   }
-  else if (variant == 0) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES>), dim3(grid), dim3(256), 0, st, a);
-  else if (variant == 5) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 96>), dim3(grid), dim3(256), 0, st, a);
-  else if (variant == 1) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, false>), dim3(grid), dim3(512), 0, st, a);
-  else if (variant == 12) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES, false, false, 192>), dim3(pgrid), dim3(512), 0, st, a);
-  else if (variant == 3 && persist) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
-  else if (variant == 4 && persist) TA_LAUNCH((gemm_nt_kernel_v4<320, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
-  else if (variant == 3) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, true>), dim3(grid), dim3(512), 0, st, a);
-  else if (variant == 4) TA_LAUNCH((gemm_nt_kernel_v2<320, ACT, OUT_BF16, HAS_RES, true>), dim3(grid), dim3(512), 0, st, a);
-  else if (variant == 10) TA_LAUNCH((gemm_nt_kernel_v5<ACT, OUT_BF16, HAS_RES>), dim3(grid), dim3(256), 0, st, a);
-  else TA_LAUNCH((gemm_nt_kernel_v2<128, ACT, OUT_BF16, HAS_RES, false>), dim3(grid), dim3(512), 0, st, a);
+  if (!a.A2) launch_variant<ACT, OUT_BF16, HAS_RES, false>(variant, persist, grid, pgrid, a, st);
   if (g_prof_on) { (void)hipEventRecord(r.b, st); g_prof.push_back(r); }
   if (g_log_on) {
     const long flags = (a.a_idx ? 1 : 0) | (a.seg ? 2 : 0) | (a.krange ? 4 : 0) | (a.A2 ? 8 : 0) | (a.w_blocked ? 16 : 0) | (a.grp_n > 0 ? 32 : 0) |
@@ -1158,13 +1022,12 @@ extern "C" int ta_gemm_bf16_nt_opt(const void* A, const void* W, void* C, int M,
   a.A2 = (const bf16_t*)xA2; a.W2 = (const bf16_t*)xW2; a.K2 = xK2; a.lda2 = o.lda2;
   a.res_bf16 = resb != nullptr;
   a.rope_tab = o.rope_tab; a.rope_rows = o.rope_rows; a.rope_cols = o.rope_cols > 0 ? o.rope_cols : N;
-  a.w_blocked = o.w_blocked ? 1 : 0;
-  a.dbg = 0; a.grp_n = 0; a.grp_w_stride = 0;
+  a.w_blocked = o.w_blocked ? 1 : 0; a.a_blocked = 0;
+  a.grp_n = 0; a.grp_w_stride = 0;
   if (a.w_blocked && ((N & 63) || xA2 || krange || a_idx)) return TA_ERR_ARG;
   if (act == 2 && (!o.rope_tab || o.rope_rows <= 0 || !out_bf16 || residual || splits > 1 || (N % 64) || o.rope_cols < 0 || (o.rope_cols % 64))) return TA_ERR_ARG;
   if (resb && splits > 1) return TA_ERR_ARG;
   if (a.A2 && (splits > 1 || krange)) return TA_ERR_ARG;
-  a.tiles_m = ta_cdiv(M, BM); a.tiles_n = ta_cdiv(N, BN);
   a.splits = splits > 1 ? splits : 1;
   if (a.splits > K / BK) a.splits = K / BK;
   a.slab_stride = (long)M * N;
@@ -1212,11 +1075,10 @@ extern "C" int ta_gemm_bf16_nt_grouped(const void* A, const void* W, void* C, in
   a.a_plain = 1; a.c_plain = 1;
   a.a_idx = a_idx; a.seg = seg; a.krange = krange;
   a.A2 = nullptr; a.W2 = nullptr; a.K2 = 0; a.lda2 = 0; a.res_bf16 = 0;
-  a.rope_tab = nullptr; a.rope_rows = 0; a.rope_cols = 0; a.w_blocked = 0; a.dbg = 0;
+  a.rope_tab = nullptr; a.rope_rows = 0; a.rope_cols = 0; a.w_blocked = 0; a.a_blocked = 0;
   a.grp_n = n_groups; a.grp_w_stride = w_stride;
   a.splits = krange ? n_groups : 1;           // K-slice form: z = group, slabs c_stride apart
   a.slab_stride = krange ? c_stride : (long)M * N;
-  a.tiles_m = ta_cdiv(M, BM); a.tiles_n = ta_cdiv(N, BN);
   if (act == 1) return out_bf16 ? launch_gemm<1, true, false>(a, st) : launch_gemm<1, false, false>(a, st);
   return out_bf16 ? launch_gemm<0, true, false>(a, st) : launch_gemm<0, false, false>(a, st);
 }

@@ -32,7 +32,8 @@ struct GemmArgs {
   int wide;            // bf16 epilogue may use 16-B (8-column) stores: N, ldc, c_off, c_bs all multiples of 8
   int w_blocked;       // W is stored as [N/64][K/64][64][64] blocks (8 KB contiguous per 64 rows x one K tile)
   int a_plain, c_plain; // the row map is the identity (one batch): skips two integer divisions per row in prologue / epilogue
-  int dbg;             // experiments only (TA355_GEMM_DEBUG): bit 0 = no epilogue stores, bit 1 = contract over ONE K tile only
+  int gelu_erf;        // act == 1: the arithmetic erf-GELU (gelu_erf_fast) instead of the chord table
+  int a_blocked;       // A is stored in blocks like W under w_blocked (the persistent kernel only; always 0, see gemm_nt_kernel_v4)
   // Grouped launch (MoE experts in ONE launch, ta_gemm_bf16_nt_grouped):
   //   rows form    seg = int[2 * grp_n] {row base, row count}: M tile indices run over the concatenation of the groups' row
   //                tiles; group e multiplies by W + e * grp_w_stride and adds bias + e * N
@@ -107,9 +108,6 @@ __device__ __forceinline__ float gelu_lut(float x, const float2* lut) {
 // tiles 236.6 -> 214.0 us); against the previous build of the library it is equal on the 256-column tiles and 0.3-0.8 ms per step
 // slower on 256x320 (profiles/r03_ad_gemm_lib_probe.txt, r03_ad_ab_store_merge_libs.txt): what the first comparison measured was the
 // slowdown of carrying both forms -- with per-strip row offsets and guards for every lane -- in one epilogue.)
-#ifndef TA355_GELU_ALWAYS_LUT
-#define TA355_GELU_ALWAYS_LUT 0     /* gemm_v7.hip: 1 -- its table is always staged, the arithmetic form is not compiled in */
-#endif
 __device__ __forceinline__ int opaque_sgpr(int v) { asm volatile("" : "+s"(v)); return v; }
 template <int NT> struct EpiPre { uint2 r[NT]; };
 // oret != nullptr (bf16 outputs): the strip's packed results are handed back instead of stored (epilogue_tile_full stores them)
@@ -150,7 +148,7 @@ __device__ __forceinline__ void epilogue_strip(const f32x4* acc, const GemmArgs&
     f32x4 v = acc[j];
     if (bias) { v[0] += bq[j].x; v[1] += bq[j].y; v[2] += bq[j].z; v[3] += bq[j].w; }
     if (BASE == 1) {
-      if (TA355_GELU_ALWAYS_LUT || lut) { v[0] = gelu_lut(v[0], lut); v[1] = gelu_lut(v[1], lut); v[2] = gelu_lut(v[2], lut); v[3] = gelu_lut(v[3], lut); }
+      if (lut) { v[0] = gelu_lut(v[0], lut); v[1] = gelu_lut(v[1], lut); v[2] = gelu_lut(v[2], lut); v[3] = gelu_lut(v[3], lut); }
       else { v[0] = gelu_erf_fast(v[0]); v[1] = gelu_erf_fast(v[1]); v[2] = gelu_erf_fast(v[2]); v[3] = gelu_erf_fast(v[3]); }
     }
     if (BASE == 2) {
@@ -362,7 +360,6 @@ __device__ __forceinline__ void epilogue_tile(const f32x4 (*acc)[NT], const Gemm
 // the accumulators in EVERY tile variant, not an addend of the epilogue: the sum is then fl(..fl(fl(r + a0 w0) + a1 w1)..) + b
 // whatever tile the launch-time model picks (the B = 32 step and the same clips at B = 4 run different variants and are compared
 // in the tests), and the kernels' epilogues have no residual load left to wait for.  Loads in batches of <= 4 strips.
-// TA355_GEMM_RES_INIT=0 (p.dbg bit 20): the r02 form, residual added in the epilogue.
 // (Round 6 tried the same for an f32 residual with an f32 output -- the fp32-stream mode: float4 loads straight into the accumulator
 // registers behind the first K tile's DMA.  Same-box A/B, profiles/r06_b_ab_f32.txt: the encoder's o_proj / fc2 launches 133.8 us
 // against 130.2, the LM's one-wave-per-SIMD tiles 65.2 against 43.2: the start values must have landed before the first MFMA, so
@@ -370,7 +367,7 @@ __device__ __forceinline__ void epilogue_tile(const f32x4 (*acc)[NT], const Gemm
 // of the first K tile.  Removed.)
 template <int ACT, bool OUT_BF16, bool HAS_RES>
 __device__ __forceinline__ bool residual_is_start(const GemmArgs& p) {
-  return HAS_RES && ACT == 0 && OUT_BF16 && p.res_bf16 && p.splits == 1 && !(p.dbg & (1 << 20));
+  return HAS_RES && ACT == 0 && OUT_BF16 && p.res_bf16 && p.splits == 1;
 }
 // HBMAX: strips per batch of loads (0: half the tile, at most 4); PIN (gemm_v7.hip): the first PIN fragments of a strip are AGPR
 // accumulators -- each start value moves there as soon as it is converted
@@ -417,7 +414,7 @@ __device__ __forceinline__ void zero_acc(f32x4 (*acc)[NT]) {
 template <int ACT, int NTHREADS>
 __device__ __forceinline__ const float2* stage_gelu_lut(char* smem, const GemmArgs& p, int tid, bool barrier_first) {
   if constexpr (ACT == 1) {
-    if (!(p.dbg & 8)) {
+    if (!p.gelu_erf) {
       if (barrier_first) __syncthreads();
       for (int i = tid; i < GELU_LUT_N * 8 / 16; i += NTHREADS) ((uint4*)smem)[i] = ((const uint4*)kGeluLut)[i];
       __syncthreads();
@@ -453,7 +450,7 @@ __device__ __forceinline__ bool resolve_group(const GemmArgs& p, int& pm, int z,
 }
 
 struct TileCtx { int ok, m0, n0, kb, ke, Mact, rbase, z; const bf16_t* Wp; const float* biasp; };
-template <int BM2, int BN2, bool KEXT>
+template <int BM2, int BN2>
 __device__ __forceinline__ TileCtx tile_ctx(const GemmArgs& p, int h, int total) {
   TileCtx c; c.ok = 0;
   int bid = h;
@@ -478,8 +475,6 @@ __device__ __forceinline__ TileCtx tile_ctx(const GemmArgs& p, int h, int total)
   c.kb = 0; c.ke = nkt;
   if (p.splits > 1) { c.kb = (nkt * z) / p.splits; c.ke = (nkt * (z + 1)) / p.splits; }   // 32-bit: the 64-bit quotients of v2 cost ~2 k cycles per tile
   if (krp) { c.kb = krp[0]; c.ke = krp[1]; }
-  if (KEXT) c.ke = nkt + p.K2 / BK;
-  if (p.dbg & 2) c.ke = min(c.ke, c.kb + 1);
   c.Mact = p.M; c.rbase = 0;
   if (segp) { c.rbase = segp[0]; c.Mact = segp[1]; if (c.m0 >= c.Mact) return c; }
   // wave-uniform by construction; values that came through a vector load (segment / K-range tables) are marked as such, so the K

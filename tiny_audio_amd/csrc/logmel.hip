@@ -98,7 +98,7 @@ __device__ __forceinline__ void fft25(cpx* y) {
 template <int LFT, int LF_G, bool MFMA = false>
 __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict__ wav, int Ls, const float* __restrict__ dft,
                                                          const float* __restrict__ window, const float* __restrict__ melfb,
-                                                         int n_mels, float* __restrict__ out, float* __restrict__ wg_rec, int T, int dbg,
+                                                         int n_mels, float* __restrict__ out, float* __restrict__ wg_rec, int T,
                                                          const int* __restrict__ mrange_g, int nseg,
                                                          const long* __restrict__ lens, int* __restrict__ mask, int nblk, int ntiles) {
   constexpr int LF_SPAN = (LFT - 1) * HOP + NFFT, LF_SCR = LF_G * NFFT * 2, LF_MELS = LFT + 1;
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict
   }
   __syncthreads();
   if (tile + tstride < tend && fast(tile + tstride)) LM_REQUEST(tile + tstride);     // in flight under this tile's transform
-  for (int it = 0; it < ((dbg & 1) ? 0 : LFT / 2 / 4 / LF_G); ++it) {            // LFT / 2 pairs per workgroup, a quarter per wave, LF_G at a time
+  for (int it = 0; it < LFT / 2 / 4 / LF_G; ++it) {            // LFT / 2 pairs per workgroup, a quarter per wave, LF_G at a time
     const int pair0 = wave * (LFT / 8) + it * LF_G;
     if constexpr (MFMA) {
       // ---- stage A: two column blocks at a time (four independent accumulator chains).  Per lane and column block everything that
@@ -341,12 +341,12 @@ __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict
   const int fgroups = 256 / n_mels;
   const int m = tid % n_mels, fg = tid / n_mels, nf = LFT / fgroups;
   const int klo = mrange[2 * m], khi = mrange[2 * m + 1];
-  for (int fb = 0; fb < ((dbg & 16) ? 0 : nf); fb += 16) {
+  for (int fb = 0; fb < nf; fb += 16) {
     float am[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) am[q] = 0.f;
     const int f0 = fg * nf + fb;
-    for (int kk = klo; kk < ((dbg & 2) ? klo : khi); ++kk) {
+    for (int kk = klo; kk < khi; ++kk) {
       const float wgt = melfb[kk * n_mels + m];
 #pragma unroll
       for (int q = 0; q < 16; ++q) am[q] = fmaf(wgt, pw[(f0 + q) * LF_PWS + kk], am[q]);
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict
   run_max = fmaxf(run_max, wm);
   if (tile + 1 >= tend && tid == 0) wg_rec[(long)blockIdx.x * nseg + (b - tile0 / nblk)] = run_max;
   const float floorv = -INFINITY, add = 0.f, mul = 1.f;           // (floor and scale are applied by the finalize pass)
-  for (int i = tid; i < ((dbg & 8) ? 0 : n_mels * LFT); i += 256) {                 // one mel row = LFT consecutive frames per store
+  for (int i = tid; i < n_mels * LFT; i += 256) {                 // one mel row = LFT consecutive frames per store
     const int r = i / LFT, f = i - r * LFT;
     if (t0 + f < T) out[((long)b * n_mels + r) * T + t0 + f] = (fmaxf(melbuf[r * LF_MELS + f], floorv) + add) * mul;
   }
@@ -473,9 +473,9 @@ extern "C" int ta_logmel_f32(const float* wav, const long* lens, int B, int Ls, 
     // sub-transforms on the f32 matrix cores (76.4 against 68.2, profiles/r04_za_*; experiment builds only).
     const dim3 grid(g.grid);
     if (g.wide)
-      TA_LAUNCH((logmel_fft_kernel<64, 4>), grid, dim3(256), lds_of(64, 4), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, 0, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);
+      TA_LAUNCH((logmel_fft_kernel<64, 4>), grid, dim3(256), lds_of(64, 4), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);
     else
-      TA_LAUNCH((logmel_fft_kernel<32, 2>), grid, dim3(256), lds_of(32, 2), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, 0, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);
+      TA_LAUNCH((logmel_fft_kernel<32, 2>), grid, dim3(256), lds_of(32, 2), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);
   }
   {
     int gx = ta_cdiv((long)n_mels * T, 256 * 4); if (gx < 1) gx = 1;
