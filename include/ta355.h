@@ -110,6 +110,35 @@ long ta_encoder_workspace_bytes(const ta_encoder_weights* w, int B, int T);
 int ta_encoder_forward(const ta_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
                        void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st);
 
+/* ---- frozen Whisper encoder (any openai/whisper-* checkpoint; the reference's other audio_tower, tiny_audio/asr_modeling.py:203-237):
+ *      replaces WhisperEncoder.forward(input_features).last_hidden_state (TF:models/whisper/modeling_whisper.py:592-650).
+ * The stem, the layer arithmetic (TF:models/whisper/modeling_whisper.py:379-407: pre-LN, q/v/out bias, k without, exact GELU,
+ * scale head_dim^-0.5, no mask) and the final LayerNorm are the GLM-ASR tower's, so ta_enc_layer is reused unchanged with
+ *   ln1_* = self_attn_layer_norm, ln2_* = final_layer_norm, wo/bo = self_attn.out_proj, w1/b1 = fc1, w2/b2 = fc2, and
+ *   wqkv_fa / bqkv_fa (REQUIRED here) = q | k | v rows in their natural order -- no rotary row interleave -- with the q rows and
+ *   the q bias multiplied by head_dim^-0.5 * log2(e), the k part of the bias zero.  wqkv / bqkv are not read.
+ * What differs: no rotary embedding anywhere; instead pos_emb (embed_positions.weight) is added once to the stem's output
+ * (TF:models/whisper/modeling_whisper.py:622-624), and the input must span exactly 2 * max_pos frames (:612-616). */
+typedef struct {
+  int hidden, ffn, n_layers, heads, n_mels, max_pos;   /* head_dim = hidden / heads must be 64; hidden, ffn multiples of 128; n_mels of 8 */
+  float ln_eps;
+  const void* conv1_w;  /* bf16 [H, K1], K1 = 3*n_mels rounded up to a multiple of 64 (256 at 80 bins); column = tap*n_mels + cin,
+                           columns 3*n_mels..K1-1 ZERO (the rows of the time-major input overlap: those columns meet the next frame) */
+  const float* conv1_b;
+  const void* conv2_w;  /* bf16 [H, 3*H], column = tap*H + cin */
+  const float* conv2_b;
+  const float* pos_emb; /* f32 [max_pos, H] = embed_positions.weight */
+  const float *norm_w, *norm_b;     /* layer_norm */
+  const ta_enc_layer* layers;       /* host array [n_layers] */
+  int res_f32;                      /* storage of the residual stream: 0 = bf16, 1 = fp32 (see the top of this file) */
+} ta_whisper_encoder_weights;
+
+long ta_whisper_encoder_workspace_bytes(const ta_whisper_encoder_weights* w, int B, int T);
+/* feats [B, n_mels, T] f32, T == 2 * max_pos (else TA_ERR_ARG) -> out_bf16 [B*S, H] (and/or out_f32), S = max_pos.
+ * frame_keep [B*S] f32 or NULL: as ta_encoder_forward (fused into the final LayerNorm). */
+int ta_whisper_encoder_forward(const ta_whisper_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
+                               void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st);
+
 /* ---- MLP projector: replaces MLPAudioProjector.forward + its autograd backward
  *      (tiny_audio/projectors.py:57-71,79-87). x bf16 [B, S, E] -> y f32 [B*N, D], N = (S-k)/k+1. */
 typedef struct {
@@ -538,6 +567,9 @@ int ta_transpose_to_bf16(const void* in, int in_is_f32, long ld_in, long in_bs, 
                          int R, int C, hipStream_t st);
 int ta_feats_to_time_major(const float* feats, void* out, int B, int C, int T, hipStream_t st);
 int ta_zero_pad_rows(void* buf, int B, int T, int C, hipStream_t st);
+/* Whisper's position table: x [B*S, H] (f32 if x_f32 else bf16) += pos f32 [S, H], row m taking table row m % S
+ * (hidden_states = inputs_embeds + embed_positions.weight, TF:models/whisper/modeling_whisper.py:622-624).  H % 8 == 0. */
+int ta_pos_add(void* x, int x_f32, const float* pos, int B, int S, int H, hipStream_t st);
 
 /* <audio> placeholder bookkeeping: _gather_audio_embeds + masked_scatter
  * (tiny_audio/asr_modeling.py:27-44,511-515). */

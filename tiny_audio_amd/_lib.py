@@ -43,6 +43,15 @@ class EncoderWeights(C.Structure):
                 ("layers", C.POINTER(EncLayer)), ("rope_il", C.c_void_p), ("res_f32", C.c_int)]
 
 
+class WhisperEncoderWeights(C.Structure):
+    """ta_whisper_encoder_weights (include/ta355.h); reuses EncLayer."""
+    _fields_ = [("hidden", C.c_int), ("ffn", C.c_int), ("n_layers", C.c_int), ("heads", C.c_int),
+                ("n_mels", C.c_int), ("max_pos", C.c_int), ("ln_eps", C.c_float),
+                ("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("conv2_w", C.c_void_p), ("conv2_b", C.c_void_p),
+                ("pos_emb", C.c_void_p), ("norm_w", C.c_void_p), ("norm_b", C.c_void_p),
+                ("layers", C.POINTER(EncLayer)), ("res_f32", C.c_int)]
+
+
 class MlpWeights(C.Structure):
     _fields_ = [("enc_dim", C.c_int), ("k", C.c_int), ("hidden", C.c_int), ("llm_dim", C.c_int), ("eps", C.c_float),
                 ("w1", C.c_void_p), ("w2", C.c_void_p), ("w2_t", C.c_void_p), ("g1", C.c_void_p), ("g2", C.c_void_p)]

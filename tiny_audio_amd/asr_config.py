@@ -2,7 +2,7 @@
 
 Mirrors ``tiny_audio/asr_config.py`` (field names, defaults, the conv length formula at :9-19) without
 depending on ``transformers``: sub-configs are plain objects carrying the shape fields the kernels need.
-An HF ``GlmAsrEncoderConfig`` / ``Qwen3Config`` (or a dict) can be passed wherever a sub-config is expected.
+An HF ``GlmAsrEncoderConfig`` / ``WhisperConfig`` / ``Qwen3Config`` (or a dict) can be passed wherever a sub-config is expected.
 """
 from __future__ import annotations
 
@@ -49,6 +49,62 @@ class EncoderConfig:
         self.layer_norm_eps = float(_get(src, ["layer_norm_eps", "ln_eps"], 1e-5))
         if self.hidden_size // self.num_attention_heads != 64 or self.partial_rotary_factor != 0.5:
             raise ValueError("ta355 encoder kernels are built for head_dim 64 with partial rotary 0.5 (GLM-ASR)")
+
+
+class WhisperEncoderConfig:
+    """The encoder half of a WhisperConfig (TF:models/whisper/configuration_whisper.py: d_model, encoder_layers,
+    encoder_attention_heads, encoder_ffn_dim, num_mel_bins, max_source_positions), under the attribute names the rest of the
+    package reads from ``EncoderConfig``.  ``WhisperEncoder`` uses nn.LayerNorm's default eps (1e-5)."""
+
+    model_type = "whisper"
+
+    def __init__(self, src=None, **kw):
+        src = {**(src if isinstance(src, dict) else {}), **kw} if (isinstance(src, dict) or src is None) else src
+        self.model_type = "whisper"
+        self.hidden_size = int(_get(src, ["d_model", "hidden_size", "hidden"], 384))
+        self.intermediate_size = int(_get(src, ["encoder_ffn_dim", "intermediate_size", "ffn"], 4 * self.hidden_size))
+        self.num_hidden_layers = int(_get(src, ["encoder_layers", "num_hidden_layers", "layers"], 4))
+        self.num_attention_heads = int(_get(src, ["encoder_attention_heads", "num_attention_heads", "heads"], self.hidden_size // 64))
+        self.num_mel_bins = int(_get(src, ["num_mel_bins", "n_mels"], 80))
+        self.max_source_positions = int(_get(src, ["max_source_positions", "max_position_embeddings"], 1500))
+        self.layer_norm_eps = float(_get(src, ["layer_norm_eps", "ln_eps"], 1e-5))
+        if self.num_attention_heads <= 0 or self.hidden_size != 64 * self.num_attention_heads:
+            raise ValueError("ta355 encoder kernels are built for head_dim 64 (every openai/whisper-* encoder)")
+
+    # the names WhisperConfig itself uses
+    d_model = property(lambda self: self.hidden_size)
+    encoder_ffn_dim = property(lambda self: self.intermediate_size)
+    encoder_layers = property(lambda self: self.num_hidden_layers)
+    encoder_attention_heads = property(lambda self: self.num_attention_heads)
+    max_position_embeddings = property(lambda self: self.max_source_positions)
+
+
+# encoder geometry of the public openai/whisper-* checkpoints: (d_model, heads, ffn, layers, mel bins); head_dim is 64 in all of them
+WHISPER_GEOMETRY = {"tiny": (384, 6, 1536, 4, 80), "base": (512, 8, 2048, 6, 80), "small": (768, 12, 3072, 12, 80),
+                    "medium": (1024, 16, 4096, 24, 80), "large-v3": (1280, 20, 5120, 32, 128), "large": (1280, 20, 5120, 32, 80)}
+
+
+def whisper_geometry(audio_model_id) -> dict:
+    """Shape fields for an ``openai/whisper-<size>[.en|-v2|-v3|-v3-turbo]`` id when no sub-config is passed ({} for an unknown name:
+    the class defaults, whisper-tiny, apply)."""
+    name = str(audio_model_id or "").lower()
+    for key in ("large-v3", "large", "medium", "small", "base", "tiny"):
+        if key in name:
+            h, nh, f, n, m = WHISPER_GEOMETRY[key]
+            return dict(d_model=h, encoder_attention_heads=nh, encoder_ffn_dim=f, encoder_layers=n, num_mel_bins=m)
+    return {}
+
+
+def is_whisper(audio_model_id, audio_config=None) -> bool:
+    """The reference's tower rule (tiny_audio/asr_modeling.py:203-237: ``"whisper" in config.audio_model_id.lower()``), extended to a
+    passed sub-config that says so itself (``model_type == "whisper"``)."""
+    if isinstance(audio_config, WhisperEncoderConfig):
+        return True
+    if isinstance(audio_config, EncoderConfig):
+        return False
+    if audio_config is not None:
+        return _get(audio_config, ["model_type"], None) == "whisper"
+    return "whisper" in str(audio_model_id or "").lower()
 
 
 class LMConfig:
@@ -112,7 +168,12 @@ class ASRConfig:
         self.freeze_projector = freeze_projector
         self.freeze_language_model = freeze_language_model
         self.max_new_tokens = max_new_tokens
-        self.audio_config = audio_config if isinstance(audio_config, EncoderConfig) else EncoderConfig(audio_config)
+        if isinstance(audio_config, (EncoderConfig, WhisperEncoderConfig)):
+            self.audio_config = audio_config
+        elif is_whisper(audio_model_id, audio_config):
+            self.audio_config = WhisperEncoderConfig(audio_config if audio_config is not None else whisper_geometry(audio_model_id))
+        else:
+            self.audio_config = EncoderConfig(audio_config)
         self.text_config = text_config if isinstance(text_config, LMConfig) else LMConfig(text_config)
         self.encoder_dim = encoder_dim or self.audio_config.hidden_size      # asr_modeling.py:259-265
         self.llm_dim = llm_dim or self.text_config.hidden_size               # asr_modeling.py:267-273

@@ -17,8 +17,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .asr_config import ASRConfig, compute_encoder_output_length
+from .asr_config import ASRConfig, WhisperEncoderConfig, compute_encoder_output_length
 from .encoder import GlmAsrEncoderMI355X
+from .whisper_encoder import WhisperEncoderMI355X
 from .language_model import FrozenLMLoss, Qwen3MI355X
 from .ops import F32
 from .projectors import PROJECTOR_CLASSES
@@ -137,7 +138,11 @@ class ASRModel(nn.Module):
         super().__init__()
         self.config = config
         self.device_ = torch.device(device)
-        self.audio_tower = GlmAsrEncoderMI355X(config.audio_config, device=device)        # asr_modeling.py:140
+        # asr_modeling.py:203-237: a Whisper encoder for every "whisper" audio_model_id, GLM-ASR's audio tower otherwise
+        if isinstance(config.audio_config, WhisperEncoderConfig):
+            self.audio_tower = WhisperEncoderMI355X(config.audio_config, device=device)
+        else:
+            self.audio_tower = GlmAsrEncoderMI355X(config.audio_config, device=device)
         self.language_model = Qwen3MI355X(config.text_config, device=device)              # :143
         self.audio_token_id = config.audio_token_id
         self.projector = self._create_projector(config).to(device=device, dtype=F32)      # :163
@@ -188,7 +193,12 @@ class ASRModel(nn.Module):
 
     def _create_feature_extractor(self, config):
         from .asr_processing import LogMelFeatureExtractor
-        return LogMelFeatureExtractor(int(getattr(config.audio_config, "num_mel_bins", 128)), self.device_)
+        fe = LogMelFeatureExtractor(int(getattr(config.audio_config, "num_mel_bins", 128)), self.device_)
+        if isinstance(config.audio_config, WhisperEncoderConfig):
+            # the reference disables the 30 s padding for GLM-ASR only (tiny_audio/asr_modeling.py:190-201): Whisper's encoder
+            # takes exactly 3000 frames
+            fe.padding = "max_length"
+        return fe
 
     def get_processor(self):
         """tiny_audio/asr_modeling.py:384-396: the processor that pairs with this model (its feature extractor, its tokenizer, its

@@ -63,7 +63,12 @@ class LogMelFeatureExtractor:
         self.feature_size = feature_size
         self.device = torch.device(device)
         self.hop_length, self.n_fft = HOP, N_FFT
-        self.padding = False                                     # tiny_audio/asr_modeling.py:199-200
+        # False: clips are padded to the longest of the batch (what the reference sets for GLM-ASR, tiny_audio/asr_modeling.py:199-200).
+        # "max_length": WhisperFeatureExtractor's own default, which the reference keeps for a Whisper tower -- every clip zero-padded
+        # (or cut) to n_samples = 30 s, 3000 frames, the mask's ones on the frames that start inside the clip
+        # (TF:models/whisper/feature_extraction_whisper.py:289-339).
+        self.padding = False
+        self.n_samples = 30 * self.sampling_rate                 # chunk_length 30 s
         dft, win = dft_tables()
         self._dft = torch.from_numpy(dft).to(self.device)
         self._win = torch.from_numpy(win).to(self.device)
@@ -98,10 +103,15 @@ class LogMelFeatureExtractor:
         if isinstance(raw_speech, np.ndarray) and raw_speech.ndim == 1:
             raw_speech = [raw_speech]
         lens = np.array([len(w) for w in raw_speech], dtype=np.int64)
-        Ls = int(lens.max())
+        if self.padding == "max_length":
+            # the log-mel (and its (max - 8) floor) is taken over the PADDED clip, as transformers does
+            lens = np.minimum(lens, self.n_samples)
+            Ls = self.n_samples
+        else:
+            Ls = int(lens.max())
         host = np.zeros((len(raw_speech), Ls), dtype=np.float32)
         for i, w in enumerate(raw_speech):
-            host[i, : len(w)] = np.asarray(w, dtype=np.float32)
+            host[i, : lens[i]] = np.asarray(w, dtype=np.float32)[: lens[i]]
         wav = torch.from_numpy(host).to(self.device, non_blocking=True)
         feats, mask = self.extract(wav, torch.from_numpy(lens).to(self.device))
         out = {"input_features": feats}

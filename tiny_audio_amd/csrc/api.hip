@@ -20,17 +20,38 @@ extern "C" int ta_version(void) { return 4; }
 
 // ============================================================================ encoder
 namespace {
+// What the two audio towers' composites share.  GLM-ASR: rotary positions in the q|k|v GEMM's epilogue of every layer (rope_*).
+// Whisper: a learned / sinusoidal table added once to the stem's output (pos_emb), no rotary; conv1's K rounded up to a K tile (k1).
+struct EncDesc {
+  int H, F, L, nh, NM, max_pos, k1;
+  float eps;
+  const void *conv1_w, *conv2_w;
+  const float *conv1_b, *conv2_b, *norm_w, *norm_b;
+  const float *rope_cos, *rope_sin, *rope_il, *pos_emb;
+  const ta_enc_layer* layers;
+  int res_f32;
+  bool whisper;
+};
+EncDesc enc_desc(const ta_encoder_weights* w) {
+  return EncDesc{w->hidden, w->ffn, w->n_layers, w->heads, w->n_mels, w->max_pos, 3 * w->n_mels, w->ln_eps, w->conv1_w, w->conv2_w,
+                 w->conv1_b, w->conv2_b, w->norm_w, w->norm_b, w->rope_cos, w->rope_sin, w->rope_il, nullptr, w->layers, w->res_f32, false};
+}
+EncDesc enc_desc(const ta_whisper_encoder_weights* w) {
+  return EncDesc{w->hidden, w->ffn, w->n_layers, w->heads, w->n_mels, w->max_pos, pad64(3 * w->n_mels), w->ln_eps, w->conv1_w, w->conv2_w,
+                 w->conv1_b, w->conv2_b, w->norm_w, w->norm_b, nullptr, nullptr, nullptr, w->pos_emb, w->layers, w->res_f32, true};
+}
 struct EncWs {
   bf16_t *x0, *x1, *xn, *qkv, *q, *k, *vt, *ao, *hf;
   float* xr;
   size_t bytes;
 };
-EncWs enc_carve(const ta_encoder_weights* w, int B, int T, void* base) {
-  const int H = w->hidden, S = (T - 1) / 2 + 1, Sp = pad64(S);
+EncWs enc_carve(const EncDesc& d, int B, int T, void* base) {
+  const int H = d.H, S = (T - 1) / 2 + 1, Sp = pad64(S);
   const long M = (long)B * S;
   Carver c(base);
   EncWs e;
-  e.x0 = c.take<bf16_t>((size_t)B * (T + 2) * w->n_mels);
+  // + the columns conv1's last row reads past its three taps when K was rounded up (they meet zero weights; zeroed per call)
+  e.x0 = c.take<bf16_t>((size_t)B * (T + 2) * d.NM + (size_t)(d.k1 - 3 * d.NM));
   e.x1 = c.take<bf16_t>((size_t)B * (T + 2) * H);
   e.xr = (float*)c.take<float>((size_t)M * H);      // residual stream (bf16 by default: the fp32 size is reserved)
   e.xn = c.take<bf16_t>((size_t)M * H);
@@ -39,67 +60,73 @@ EncWs enc_carve(const ta_encoder_weights* w, int B, int T, void* base) {
   e.k = c.take<bf16_t>((size_t)M * H);
   e.vt = c.take<bf16_t>((size_t)B * H * Sp);
   e.ao = c.take<bf16_t>((size_t)M * H);
-  e.hf = c.take<bf16_t>((size_t)M * w->ffn);
+  e.hf = c.take<bf16_t>((size_t)M * d.F);
   e.bytes = c.total();
   return e;
 }
-}  // namespace
 
-extern "C" long ta_encoder_workspace_bytes(const ta_encoder_weights* w, int B, int T) {
-  return (long)enc_carve(w, B, T, nullptr).bytes;
-}
-
-extern "C" int ta_encoder_forward(const ta_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
-                                  void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st) {
+int enc_forward(const EncDesc& w, const float* feats, int B, int T, const float* frame_keep, void* out_bf16, float* out_f32,
+                void* ws, long ws_bytes, hipStream_t st) {
   if (B <= 0 || T <= 0) return TA_OK;
-  const int H = w->hidden, F = w->ffn, NM = w->n_mels, nh = w->heads;
-  if (H % 128 || F % 128 || (3 * NM) % 64 || H / nh != 64 || (!out_bf16 && !out_f32)) return TA_ERR_ARG;
+  const int H = w.H, F = w.F, NM = w.NM, nh = w.nh, K1 = w.k1;
+  if (H % 128 || F % 128 || K1 % 64 || NM % 8 || H / nh != 64 || (!out_bf16 && !out_f32)) return TA_ERR_ARG;
   const int S = (T - 1) / 2 + 1, Sp = pad64(S);
-  if (S > w->max_pos) return TA_ERR_ARG;
+  if (S > w.max_pos) return TA_ERR_ARG;
+  // WhisperEncoder.forward raises unless the features span exactly 2 * max_source_positions frames (TF:models/whisper/modeling_whisper.py:612-616)
+  if (w.whisper && (T != 2 * w.max_pos || !w.pos_emb || H != nh * 64)) return TA_ERR_ARG;
   const int M = B * S;
   EncWs e = enc_carve(w, B, T, ws);
   if ((long)e.bytes > ws_bytes) return TA_ERR_ARG;
   // conv front end as two row-mapped GEMMs over zero-padded time-major buffers
   RC(ta_feats_to_time_major(feats, e.x0, B, NM, T, st));
+  if (K1 > 3 * NM && hipMemsetAsync(e.x0 + (size_t)B * (T + 2) * NM, 0, (size_t)(K1 - 3 * NM) * sizeof(bf16_t), st) != hipSuccess)
+    return TA_ERR_LAUNCH;
   RC(ta_zero_pad_rows(e.x1, B, T, H, st));
-  RC(ta_gemm_bf16_nt(e.x0, w->conv1_w, e.x1, B * T, H, 3 * NM, NM, T, (long)(T + 2) * NM, H, T, (long)(T + 2) * H, H,
-                     w->conv1_b, nullptr, 1, 1, 1, nullptr, st));
+  RC(ta_gemm_bf16_nt(e.x0, w.conv1_w, e.x1, B * T, H, K1, NM, T, (long)(T + 2) * NM, H, T, (long)(T + 2) * H, H,
+                     w.conv1_b, nullptr, 1, 1, 1, nullptr, st));
   // Residual stream: bf16, the dtype the reference's encoder runs in (model_dtype bfloat16: every residual add and
   // LayerNorm input is bf16 there).  It halves the bytes of the two residual GEMM epilogues and of the LayerNorm reads
-  // per layer -- HBM time that nothing overlaps.  ta_encoder_weights.res_f32 = 1 keeps an fp32 stream instead.
-  const bool res_f32 = w->res_f32 != 0;
+  // per layer -- HBM time that nothing overlaps.  res_f32 = 1 keeps an fp32 stream instead.
+  const bool res_f32 = w.res_f32 != 0;
   const int rb = res_f32 ? 0 : 1;
   auto ln = [&](const float* gw, const float* gb, void* yb, float* yf, const float* rowscale) -> int {
-    return rb ? ta_layernorm_bf16(e.xr, gw, gb, yb, yf, rowscale, M, H, w->ln_eps, st)
-              : ta_layernorm_f32(e.xr, gw, gb, yb, yf, rowscale, M, H, w->ln_eps, st);
+    return rb ? ta_layernorm_bf16(e.xr, gw, gb, yb, yf, rowscale, M, H, w.eps, st)
+              : ta_layernorm_f32(e.xr, gw, gb, yb, yf, rowscale, M, H, w.eps, st);
   };
   auto res_gemm = [&](const void* A, const void* Wm, int K, const float* bias) -> int {      // xr += A Wm^T + bias
     if (rb) { ta_gemm_opts o = opts_none(); o.residual_bf16 = e.xr; return gemm_opt(A, Wm, e.xr, M, H, K, bias, nullptr, 0, 1, o, st); }
     return gemm(A, Wm, e.xr, M, H, K, bias, e.xr, 0, 0, st);
   };
-  RC(ta_gemm_bf16_nt(e.x1, w->conv2_w, e.xr, M, H, 3 * H, 2L * H, S, (long)(T + 2) * H, H, 0, 0, 0, w->conv2_b, nullptr,
+  RC(ta_gemm_bf16_nt(e.x1, w.conv2_w, e.xr, M, H, 3 * H, 2L * H, S, (long)(T + 2) * H, H, 0, 0, 0, w.conv2_b, nullptr,
                      1, rb, 1, nullptr, st));
+  // Whisper: hidden = gelu(conv2) + embed_positions.weight, once (TF:models/whisper/modeling_whisper.py:618-624); row m takes table row m % S
+  if (w.whisper) RC(ta_pos_add(e.xr, res_f32 ? 1 : 0, w.pos_emb, B, S, H, st));
   const float scale = 0.125f;   // head_dim ** -0.5, head_dim = 64
   // Default: q | k | v from ONE GEMM + ta_attention_enc_fwd (needs the derived weight images, head_dim 64).  TA355_ENC_QKV_FUSED=0
   // keeps the three-kernel path (q|k|v GEMM + ta_enc_qkv_post + ta_attention_fwd); read per call: the tests compare both.
   // (Rounds 1-2 had a third form -- rope in the q|k epilogue + V^T = Wv xn^T as a second GEMM; rounds 1-3 a folded-LayerNorm form:
-  // both removed in round 5)
+  // both removed in round 5)  The Whisper tower has the one-GEMM form only (its other form would need rotary tables).
   const char* fz = getenv("TA355_ENC_QKV_FUSED");
-  const bool fa = !(fz && *fz == '0') && w->rope_il && (H / nh) == 64;
-  for (int l = 0; l < w->n_layers; ++l) {
-    const ta_enc_layer& L = w->layers[l];
+  const bool fa = w.whisper || (!(fz && *fz == '0') && w.rope_il && (H / nh) == 64);
+  for (int l = 0; l < w.L; ++l) {
+    const ta_enc_layer& L = w.layers[l];
+    if (w.whisper && !(L.wqkv_fa && L.bqkv_fa)) return TA_ERR_ARG;
     RC(ln(L.ln1_w, L.ln1_b, e.xn, nullptr, nullptr));
     if (fa && L.wqkv_fa && L.bqkv_fa) {
       // Round 3: q | k | v out of ONE GEMM as a token-major [M, 3H] buffer (rope on the q | k columns, q pre-scaled by
       // head_dim^-0.5 log2 e through the weight image), read in place by the DMA-staged base-2 attention kernel
       // (csrc/attention_enc.hip): no V^T GEMM, no transposed image, any M.
-      ta_gemm_opts o = opts_none(); o.rope_tab = w->rope_il; o.rope_rows = S; o.rope_cols = 2 * H;
-      RC(gemm_opt(e.xn, L.wqkv_fa, e.qkv, M, 3 * H, H, L.bqkv_fa, nullptr, 2, 1, o, st));
+      if (w.whisper) {
+        RC(gemm(e.xn, L.wqkv_fa, e.qkv, M, 3 * H, H, L.bqkv_fa, nullptr, 0, 1, st));
+      } else {
+        ta_gemm_opts o = opts_none(); o.rope_tab = w.rope_il; o.rope_rows = S; o.rope_cols = 2 * H;
+        RC(gemm_opt(e.xn, L.wqkv_fa, e.qkv, M, 3 * H, H, L.bqkv_fa, nullptr, 2, 1, o, st));
+      }
       RC(ta_attention_enc_fwd(e.qkv, e.ao, B, nh, S, st));
       RC(res_gemm(e.ao, L.wo, H, L.bo));
     } else {
       RC(gemm(e.xn, L.wqkv, e.qkv, M, 3 * H, H, L.bqkv, nullptr, 0, 1, st));
-      RC(ta_enc_qkv_post(e.qkv, w->rope_cos, w->rope_sin, e.q, e.k, e.vt, B, nh, S, Sp, st));
+      RC(ta_enc_qkv_post(e.qkv, w.rope_cos, w.rope_sin, e.q, e.k, e.vt, B, nh, S, Sp, st));
       RC(ta_attention_fwd(e.q, e.k, e.vt, e.ao, nullptr, nullptr, B, nh, nh, S, Sp, 64, 0, scale, st));
       RC(res_gemm(e.ao, L.wo, H, L.bo));
     }
@@ -107,8 +134,24 @@ extern "C" int ta_encoder_forward(const ta_encoder_weights* w, const float* feat
     RC(gemm(e.xn, L.w1, e.hf, M, F, H, L.b1, nullptr, 1, 1, st));
     RC(res_gemm(e.hf, L.w2, F, L.b2));
   }
-  RC(ln(w->norm_w, w->norm_b, out_bf16, out_f32, frame_keep));
+  RC(ln(w.norm_w, w.norm_b, out_bf16, out_f32, frame_keep));
   return TA_OK;
+}
+}  // namespace
+
+extern "C" long ta_encoder_workspace_bytes(const ta_encoder_weights* w, int B, int T) {
+  return (long)enc_carve(enc_desc(w), B, T, nullptr).bytes;
+}
+extern "C" int ta_encoder_forward(const ta_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
+                                  void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st) {
+  return enc_forward(enc_desc(w), feats, B, T, frame_keep, out_bf16, out_f32, ws, ws_bytes, st);
+}
+extern "C" long ta_whisper_encoder_workspace_bytes(const ta_whisper_encoder_weights* w, int B, int T) {
+  return (long)enc_carve(enc_desc(w), B, T, nullptr).bytes;
+}
+extern "C" int ta_whisper_encoder_forward(const ta_whisper_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
+                                          void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st) {
+  return enc_forward(enc_desc(w), feats, B, T, frame_keep, out_bf16, out_f32, ws, ws_bytes, st);
 }
 
 // ============================================================================ MLP projector

@@ -147,6 +147,40 @@ __global__ void zero_pad_rows_kernel(bf16_t* __restrict__ buf, int T, int C) {
   }
 }
 
+// ---------------------------------------------------------------------------- Whisper position table
+// x [B*S, H] (bf16 or f32 storage of the encoder's residual stream) += pos f32 [>= S, H], row m of the stream taking table row m % S
+// (WhisperEncoder: hidden = gelu(conv2) + embed_positions.weight, TF:models/whisper/modeling_whisper.py:622-624).  One read and one write of the stream,
+// 16 bytes per lane on the stream side; the table (S * H * 4 bytes, 7.7 MB at large-v3) stays in L2 / MALL across the B clips.
+template <bool F32>
+__global__ __launch_bounds__(256) void pos_add_kernel(void* __restrict__ xv, const float* __restrict__ pos, long n_chunks, long per_clip) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_chunks; i += (long)gridDim.x * blockDim.x) {
+    const long j = i % per_clip;                       // chunk inside the clip = chunk inside the table
+    if constexpr (F32) {
+      float4 v = ((const float4*)xv)[i];
+      const float4 p = ((const float4*)pos)[j];
+      v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+      ((float4*)xv)[i] = v;
+    } else {
+      const uint4 v = ((const uint4*)xv)[i];
+      const float4 p0 = ((const float4*)pos)[2 * j], p1 = ((const float4*)pos)[2 * j + 1];
+      uint4 o;
+      o.x = pack2bf(bf2f(v.x & 0xffff) + p0.x, bf2f(v.x >> 16) + p0.y);
+      o.y = pack2bf(bf2f(v.y & 0xffff) + p0.z, bf2f(v.y >> 16) + p0.w);
+      o.z = pack2bf(bf2f(v.z & 0xffff) + p1.x, bf2f(v.z >> 16) + p1.y);
+      o.w = pack2bf(bf2f(v.w & 0xffff) + p1.z, bf2f(v.w >> 16) + p1.w);
+      ((uint4*)xv)[i] = o;
+    }
+  }
+}
+extern "C" int ta_pos_add(void* x, int x_f32, const float* pos, int B, int S, int H, hipStream_t st) {
+  if (B <= 0 || S <= 0) return TA_OK;
+  if (!x || !pos || H <= 0 || (H % 8)) return TA_ERR_ARG;
+  const long per_clip = (long)S * H / (x_f32 ? 4 : 8), n = per_clip * B;
+  if (x_f32) TA_LAUNCH((pos_add_kernel<true>), dim3(ew_blocks(n)), dim3(256), 0, st, x, pos, n, per_clip);
+  else TA_LAUNCH((pos_add_kernel<false>), dim3(ew_blocks(n)), dim3(256), 0, st, x, pos, n, per_clip);
+  TA_CHECK_LAUNCH(); return TA_OK;
+}
+
 // ---------------------------------------------------------------------------- <audio> placeholder bookkeeping
 // tiny_audio/asr_modeling.py:27-44,511-515: the r-th <audio> position (row-major over [B,L]) receives packed row r,
 // packed = first counts[i] projector rows of sample i (zero rows when counts[i] > N).

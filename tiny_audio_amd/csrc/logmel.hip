@@ -95,7 +95,8 @@ __device__ __forceinline__ void fft25(cpx* y) {
 // (Re / Im x k2 < 16 / k2 >= 16) x 13 k-steps per pair; Z lands in the scratch in the interleaved [k][re, im] form the combine reads.
 // Per frame: 21 + 26 MFMAs of 32 cycles on the CU's four matrix cores (~310 cycles) against ~1 150 cycles of partially filled VALU
 // waves; the mel stage and everything around it are unchanged.
-template <int LFT, int LF_G, bool MFMA = false>
+// MEL_ITEMS: the mel stage's thread mapping for an n_mels that does not divide 256 (Whisper's 80 bins, see the mel stage below).
+template <int LFT, int LF_G, bool MFMA = false, bool MEL_ITEMS = false>
 __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict__ wav, int Ls, const float* __restrict__ dft,
                                                          const float* __restrict__ window, const float* __restrict__ melfb,
                                                          int n_mels, float* __restrict__ out, float* __restrict__ wg_rec, int T,
@@ -338,6 +339,29 @@ __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict
   // ---- mel + log10: thread = (mel bin m, group of frames), every filter over its own bins only
   float* melbuf = span;                                           // [n_mels][LF_MELS]
   float lmax = -INFINITY;
+  if constexpr (MEL_ITEMS) {
+    // n_mels = 80 (every Whisper checkpoint below large-v3): 256 / n_mels is not whole, so the work is cut into items of (filter, 16
+    // consecutive frames) -- 80 x LFT / 16 = 320 of them at LFT = 64 -- dealt to the threads round-robin: two passes, the second on
+    // one wave.  Per output the same fmaf chain over the filter's own bins as the mapping below.
+    for (int item = tid; item < n_mels * (LFT / 16); item += 256) {
+      const int m = item % n_mels, f0 = (item / n_mels) * 16;
+      const int klo = mrange[2 * m], khi = mrange[2 * m + 1];
+      float am[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) am[q] = 0.f;
+      for (int kk = klo; kk < khi; ++kk) {
+        const float wgt = melfb[kk * n_mels + m];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) am[q] = fmaf(wgt, pw[(f0 + q) * LF_PWS + kk], am[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float v = log10f(fmaxf(am[q], 1e-10f));
+        melbuf[m * LF_MELS + f0 + q] = v;
+        if (t0 + f0 + q < T) lmax = fmaxf(lmax, v);
+      }
+    }
+  } else {
   const int fgroups = 256 / n_mels;
   const int m = tid % n_mels, fg = tid / n_mels, nf = LFT / fgroups;
   const int klo = mrange[2 * m], khi = mrange[2 * m + 1];
@@ -357,6 +381,7 @@ __global__ __launch_bounds__(256) void logmel_fft_kernel(const float* __restrict
       melbuf[m * LF_MELS + f0 + q] = v;
       if (t0 + f0 + q < T) lmax = fmaxf(lmax, v);
     }
+  }
   }
   lmax = wave_max(lmax);
   float* wred = (float*)(mrange + 2 * n_mels) + 1;                // [4] behind the mel ranges and the rendezvous float (sized by the host)
@@ -458,21 +483,29 @@ extern "C" int ta_logmel_f32(const float* wav, const long* lens, int B, int Ls, 
                              hipStream_t st) {
   if (B <= 0) return TA_OK;
   const int T = Ls / HOP;
-  if (T <= 0 || Ls <= NFFT / 2 || (n_mels != 64 && n_mels != 128 && n_mels != 256) || !scratch || !mel_ranges) return TA_ERR_ARG;
+  if (T <= 0 || Ls <= NFFT / 2 || (n_mels != 64 && n_mels != 80 && n_mels != 128 && n_mels != 256) || !scratch || !mel_ranges) return TA_ERR_ARG;
   const LogmelGeom g = logmel_geom(B, Ls, n_mels);
   {
-    auto lds_of = [&](int lft, int gq) { return (size_t)((lft - 1) * HOP + NFFT + 4 * gq * NFFT * 2 + lft * LF_PWS + 3 * NFFT) * 4 + (size_t)n_mels * 2 * 4 + 32; };
+    auto lds_nm = [](int lft, int gq, int nm) { return (size_t)((lft - 1) * HOP + NFFT + 4 * gq * NFFT * 2 + lft * LF_PWS + 3 * NFFT) * 4 + (size_t)nm * 2 * 4 + 32; };
+    auto lds_of = [&](int lft, int gq) { return lds_nm(lft, gq, n_mels); };
     static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)logmel_fft_kernel<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(64, 4));
-      (void)hipFuncSetAttribute((const void*)logmel_fft_kernel<32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(32, 2));
+    if (!attr) {   // (the limit is raised once per process, for whichever n_mels calls first: the table of a later, larger n_mels must fit too)
+      (void)hipFuncSetAttribute((const void*)logmel_fft_kernel<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nm(64, 4, 256));
+      (void)hipFuncSetAttribute((const void*)logmel_fft_kernel<32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_nm(32, 2, 256));
       attr = true;
+    }
+    static bool attr80 = false;
+    if (n_mels == 80 && !attr80) {
+      (void)hipFuncSetAttribute((const void*)logmel_fft_kernel<64, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_of(64, 4));
+      attr80 = true;
     }
     // persistent workgroups over the tiles of all clips (round 4).  Measured and removed in round 5: one workgroup per tile (rounds 2-3:
     // 68 us against 42), a single-pass form whose workgroups rendezvous per clip (113.7 us against 80.9, profiles/r03_f_*), the
     // sub-transforms on the f32 matrix cores (76.4 against 68.2, profiles/r04_za_*; experiment builds only).
     const dim3 grid(g.grid);
-    if (g.wide)
+    if (n_mels == 80)   // the wide tile with the item-mapped mel stage; melbuf [80][65] fits the span it reuses, LDS as lds_of(64, 4)
+      TA_LAUNCH((logmel_fft_kernel<64, 4, false, true>), grid, dim3(256), lds_of(64, 4), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);
+    else if (g.wide)
       TA_LAUNCH((logmel_fft_kernel<64, 4>), grid, dim3(256), lds_of(64, 4), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);
     else
       TA_LAUNCH((logmel_fft_kernel<32, 2>), grid, dim3(256), lds_of(32, 2), st, wav, Ls, dft, window, melfb, n_mels, feats, scratch, T, mel_ranges, g.nseg, lens, mask, g.nblk, g.ntiles);

@@ -61,6 +61,17 @@ def encoder_state_dict(path: str) -> Dict[str, torch.Tensor]:
     return out
 
 
+def whisper_encoder_state_dict(path: str) -> Dict[str, torch.Tensor]:
+    """``WhisperEncoder`` state dict (``conv1.weight``, ``embed_positions.weight``, ``layers.N.self_attn.q_proj.weight`` ...) from a
+    local ``openai/whisper-*`` snapshot: the tensors under ``model.encoder.`` (``WhisperForConditionalGeneration``) or ``encoder.``
+    (``WhisperModel``); the reference keeps only that sub-module (tiny_audio/asr_modeling.py:203-237)."""
+    from .whisper_encoder import strip_prefix
+    sd = strip_prefix(read_tensors(path, lambda k: k.startswith(("model.encoder.", "encoder."))))
+    if "embed_positions.weight" not in sd or "conv1.weight" not in sd:
+        raise KeyError(f"{path}: no encoder.conv1.weight / encoder.embed_positions.weight -- not a Whisper checkpoint?")
+    return sd
+
+
 def lm_state_dict(path: str) -> Dict[str, torch.Tensor]:
     """Qwen3ForCausalLM state dict (``model.embed_tokens.weight`` ... ; a tied ``lm_head.weight`` is dropped).  The embedding
     keeps the checkpoint's row count; ``Qwen3MI355X.load_state_dict_hf`` cuts it to the tokenizer's vocabulary."""

@@ -5,6 +5,7 @@ reference has no FFI; its seams are nn.Module boundaries,
 
     ta355::logmel              WhisperFeatureExtractor.__call__           scripts/train.py:327-333
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
+    ta355::whisper_encoder_forward  the same seam with a Whisper tower    tiny_audio/asr_modeling.py:203-237
     ta355::mlp_projector       MLPAudioProjector.forward   (+ autograd)   tiny_audio/projectors.py:57-71
     ta355::moe_projector       MoEAudioProjector.forward   (+ autograd)   tiny_audio/projectors.py:257-347
     ta355::lm_forward_loss     embed + masked_scatter + Qwen3ForCausalLM(labels=...)  (+ autograd: d audio rows, LoRA
@@ -101,6 +102,20 @@ def encoder_forward(input_features: Tensor, frame_keep: Optional[Tensor], handle
 
 
 @encoder_forward.register_fake
+def _(input_features, frame_keep, handle, return_f32):
+    enc = module_of(handle)
+    B, _, T = input_features.shape
+    return input_features.new_empty((B, enc.output_length(T), enc.config.hidden_size), dtype=F32 if return_f32 else BF16)
+
+
+@torch.library.custom_op("ta355::whisper_encoder_forward", mutates_args=())
+def whisper_encoder_forward(input_features: Tensor, frame_keep: Optional[Tensor], handle: int, return_f32: bool) -> Tensor:
+    """Whisper tower: f32 [B, n_mels, 2 * max_source_positions] -> last_hidden_state [B, max_source_positions, H] (bf16, or f32 on
+    request); ``frame_keep`` as in ``encoder_forward``.  Replaces ``WhisperEncoder.forward`` (tiny_audio/asr_modeling.py:203-237)."""
+    return module_of(handle)._forward_impl(input_features, frame_keep, return_f32)
+
+
+@whisper_encoder_forward.register_fake
 def _(input_features, frame_keep, handle, return_f32):
     enc = module_of(handle)
     B, _, T = input_features.shape
@@ -480,4 +495,4 @@ def _lm_drop_bwd(ctx, g_loss, _g_nll, _g_logits, _g_tape, _g_ws):
 lm_forward_loss_drop.register_autograd(_lm_drop_bwd, setup_context=_lm_drop_setup)
 
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
-             "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop")
+             "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward")
