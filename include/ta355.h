@@ -209,14 +209,15 @@ int ta_moe_router_aux_grads(const ta_moe_weights* w, const void* x_bf16, int B, 
                             int training, const void* tape, float* d_norm_w_aux, float* d_router_w_aux, void* ws, long ws_bytes,
                             hipStream_t st);
 
-/* ---- frozen Qwen3 LM + shifted CE: replaces model.language_model(inputs_embeds=, attention_mask=, labels=)
+/* ---- frozen causal LM (Qwen3; SmolLM3 / Llama with head_dim 128) + shifted CE: replaces model.language_model(inputs_embeds=, attention_mask=, labels=)
  *      together with the embed/masked_scatter glue of ASRModel.forward
  *      (tiny_audio/asr_modeling.py:497-526; TF:models/qwen3/modeling_qwen3.py:367-508; TF:loss/loss_utils.py:33-71)
  *      and its activation-gradient backward (encoder + LM frozen: dX only). */
 typedef struct {
   const float* ln_in_w;             /* [D] */
   const void *wqkv, *wqkv_t;        /* bf16 [NQKV, D], [D, NQKV]; rows = q | k | v */
-  const float *qn_w, *kn_w;         /* [head_dim] */
+  const float *qn_w, *kn_w;         /* [head_dim] q_norm / k_norm (Qwen3), or BOTH NULL: a decoder without q/k-norm (SmolLM3, Llama:
+                                       TF:models/smollm3/modeling_smollm3.py:174-250) -- q and k go to RoPE unscaled.  One set, one not: TA_ERR_ARG */
   const void *wo, *wo_t;            /* bf16 [D, Hq*hd], [Hq*hd, D] */
   const float* ln_post_w;           /* [D] */
   const void *wgu, *wgu_t;          /* bf16 [2F, D] rows = gate | up, [D, 2F] */
@@ -253,6 +254,12 @@ typedef struct {
   int res_f32;                      /* storage of the forward residual stream and of its rows in the tape: 0 = bf16, 1 = fp32 */
   int dx_f32;                       /* storage of the backward d(x) stream: 0 = follows res_f32, 1 = fp32 even over a bf16 forward
                                        stream (rounds 1-3) */
+  unsigned long long nope_layers;   /* bit l set = decoder layer l applies NO rotary embedding ("NoPE": SmolLM3's no_rope_layers[l] == 0,
+                                       TF:models/smollm3/configuration_smollm3.py; use_rope at TF:models/smollm3/modeling_smollm3.py:174-250):
+                                       q and k skip the rotation and its table loads in training, prefill and both decode steps, and the
+                                       K rows of the cache are the unrotated ones.  0 = every layer rotates (Qwen3, Llama).  A set bit
+                                       needs n_layers <= 64.  Appended in ABI 4: handles are ZERO-INITIALISED by the caller (ctypes
+                                       structures and `= {}` are), so a caller that never names the field runs Qwen3's arithmetic. */
 } ta_lm_weights;
 
 /* Gradients of the LM's own weights (full decoder fine-tuning).  All f32, ACCUMULATED (+=) into the caller's buffers, which
@@ -530,6 +537,9 @@ int ta_attention_fwd_ex(const void* Q, const void* K, const void* VT, void* O, f
  * (token, head)).  V may be NULL (round 6): V is neither normalised nor rotated, so ta_attention_bwd_qkv can read it in place from
  * qkv0 and the head-major copy is only needed by callers that use it themselves (the KV cache of ta_lm_prefill, ta_attention_bwd).
  * tiny_audio path: TF:models/qwen3/modeling_qwen3.py:211-280 forward. */
+/* qn_w == kn_w == NULL: no q/k-norm (rq / rk are then neither written nor needed: they may be NULL); cosT == sinT == NULL: no rotary
+ * embedding (a NoPE layer).  The two switches are independent; each combination is its own kernel instantiation.  The same convention
+ * holds for ta_attention_bwd_qkv, ta_lm_qkv_post_fwd and ta_lm_qkv_post_bwd; one pointer of a pair NULL and the other not is TA_ERR_ARG. */
 int ta_attention_fwd_qkv(const void* qkv0, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
                          const int* pos, void* Q, void* K, void* V, float* rq, float* rk, void* O, float* LSE,
                          const int* kmask, int B, int Hq, int Hkv, int L, float scale, float eps, hipStream_t st);

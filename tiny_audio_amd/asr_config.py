@@ -2,7 +2,7 @@
 
 Mirrors ``tiny_audio/asr_config.py`` (field names, defaults, the conv length formula at :9-19) without
 depending on ``transformers``: sub-configs are plain objects carrying the shape fields the kernels need.
-An HF ``GlmAsrEncoderConfig`` / ``WhisperConfig`` / ``Qwen3Config`` (or a dict) can be passed wherever a sub-config is expected.
+An HF ``GlmAsrEncoderConfig`` / ``WhisperConfig`` / ``Qwen3Config`` / ``SmolLM3Config`` / ``LlamaConfig`` (or a dict) can be passed wherever a sub-config is expected.
 """
 from __future__ import annotations
 
@@ -107,24 +107,81 @@ def is_whisper(audio_model_id, audio_config=None) -> bool:
     return "whisper" in str(audio_model_id or "").lower()
 
 
+# what each supported decoder family fixes: (q/k-norm, defaults vocab / hidden / ffn / layers / heads / kv heads / rope theta / max positions)
+LM_FAMILIES = {"qwen3": (True, (151670, 1024, 3072, 28, 16, 8, 1e6, 4096)),            # Qwen3-0.6B (SURVEY.md section 8 preamble)
+               "smollm3": (False, (128256, 2048, 11008, 36, 16, 4, 2e6, 32768)),        # SmolLM3Config() = SmolLM3-3B
+               "llama": (False, (128256, 2048, 8192, 16, 16, 4, 5e5, 4096))}
+MAX_LM_LAYERS = 64      # csrc/api.hip; also the width of ta_lm_weights.nope_layers
+
+
+def _has(src, name):
+    """True when ``src`` (dict or object) carries ``name`` and it is truthy."""
+    return bool(_get(src, [name], False))
+
+
 class LMConfig:
-    """Qwen3Config fields; defaults = Qwen3-0.6B (SURVEY.md section 8 preamble)."""
+    """The decoder's shape fields, from a Qwen3Config / SmolLM3Config / LlamaConfig (or a dict, or keyword arguments); defaults =
+    Qwen3-0.6B (SURVEY.md section 8 preamble).  ``model_type`` picks the family:
+
+    * ``qwen3``: per-head q_norm / k_norm before RoPE (``qk_norm``), every layer rotates;
+    * ``smollm3``: no q/k-norm; ``no_rope_layers[i] == 0`` switches RoPE off in layer i ("NoPE"), from the source or derived from
+      ``no_rope_layer_interval`` as TF:models/smollm3/configuration_smollm3.py derives it; defaults = ``SmolLM3Config()``;
+    * ``llama``: no q/k-norm, every layer rotates.
+
+    What the kernels do not do is refused here with a ValueError that names the field."""
 
     def __init__(self, src=None, **kw):
         src = {**(src if isinstance(src, dict) else {}), **kw} if (isinstance(src, dict) or src is None) else src
-        self.vocab_size = int(_get(src, ["vocab_size", "vocab"], 151670))
-        self.hidden_size = int(_get(src, ["hidden_size", "hidden"], 1024))
-        self.intermediate_size = int(_get(src, ["intermediate_size", "ffn"], 3072))
-        self.num_hidden_layers = int(_get(src, ["num_hidden_layers", "layers"], 28))
-        self.num_attention_heads = int(_get(src, ["num_attention_heads", "heads"], 16))
-        self.num_key_value_heads = int(_get(src, ["num_key_value_heads", "kv_heads"], 8))
-        self.head_dim = int(_get(src, ["head_dim"], 128))
+        self.model_type = str(_get(src, ["model_type"], "qwen3"))
+        if self.model_type not in LM_FAMILIES:
+            raise ValueError(f"model_type {self.model_type!r}: the text tower is one of {sorted(LM_FAMILIES)}")
+        qk_norm, (V, D, F, NL, NH, NKV, theta, max_pos) = LM_FAMILIES[self.model_type]
+        self.vocab_size = int(_get(src, ["vocab_size", "vocab"], V))
+        self.hidden_size = int(_get(src, ["hidden_size", "hidden"], D))
+        self.intermediate_size = int(_get(src, ["intermediate_size", "ffn"], F))
+        self.num_hidden_layers = int(_get(src, ["num_hidden_layers", "layers"], NL))
+        self.num_attention_heads = int(_get(src, ["num_attention_heads", "heads"], NH))
+        self.num_key_value_heads = int(_get(src, ["num_key_value_heads", "kv_heads"], NKV))
+        # Qwen3Config always carries head_dim (128 in every published size); SmolLM3 / Llama configs derive it
+        self.head_dim = int(_get(src, ["head_dim"], 128 if self.model_type == "qwen3" else self.hidden_size // self.num_attention_heads))
         self.rms_norm_eps = float(_get(src, ["rms_norm_eps", "rms_eps"], 1e-6))
         rp = _get(src, ["rope_parameters"], None) or {}
-        self.rope_theta = float(_get(src, ["rope_theta"], None) or rp.get("rope_theta", 1e6))
-        self.max_position_embeddings = int(_get(src, ["max_position_embeddings"], 4096))
+        self.rope_theta = float(_get(src, ["rope_theta"], None) or rp.get("rope_theta", theta))
+        self.max_position_embeddings = int(_get(src, ["max_position_embeddings"], max_pos))
+        self.qk_norm = qk_norm
+        nrl = _get(src, ["no_rope_layers"], None) if self.model_type == "smollm3" else None
+        if nrl is None:
+            every = int(_get(src, ["no_rope_layer_interval"], 4)) if self.model_type == "smollm3" else 0
+            nrl = [int(every == 0 or (i + 1) % every != 0) for i in range(self.num_hidden_layers)]   # configuration_smollm3.py __post_init__
+        self.no_rope_layers = [int(bool(v)) for v in list(nrl)[: self.num_hidden_layers]]
+        if len(self.no_rope_layers) != self.num_hidden_layers:
+            raise ValueError(f"no_rope_layers has {len(self.no_rope_layers)} entries for num_hidden_layers = {self.num_hidden_layers}")
         if self.head_dim != 128:
-            raise ValueError("ta355 LM kernels are built for head_dim 128 (Qwen3)")
+            raise ValueError(f"head_dim = {self.head_dim}: ta355 LM kernels are built for head_dim 128 (Qwen3, SmolLM3-3B)")
+        if self.num_hidden_layers > MAX_LM_LAYERS:
+            raise ValueError(f"num_hidden_layers = {self.num_hidden_layers}: at most {MAX_LM_LAYERS} decoder layers")
+        if self.model_type != "qwen3":          # (a Qwen3 source is read exactly as before: its extra fields are not looked at)
+            for name in ("attention_bias", "mlp_bias", "use_sliding_window"):
+                if _has(src, name):
+                    raise ValueError(f"{name} = True is not built (the LM linears carry no bias, every layer attends to the whole prefix)")
+            rope_type = rp.get("rope_type", rp.get("type", "default")) if isinstance(rp, dict) else "default"
+            rs = _get(src, ["rope_scaling"], None)
+            if isinstance(rs, dict):
+                rope_type = rs.get("rope_type", rs.get("type", rope_type))
+            if rope_type not in (None, "default"):
+                raise ValueError(f"rope_type = {rope_type!r}: only the default rotary embedding is built (no llama3 / yarn scaling)")
+            if _get(src, ["tie_word_embeddings"], True) is False:
+                raise ValueError("tie_word_embeddings = False is not built (lm_head is the embedding matrix)")
+
+    @property
+    def nope_mask(self) -> int:
+        """ta_lm_weights.nope_layers: bit l set = layer l does not rotate."""
+        return sum(1 << i for i, v in enumerate(self.no_rope_layers) if not v)
+
+
+def smollm3_geometry(text_model_id) -> dict:
+    """Sub-config fields for a ``HuggingFaceTB/SmolLM3-*`` id when no ``text_config`` is passed ({} for any other name: Qwen3)."""
+    return {"model_type": "smollm3"} if "smollm3" in str(text_model_id or "").lower() else {}
 
 
 class ASRConfig:
@@ -174,7 +231,10 @@ class ASRConfig:
             self.audio_config = WhisperEncoderConfig(audio_config if audio_config is not None else whisper_geometry(audio_model_id))
         else:
             self.audio_config = EncoderConfig(audio_config)
-        self.text_config = text_config if isinstance(text_config, LMConfig) else LMConfig(text_config)
+        if isinstance(text_config, LMConfig):
+            self.text_config = text_config
+        else:       # an explicit sub-config decides by its own model_type; without one the model id does (the whisper_geometry pattern)
+            self.text_config = LMConfig(text_config if text_config is not None else smollm3_geometry(text_model_id))
         self.encoder_dim = encoder_dim or self.audio_config.hidden_size      # asr_modeling.py:259-265
         self.llm_dim = llm_dim or self.text_config.hidden_size               # asr_modeling.py:267-273
         self.audio_token_id = audio_token_id

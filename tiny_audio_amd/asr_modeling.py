@@ -20,7 +20,7 @@ from . import _lib, ops
 from .asr_config import ASRConfig, WhisperEncoderConfig, compute_encoder_output_length
 from .encoder import GlmAsrEncoderMI355X
 from .whisper_encoder import WhisperEncoderMI355X
-from .language_model import FrozenLMLoss, Qwen3MI355X
+from .language_model import NO_NORM_FULL_FT, FrozenLMLoss, Qwen3MI355X
 from .ops import F32
 from .projectors import PROJECTOR_CLASSES
 
@@ -143,6 +143,17 @@ class ASRModel(nn.Module):
             self.audio_tower = WhisperEncoderMI355X(config.audio_config, device=device)
         else:
             self.audio_tower = GlmAsrEncoderMI355X(config.audio_config, device=device)
+        tc = config.text_config
+        if tc.model_type != "qwen3":
+            # ASRConfig's token-id defaults are Qwen3's (151669 / 151643 / 151645): beyond a SmolLM3 / Llama vocabulary they would index
+            # the embedding table out of range
+            for name in ("audio_token_id", "pad_token_id", "eos_token_id"):
+                tid = getattr(config, name, None)
+                if tid is not None and int(tid) >= tc.vocab_size:
+                    raise ValueError(f"{name} = {tid} lies outside the {tc.model_type} vocabulary (vocab_size = {tc.vocab_size}): "
+                                     f"pass the tokenizer's own id")
+            if not getattr(config, "freeze_language_model", True):
+                raise NotImplementedError(NO_NORM_FULL_FT)
         self.language_model = Qwen3MI355X(config.text_config, device=device)              # :143
         self.audio_token_id = config.audio_token_id
         self.projector = self._create_projector(config).to(device=device, dtype=F32)      # :163

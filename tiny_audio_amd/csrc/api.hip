@@ -270,6 +270,10 @@ LmDims lm_dims(const ta_lm_weights* w, int B, int L) {
   return d;
 }
 // short causal sequences: QK-norm + RoPE + head split ride in the attention kernel's staging (ta_attention_fwd_qkv)
+// the RoPE tables of decoder layer l, or NULL for a NoPE layer (ta_lm_weights.nope_layers; SmolLM3's no_rope_layers[l] == 0,
+// TF:models/smollm3/modeling_smollm3.py:174-250): every attention entry point reads NULL tables as "do not rotate"
+inline const float* lm_rope_cos(const ta_lm_weights* w, int l) { return ((w->nope_layers >> l) & 1) ? nullptr : w->rope_cos; }
+inline const float* lm_rope_sin(const ta_lm_weights* w, int l) { return ((w->nope_layers >> l) & 1) ? nullptr : w->rope_sin; }
 inline bool lm_attn_fused(const LmDims& d, int L) { return d.hd == 128 && L <= 192 && (d.nq / d.nkv) * ((L + 31) / 32) <= 12; }
 LmTape lm_tape(const ta_lm_weights* w, int B, int L, int n_lab, void* base, LmLayerTape* store) {
   const LmDims d = lm_dims(w, B, L);
@@ -394,7 +398,8 @@ extern "C" long ta_lm_workspace_bytes(const ta_lm_weights* w, int B, int L, int 
   return (long)lm_ws(w, B, L, n_label_rows, nullptr).bytes;
 }
 
-// The decoder layers of Qwen3 (TF:models/qwen3/modeling_qwen3.py:283-324) over B*L token rows.  Training keeps one
+// The decoder layers of Qwen3 (TF:models/qwen3/modeling_qwen3.py:283-324) over B*L token rows -- or of a tower without q/k-norm (SmolLM3,
+// Llama: Lw.qn_w == Lw.kn_w == NULL) and with per-layer NoPE (w->nope_layers): same layer, two switches on the q / k post-processing.  Training keeps one
 // tape entry per layer; inference (`alias`) reuses entry 0 for every layer.  `ext`: adapter images held outside the
 // tape (generation keeps them across decode steps); kcache/vcache: see ta_lm_prefill.
 static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int L, const int* kmask, const int* pos,
@@ -486,10 +491,10 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
     if (fused_fwd)
       // the head-major copy of V exists for the KV cache (prefill) and for the un-fused backward (trainable q_norm / k_norm); the fused
       // backward reads V in place from qkv0, which the tape keeps anyway
-      RC(ta_attention_fwd_qkv(p.qkv0, Lw.qn_w, Lw.kn_w, w->rope_cos, w->rope_sin, pos, p.q, p.k, (kcache || w->train_base) ? p.v : nullptr, p.rq, p.rk, p.ao, p.lse, kmask,
+      RC(ta_attention_fwd_qkv(p.qkv0, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, p.q, p.k, (kcache || w->train_base) ? p.v : nullptr, p.rq, p.rk, p.ao, p.lse, kmask,
                               B, d.nq, d.nkv, L, scale, w->eps, st));
     else
-      RC(ta_lm_qkv_post_fwd(p.qkv0, Lw.qn_w, Lw.kn_w, w->rope_cos, w->rope_sin, pos, p.q, p.k, p.v, p.qt, p.kt, p.vt, p.rq,
+      RC(ta_lm_qkv_post_fwd(p.qkv0, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, p.q, p.k, p.v, p.qt, p.kt, p.vt, p.rq,
                             p.rk, B, d.nq, d.nkv, L, d.Lp, w->eps, st));
     if (kcache) {   // greedy decoding: keys / values of the prompt go to the cache [layer, B, Hkv, Lmax, hd]
       const size_t row = (size_t)L * d.hd * 2, pitch = (size_t)Lmax * d.hd * 2, rows = (size_t)B * d.nkv;
@@ -801,11 +806,11 @@ extern "C" int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, con
     RC(ta_attn_bwd_prep(s.dao, p.ao, s.delta, s.dot, B, d.nq, L, d.Lp, st));
     if (!(g && (g->dqn || g->dkn))) {
       RC(ta_attention_bwd_qkv(p.q, p.k, (w->train_base || !lm_attn_fused(d, L)) ? p.v : nullptr, s.dao, (long)d.nq * d.hd, p.lse, s.delta, kmask, p.qkv0, p.rq, p.rk, Lw.qn_w, Lw.kn_w,
-                              w->rope_cos, w->rope_sin, pos, s.dqkv, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
+                              lm_rope_cos(w, l), lm_rope_sin(w, l), pos, s.dqkv, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
     } else {
       RC(ta_attention_bwd(p.q, p.qt, p.k, p.kt, p.v, s.dao, (long)d.nq * d.hd, s.dot, p.lse, s.delta, kmask, s.dq, s.dk, s.dv,
                           B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
-      RC(ta_lm_qkv_post_bwd(s.dq, s.dk, s.dv, p.qkv0, p.rq, p.rk, Lw.qn_w, Lw.kn_w, w->rope_cos, w->rope_sin, pos, s.dqkv,
+      RC(ta_lm_qkv_post_bwd(s.dq, s.dk, s.dv, p.qkv0, p.rq, p.rk, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, s.dqkv,
                             g ? g->dqn : nullptr, g ? g->dkn : nullptr, B, d.nq, d.nkv, L, st));
     }
     if (g) RC(wgrad(s.dqkv, d.NQKV, p.xn_s, d.D, g->dwqkv));

@@ -576,7 +576,10 @@ constexpr int BWD_BUF = 2 * 64 * 128 * 2 + 512;      // one staging buffer of th
 // stamps of this kernel (scripts/attn_stamps.py, profiles/r06_d_attn_stamps_f32.txt) show it moving ~784 KB per workgroup through the
 // CU's vector-memory path at ~10 B per cycle for its whole life -- it is bound by that path, not by latency or MFMA -- and 196 KB of
 // it were query-side table rows.  Results are bit-identical (each row's arithmetic and its order over the keys do not change).
-template <int HD, int MAXT, int QSUB, int NW, bool PAIR = false>
+// NORM / ROPE (compile-time, chosen by the host per layer; <true, true> = Qwen3): NORM = false is a decoder without q_norm / k_norm
+// (SmolLM3, Llama; TF:models/smollm3/modeling_smollm3.py:174-250) -- q and k go to RoPE unscaled, rq / rk are not written; ROPE = false
+// is a NoPE layer (use_rope false there) -- no rotation and none of its table loads.  With neither, K stays as the DMA left it.
+template <int HD, int MAXT, int QSUB, int NW, bool PAIR = false, bool NORM = true, bool ROPE = true>
 __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t* __restrict__ qkv0, const float* __restrict__ qn_w,
                                                                const float* __restrict__ kn_w, const float* __restrict__ cosT,
                                                                const float* __restrict__ sinT, const int* __restrict__ pos,
@@ -618,10 +621,14 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
   }
   {
     const int c = tid & 15;                           // NT_ is a multiple of 16: a thread keeps its chunk column in every pass
-    const float4 wa = *(const float4*)(kn_w + c * 8), wb = *(const float4*)(kn_w + c * 8 + 4);
-    const float wk[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+    float wk[8];
+    if constexpr (NORM) {
+      const float4 wa = *(const float4*)(kn_w + c * 8), wb = *(const float4*)(kn_w + c * 8 + 4);
+      wk[0] = wa.x; wk[1] = wa.y; wk[2] = wa.z; wk[3] = wa.w; wk[4] = wb.x; wk[5] = wb.y; wk[6] = wb.z; wk[7] = wb.w;
+    }
     float4 cc[2][4];                                  // cos | sin rows of the current and the next pass
     auto rope_rows = [&](int i, float4* dst) {
+      if constexpr (!ROPE) return;
       const int ch = tid + i * NT_, t = ch / (64 * (HD / 8)), w = ch % (64 * (HD / 8));
       const int krow = t * KV_TILE + w / (HD / 8), gr = krow > L - 1 ? L - 1 : krow;
       const int pp = pos ? pos[(long)b * L + gr] : gr;
@@ -647,29 +654,43 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
         const uint4 kin = *(const uint4*)kp;
         const uint4 vin = *(const uint4*)(Vs + t * RowTile<HD>::BYTES + RowTile<HD>::off_tr(r, c));
         const uint32_t u[4] = {kin.x, kin.y, kin.z, kin.w};
-        float x[8], ss = 0.f;
+        uint4 kv = kin;
+        float rr = 1.f;
+        if constexpr (NORM || ROPE) {
+          float x[8];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { x[2 * k] = bf2f((bf16_t)(u[k] & 0xffff)); x[2 * k + 1] = bf2f((bf16_t)(u[k] >> 16)); }
+          for (int k = 0; k < 4; ++k) { x[2 * k] = bf2f((bf16_t)(u[k] & 0xffff)); x[2 * k + 1] = bf2f((bf16_t)(u[k] >> 16)); }
+          if constexpr (NORM) {
+            float ss = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) ss += x[e] * x[e];
-        ss = row_sum16(ss);
-        const float rr = rsqrtf(ss / (float)HD + eps);
-        const float4* q4 = cc[i & 1];
-        const float cs[8] = {q4[0].x, q4[0].y, q4[0].z, q4[0].w, q4[1].x, q4[1].y, q4[1].z, q4[1].w};
-        const float sn[8] = {q4[2].x, q4[2].y, q4[2].z, q4[2].w, q4[3].x, q4[3].y, q4[3].z, q4[3].w};
-        float y[8];
+            for (int e = 0; e < 8; ++e) ss += x[e] * x[e];
+            ss = row_sum16(ss);
+            rr = rsqrtf(ss / (float)HD + eps);
+          }
+          const float4* q4 = cc[i & 1];
+          float cs[8], sn[8];
+          if constexpr (ROPE) {
+            cs[0] = q4[0].x; cs[1] = q4[0].y; cs[2] = q4[0].z; cs[3] = q4[0].w; cs[4] = q4[1].x; cs[5] = q4[1].y; cs[6] = q4[1].z; cs[7] = q4[1].w;
+            sn[0] = q4[2].x; sn[1] = q4[2].y; sn[2] = q4[2].z; sn[3] = q4[2].w; sn[4] = q4[3].x; sn[5] = q4[3].y; sn[6] = q4[3].z; sn[7] = q4[3].w;
+          }
+          float y[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float n = x[e] * rr * wk[e];
-          const float np = row_xor8(n);               // the RoPE partner (dims d <-> d + 64) sits 8 lanes away
-          y[e] = c < 8 ? n * cs[e] - np * sn[e] : n * cs[e] + np * sn[e];
+          for (int e = 0; e < 8; ++e) {
+            const float n = NORM ? x[e] * rr * wk[e] : x[e];
+            if constexpr (ROPE) {
+              const float np = row_xor8(n);             // the RoPE partner (dims d <-> d + 64) sits 8 lanes away
+              y[e] = c < 8 ? n * cs[e] - np * sn[e] : n * cs[e] + np * sn[e];
+            } else {
+              y[e] = n;
+            }
+          }
+          kv = make_uint4(pack2bf(y[0], y[1]), pack2bf(y[2], y[3]), pack2bf(y[4], y[5]), pack2bf(y[6], y[7]));
+          *(uint4*)kp = kv;                           // in place: this thread is the only reader and writer of its chunk
         }
-        const uint4 kv = make_uint4(pack2bf(y[0], y[1]), pack2bf(y[2], y[3]), pack2bf(y[4], y[5]), pack2bf(y[6], y[7]));
-        *(uint4*)kp = kv;                             // in place: this thread is the only reader and writer of its chunk
         if (krow < L) {
           *(uint4*)(Ko + ((long)(b * Hkv + hk) * L + krow) * HD + c * 8) = kv;
           if (Vo) *(uint4*)(Vo + ((long)(b * Hkv + hk) * L + krow) * HD + c * 8) = vin;
-          if (c == 0) rk[tok * Hkv + hk] = rr;
+          if (NORM && c == 0) rk[tok * Hkv + hk] = rr;
         }
       }
     }
@@ -699,7 +720,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
     uint4 raw[HD / 32];
 #pragma unroll
     for (int ks = 0; ks < HD / 32; ++ks) raw[ks] = *(const uint4*)(src + ks * 32 + g * 8);
-    if (!PAIR || sub == 0) {
+    if (ROPE && (!PAIR || sub == 0)) {
       const int p = pos ? pos[tok] : qr;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
@@ -714,25 +735,34 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
       const uint32_t u[4] = {raw[ks].x, raw[ks].y, raw[ks].z, raw[ks].w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) { x[ks][2 * k] = bf2f((bf16_t)(u[k] & 0xffff)); x[ks][2 * k + 1] = bf2f((bf16_t)(u[k] >> 16)); }
+      if constexpr (NORM) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) ss += x[ks][e] * x[ks][e];
+        for (int e = 0; e < 8; ++e) ss += x[ks][e] * x[ks][e];
+      }
     }
-    ss = group_sum(ss);
-    const float rr = rsqrtf(ss / (float)HD + eps);
+    float rr = 1.f;
+    if constexpr (NORM) { ss = group_sum(ss); rr = rsqrtf(ss / (float)HD + eps); }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {                   // dims d = ks * 32 + g * 8 + e < 64 and their partners d + 64 (fragment ks + 2)
       const int d0 = ks * 32 + g * 8;
-      const float4 c0 = tc[ks][0], c1 = tc[ks][1], s0 = ts[ks][0], s1 = ts[ks][1];
-      const float4 wa = *(const float4*)(qn_w + d0), wb = *(const float4*)(qn_w + d0 + 4);
-      const float4 wc = *(const float4*)(qn_w + 64 + d0), wd = *(const float4*)(qn_w + 64 + d0 + 4);
-      const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-      const float w1[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w}, w2[8] = {wc.x, wc.y, wc.z, wc.w, wd.x, wd.y, wd.z, wd.w};
+      float cs[8], sn[8], w1[8], w2[8];
+      if constexpr (ROPE) {
+        const float4 c0 = tc[ks][0], c1 = tc[ks][1], s0 = ts[ks][0], s1 = ts[ks][1];
+        cs[0] = c0.x; cs[1] = c0.y; cs[2] = c0.z; cs[3] = c0.w; cs[4] = c1.x; cs[5] = c1.y; cs[6] = c1.z; cs[7] = c1.w;
+        sn[0] = s0.x; sn[1] = s0.y; sn[2] = s0.z; sn[3] = s0.w; sn[4] = s1.x; sn[5] = s1.y; sn[6] = s1.z; sn[7] = s1.w;
+      }
+      if constexpr (NORM) {
+        const float4 wa = *(const float4*)(qn_w + d0), wb = *(const float4*)(qn_w + d0 + 4);
+        const float4 wc = *(const float4*)(qn_w + 64 + d0), wd = *(const float4*)(qn_w + 64 + d0 + 4);
+        w1[0] = wa.x; w1[1] = wa.y; w1[2] = wa.z; w1[3] = wa.w; w1[4] = wb.x; w1[5] = wb.y; w1[6] = wb.z; w1[7] = wb.w;
+        w2[0] = wc.x; w2[1] = wc.y; w2[2] = wc.z; w2[3] = wc.w; w2[4] = wd.x; w2[5] = wd.y; w2[6] = wd.z; w2[7] = wd.w;
+      }
       float y1[8], y2[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float n1 = x[ks][e] * rr * w1[e], n2 = x[ks + 2][e] * rr * w2[e];
-        y1[e] = n1 * cs[e] - n2 * sn[e];
-        y2[e] = n2 * cs[e] + n1 * sn[e];
+        const float n1 = NORM ? x[ks][e] * rr * w1[e] : x[ks][e], n2 = NORM ? x[ks + 2][e] * rr * w2[e] : x[ks + 2][e];
+        y1[e] = ROPE ? n1 * cs[e] - n2 * sn[e] : n1;
+        y2[e] = ROPE ? n2 * cs[e] + n1 * sn[e] : n2;
       }
       union { bf16x8 v; uint4 u; } a, c;
       a.u = make_uint4(pack2bf(y1[0], y1[1]), pack2bf(y1[2], y1[3]), pack2bf(y1[4], y1[5]), pack2bf(y1[6], y1[7]));
@@ -744,7 +774,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
         *(uint4*)(qdst + 64 + d0) = c.u;
       }
     }
-    if (qrow < L && g == 0) rq[tok * Hq + h] = rr;
+    if (NORM && qrow < L && g == 0) rq[tok * Hq + h] = rr;
   }
   f32x4 o[QSUB][ND + 1];
 #pragma unroll
@@ -880,6 +910,9 @@ __device__ __forceinline__ void qkv_stage_f32(char* st, const f32x4* acc, int wa
     *(float4*)(st + (wave * 16 + l15) * QP_PITCH + (dt * 16 + g * 4) * 4) = make_float4(acc[dt][0], acc[dt][1], acc[dt][2], acc[dt][3]);
 }
 // sec 0 / 1: RoPE^T + RMSNorm backward of q / k head `head`; sec 2: v, copied through.  row0 = first sequence row of the tile.
+// NORM = false (no q_norm / k_norm: SmolLM3, Llama): d(q), d(k) = RoPE^T(dQ) -- no RMSNorm term, qkv0's q / k columns and rq / rk are
+// not read.  ROPE = false (a NoPE layer): no RoPE^T, no table loads.
+template <bool NORM, bool ROPE>
 __device__ __forceinline__ void qkv_post_bwd_tile(const char* st, const QkvPostBwd& F, int sec, int b, int row0, int L, int head,
                                                   int Hq, int Hkv, int tid) {
   constexpr int HD = 128;
@@ -887,7 +920,7 @@ __device__ __forceinline__ void qkv_post_bwd_tile(const char* st, const QkvPostB
   const int Hs = sec == 0 ? Hq : Hkv, j = tid & 7;
   const long coff = (long)(sec == 0 ? head : (sec == 1 ? Hq + head : Hq + Hkv + head)) * HD;
   float w1[8], w2[8];
-  if (sec < 2) {
+  if (NORM && sec < 2) {
     const float* nw = sec == 0 ? F.qn_w : F.kn_w;
     const float4 a = *(const float4*)(nw + 8 * j), b4 = *(const float4*)(nw + 8 * j + 4), c = *(const float4*)(nw + 64 + 8 * j), d = *(const float4*)(nw + 64 + 8 * j + 4);
     w1[0] = a.x; w1[1] = a.y; w1[2] = a.z; w1[3] = a.w; w1[4] = b4.x; w1[5] = b4.y; w1[6] = b4.z; w1[7] = b4.w;
@@ -904,32 +937,49 @@ __device__ __forceinline__ void qkv_post_bwd_tile(const char* st, const QkvPostB
     { const float4 a = *(const float4*)(sr + 8 * j), b4 = *(const float4*)(sr + 8 * j + 4), c = *(const float4*)(sr + 64 + 8 * j), d = *(const float4*)(sr + 64 + 8 * j + 4);
       d1[0] = a.x; d1[1] = a.y; d1[2] = a.z; d1[3] = a.w; d1[4] = b4.x; d1[5] = b4.y; d1[6] = b4.z; d1[7] = b4.w;
       d2[0] = c.x; d2[1] = c.y; d2[2] = c.z; d2[3] = c.w; d2[4] = d.x; d2[5] = d.y; d2[6] = d.z; d2[7] = d.w; }
-    if (sec < 2) {
-      const bf16_t* src = F.qkv0 + tok * ld + coff;
-      const uint4 xa = *(const uint4*)(src + 8 * j), xb = *(const uint4*)(src + 64 + 8 * j);
-      const uint32_t ua[4] = {xa.x, xa.y, xa.z, xa.w}, ub[4] = {xb.x, xb.y, xb.z, xb.w};
-      float x1[8], x2[8];
+    if ((NORM || ROPE) && sec < 2) {
+      float cs[8], sn[8];
+      if constexpr (NORM) {
+        const bf16_t* src = F.qkv0 + tok * ld + coff;
+        const uint4 xa = *(const uint4*)(src + 8 * j), xb = *(const uint4*)(src + 64 + 8 * j);
+        const uint32_t ua[4] = {xa.x, xa.y, xa.z, xa.w}, ub[4] = {xb.x, xb.y, xb.z, xb.w};
+        float x1[8], x2[8];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        x1[2 * k] = bf2f((bf16_t)(ua[k] & 0xffff)); x1[2 * k + 1] = bf2f((bf16_t)(ua[k] >> 16));
-        x2[2 * k] = bf2f((bf16_t)(ub[k] & 0xffff)); x2[2 * k + 1] = bf2f((bf16_t)(ub[k] >> 16));
+        for (int k = 0; k < 4; ++k) {
+          x1[2 * k] = bf2f((bf16_t)(ua[k] & 0xffff)); x1[2 * k + 1] = bf2f((bf16_t)(ua[k] >> 16));
+          x2[2 * k] = bf2f((bf16_t)(ub[k] & 0xffff)); x2[2 * k + 1] = bf2f((bf16_t)(ub[k] >> 16));
+        }
+        if constexpr (ROPE) {
+          const int p = F.pos ? F.pos[tok] : lc;
+          const float4 c0 = *(const float4*)(F.cosT + (long)p * 64 + 8 * j), c1 = *(const float4*)(F.cosT + (long)p * 64 + 8 * j + 4);
+          const float4 s0 = *(const float4*)(F.sinT + (long)p * 64 + 8 * j), s1 = *(const float4*)(F.sinT + (long)p * 64 + 8 * j + 4);
+          cs[0] = c0.x; cs[1] = c0.y; cs[2] = c0.z; cs[3] = c0.w; cs[4] = c1.x; cs[5] = c1.y; cs[6] = c1.z; cs[7] = c1.w;
+          sn[0] = s0.x; sn[1] = s0.y; sn[2] = s0.z; sn[3] = s0.w; sn[4] = s1.x; sn[5] = s1.y; sn[6] = s1.z; sn[7] = s1.w;
+        }
+        const float r = (sec == 0 ? F.rq : F.rk)[tok * Hs + head];
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dn1 = ROPE ? d1[e] * cs[e] + d2[e] * sn[e] : d1[e], dn2 = ROPE ? d2[e] * cs[e] - d1[e] * sn[e] : d2[e];     // RoPE^T
+          x1[e] *= r; x2[e] *= r;                                                               // x-hat
+          d1[e] = dn1 * w1[e]; d2[e] = dn2 * w2[e];
+          dot += d1[e] * x1[e] + d2[e] * x2[e];
+        }
+        const float md = oct_sum8(dot) / (float)HD;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { d1[e] = r * (d1[e] - x1[e] * md); d2[e] = r * (d2[e] - x2[e] * md); }
+      } else {                                            // RoPE^T alone
+        const int p = F.pos ? F.pos[tok] : lc;
+        const float4 c0 = *(const float4*)(F.cosT + (long)p * 64 + 8 * j), c1 = *(const float4*)(F.cosT + (long)p * 64 + 8 * j + 4);
+        const float4 s0 = *(const float4*)(F.sinT + (long)p * 64 + 8 * j), s1 = *(const float4*)(F.sinT + (long)p * 64 + 8 * j + 4);
+        cs[0] = c0.x; cs[1] = c0.y; cs[2] = c0.z; cs[3] = c0.w; cs[4] = c1.x; cs[5] = c1.y; cs[6] = c1.z; cs[7] = c1.w;
+        sn[0] = s0.x; sn[1] = s0.y; sn[2] = s0.z; sn[3] = s0.w; sn[4] = s1.x; sn[5] = s1.y; sn[6] = s1.z; sn[7] = s1.w;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dn1 = d1[e] * cs[e] + d2[e] * sn[e], dn2 = d2[e] * cs[e] - d1[e] * sn[e];
+          d1[e] = dn1; d2[e] = dn2;
+        }
       }
-      const int p = F.pos ? F.pos[tok] : lc;
-      const float4 c0 = *(const float4*)(F.cosT + (long)p * 64 + 8 * j), c1 = *(const float4*)(F.cosT + (long)p * 64 + 8 * j + 4);
-      const float4 s0 = *(const float4*)(F.sinT + (long)p * 64 + 8 * j), s1 = *(const float4*)(F.sinT + (long)p * 64 + 8 * j + 4);
-      const float cs[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, sn[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-      const float r = (sec == 0 ? F.rq : F.rk)[tok * Hs + head];
-      float dot = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float dn1 = d1[e] * cs[e] + d2[e] * sn[e], dn2 = d2[e] * cs[e] - d1[e] * sn[e];     // RoPE^T
-        x1[e] *= r; x2[e] *= r;                                                               // x-hat
-        d1[e] = dn1 * w1[e]; d2[e] = dn2 * w2[e];
-        dot += d1[e] * x1[e] + d2[e] * x2[e];
-      }
-      const float md = oct_sum8(dot) / (float)HD;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d1[e] = r * (d1[e] - x1[e] * md); d2[e] = r * (d2[e] - x2[e] * md); }
     }
     if (live) {
       bf16_t* dst = F.dqkv + ((long)b * L + l) * ld + coff;
@@ -942,7 +992,7 @@ __device__ __forceinline__ void qkv_post_bwd_tile(const char* st, const QkvPostB
 
 // ============================================================================ backward: dQ
 // grid (q tiles, Hq, B).  dQ^T[d,q] = sum_key K^T[d,key] dS^T[key,q],  dS = P o (dP - Delta) * scale
-template <int HD, bool CAUSAL>
+template <int HD, bool CAUSAL, bool NORM, bool ROPE>
 __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                  const bf16_t* __restrict__ V, const bf16_t* __restrict__ KT,
                                                  const bf16_t* __restrict__ dO, long dO_stride,
@@ -1044,7 +1094,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
     if constexpr (HD == 128) {
       qkv_stage_f32(smem, dq, wave, l15, g);                 // the last loop iteration ended with a barrier: the tiles are free
       __syncthreads();
-      qkv_post_bwd_tile(smem, F, 0, b, qt * 64, L, h, Hq, Hkv, tid);
+      qkv_post_bwd_tile<NORM, ROPE>(smem, F, 0, b, qt * 64, L, h, Hq, Hkv, tid);
     }
 #ifdef TA355_ATTN_STAMPS
     ATTN_STAMP(gridDim.x - 1 - blockIdx.x + 4096, 3, 0);
@@ -1067,7 +1117,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
 // ============================================================================ backward: dK, dV
 // grid (key tiles, Hkv, B); loops over the Hq/Hkv query heads of the group and over query tiles.
 //   dV^T[d,key] += dO^T[d,q] P[q,key]      dK^T[d,key] += Q^T[d,q] dS[q,key]
-template <int HD, bool CAUSAL>
+template <int HD, bool CAUSAL, bool NORM, bool ROPE>
 __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ QT,
                                                   const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                   const bf16_t* __restrict__ dO, long dO_stride,
@@ -1182,11 +1232,11 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
     if constexpr (HD == 128) {
       qkv_stage_f32(smem, dk, wave, l15, g);
       __syncthreads();
-      qkv_post_bwd_tile(smem, F, 1, b, kt_idx * 64, L, hk, Hq, Hkv, tid);
+      qkv_post_bwd_tile<NORM, ROPE>(smem, F, 1, b, kt_idx * 64, L, hk, Hq, Hkv, tid);
       __syncthreads();
       qkv_stage_f32(smem, dv, wave, l15, g);
       __syncthreads();
-      qkv_post_bwd_tile(smem, F, 2, b, kt_idx * 64, L, hk, Hq, Hkv, tid);
+      qkv_post_bwd_tile<NORM, ROPE>(smem, F, 2, b, kt_idx * 64, L, hk, Hq, Hkv, tid);
     }
 #ifdef TA355_ATTN_STAMPS
     ATTN_STAMP(blockIdx.x, 3, 0);
@@ -1212,7 +1262,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
 // One launch for both halves of the backward: blocks [0, n_dkv) run the dK / dV body, the rest the dQ body.  The two
 // are independent (both only read Q, K, V, dO), so a single grid lets the dQ workgroups fill the CUs while the longer
 // dK / dV ones drain, without a second stream or a kernel boundary in between.  The heavier dK / dV blocks go first.
-template <int HD, bool CAUSAL>
+template <int HD, bool CAUSAL, bool NORM = true, bool ROPE = true>      // NORM / ROPE: the fused epilogue's variant (qkv_post_bwd_tile)
 __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ QT,
                                                        const bf16_t* __restrict__ K, const bf16_t* __restrict__ KT,
                                                        const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO, long dO_stride,
@@ -1223,9 +1273,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restri
                                                        const QkvPostBwd F) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if ((int)blockIdx.x < n_dkv)
-    attn_bwd_dkv_body<HD, CAUSAL>(smem, blockIdx.x, Q, QT, K, V, dO, dO_stride, dOT, LSE, Delta, kmask, dK, dV, B, Hq, Hkv, L, Lp, scale, F);
+    attn_bwd_dkv_body<HD, CAUSAL, NORM, ROPE>(smem, blockIdx.x, Q, QT, K, V, dO, dO_stride, dOT, LSE, Delta, kmask, dK, dV, B, Hq, Hkv, L, Lp, scale, F);
   else
-    attn_bwd_dq_body<HD, CAUSAL>(smem, blockIdx.x - n_dkv, Q, K, V, KT, dO, dO_stride, LSE, Delta, kmask, dQ, B, Hq, Hkv, L, Lp, scale, F);
+    attn_bwd_dq_body<HD, CAUSAL, NORM, ROPE>(smem, blockIdx.x - n_dkv, Q, K, V, KT, dO, dO_stride, LSE, Delta, kmask, dQ, B, Hq, Hkv, L, Lp, scale, F);
 }
 
 
@@ -1289,10 +1339,16 @@ static int attention_bwd_launch(const void* Q, const void* K, const void* V, con
   constexpr int HD = 128;
   // K^T / Q^T / dO^T fragments are read transposed out of the row tiles; the fused epilogue re-uses the space for a [64][128] f32 image
   const size_t lds_kv = (2 * (size_t)BWD_BUF > 64 * (size_t)QP_PITCH) ? 2 * (size_t)BWD_BUF : 64 * (size_t)QP_PITCH;      // two staging buffers
+  // the fused epilogue's variant: with q/k-norm and RoPE (Qwen3) unless the caller passed NULL norm weights / NULL tables
+  const bool norm = !F.qkv0 || F.qn_w, rope = !F.qkv0 || F.cosT;
+  if (!causal && !(norm && rope)) return TA_ERR_ARG;               // the other variants exist for the causal (LM) form only
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
     attr_done = true;
   }
   const int n_dq = grouped_grid((Hq / Hkv) * ta_cdiv(L, 64), B * Hkv), n_dkv = grouped_grid(ta_cdiv(L, 64), B * Hkv);
@@ -1301,11 +1357,14 @@ static int attention_bwd_launch(const void* Q, const void* K, const void* V, con
   // removed in round 5: two launches -- +0.47 ms per step, r02; the dK/dV and dQ workgroups of one (clip, kv head) interleaved on
   // one XCD -- 45.42 vs 45.29 ms per step: the heavier blocks first balance the tail better than the shared L2 lines help.)
   const bf16_t* nul = nullptr;
-#define BWD(C_)                                                                                                                     \
-  TA_LAUNCH((attn_bwd_kernel<HD, C_>), grid, blk, lds_kv, st, (const bf16_t*)Q, nul, (const bf16_t*)K, nul, (const bf16_t*)V,       \
+#define BWD(...)                                                                                                                    \
+  TA_LAUNCH((attn_bwd_kernel<HD, __VA_ARGS__>), grid, blk, lds_kv, st, (const bf16_t*)Q, nul, (const bf16_t*)K, nul, (const bf16_t*)V, \
             (const bf16_t*)dO, dO_stride, nul, LSE, Delta, kmask, (bf16_t*)dQ, (bf16_t*)dK, (bf16_t*)dV, B, Hq, Hkv, L, Lp, scale, n_dkv, F)
-  if (causal) BWD(true);
-  else BWD(false);
+  if (!causal) BWD(false);
+  else if (norm && rope) BWD(true);
+  else if (norm) BWD(true, true, false);
+  else if (rope) BWD(true, false, true);
+  else BWD(true, false, false);
 #undef BWD
   TA_CHECK_LAUNCH();
   return TA_OK;
@@ -1318,23 +1377,33 @@ extern "C" int ta_attention_fwd_qkv(const void* qkv0, const float* qn_w, const f
                                     const int* pos, void* Q, void* K, void* V, float* rq, float* rk, void* O, float* LSE,
                                     const int* kmask, int B, int Hq, int Hkv, int L, float scale, float eps, hipStream_t st) {
   if (B <= 0 || L <= 0) return TA_OK;
-  if (!qkv0 || !Q || !K || !rq || !rk || !O || Hkv <= 0 || Hq % Hkv) return TA_ERR_ARG;     // V may be NULL: no head-major copy of V
+  if (!qkv0 || !Q || !K || !O || Hkv <= 0 || Hq % Hkv) return TA_ERR_ARG;     // V may be NULL: no head-major copy of V
+  if (!qn_w != !kn_w || !cosT != !sinT) return TA_ERR_ARG;      // both norm weights or neither (no q/k-norm); both tables or neither (NoPE)
+  const bool norm = qn_w != nullptr, rope = cosT != nullptr;
+  if (norm && (!rq || !rk)) return TA_ERR_ARG;
   const int grp = Hq / Hkv;
   if (L > 192 || grp * ((L + 31) / 32) > 12) return TA_ERR_ARG;
   constexpr int MAXT = 3, QS = 2, NW = 6;
   const size_t lds = 2 * MAXT * RowTile<128>::BYTES + MAXT * 64 * 4;
   static bool attr = false;
+#define FQ_ATTR(...) (void)hipFuncSetAttribute((const void*)attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    FQ_ATTR(false); FQ_ATTR(true);
+    FQ_ATTR(false, true, false); FQ_ATTR(true, true, false); FQ_ATTR(false, false, true); FQ_ATTR(true, false, true);
+    FQ_ATTR(false, false, false); FQ_ATTR(true, false, false);
     attr = true;
   }
-  if (grp == 2)     // Qwen3 (16 / 8): both heads of the group on the same 16 rows per wave (one fetch of the rows' cos / sin entries)
-    TA_LAUNCH((attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, true>), dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)qkv0, qn_w, kn_w, cosT, sinT,
-              pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps);
-  else
-    TA_LAUNCH((attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW>), dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)qkv0, qn_w, kn_w, cosT, sinT,
-              pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps);
+#undef FQ_ATTR
+#define FQ(...)                                                                                                                       \
+  TA_LAUNCH((attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, __VA_ARGS__>), dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)qkv0, qn_w, kn_w, \
+            cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps)
+  // groups of two (Qwen3 16 / 8): both heads of the group on the same 16 rows per wave (one fetch of the rows' cos / sin entries)
+  const bool pair = grp == 2;
+  if (norm && rope) { if (pair) FQ(true); else FQ(false); }
+  else if (norm) { if (pair) FQ(true, true, false); else FQ(false, true, false); }
+  else if (rope) { if (pair) FQ(true, false, true); else FQ(false, false, true); }
+  else { if (pair) FQ(true, false, false); else FQ(false, false, false); }
+#undef FQ
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
@@ -1355,7 +1424,7 @@ extern "C" int ta_attention_bwd_qkv(const void* Q, const void* K, const void* V,
                                     const float* qn_w, const float* kn_w, const float* cosT, const float* sinT, const int* pos,
                                     void* dqkv, int B, int Hq, int Hkv, int L, int Lp, int head_dim, int causal, float scale,
                                     hipStream_t st) {
-  if (!qkv0 || !dqkv || !rq || !rk || !qn_w || !kn_w || !cosT || !sinT) return TA_ERR_ARG;
+  if (!qkv0 || !dqkv || !qn_w != !kn_w || !cosT != !sinT || (qn_w && (!rq || !rk))) return TA_ERR_ARG;   // NULL norm weights: no q/k-norm; NULL tables: NoPE
   QkvPostBwd F = {(const bf16_t*)qkv0, rq, rk, qn_w, kn_w, cosT, sinT, pos, (bf16_t*)dqkv};
   return attention_bwd_launch(Q, K, V, dO, dO_stride, LSE, Delta, kmask, nullptr, nullptr, nullptr, B, Hq, Hkv, L, Lp, head_dim, causal,
                               scale, F, st);

@@ -294,7 +294,8 @@ __global__ __launch_bounds__(256) void dec_final_norm_kernel(const float* __rest
 // key (appended to the cache), wave GRP+1 copies the new value row (likewise) -- the arithmetic of lm_qkv_post_decode_kernel.  Then
 // 16 lanes share a key row (16 B each): scores of all GRP heads from ONE read of K, fp32 softmax, P V from one read of V.
 // LDS: q [GRP][128] f32 | new k, v [2][128] bf16-rounded f32 | scores [GRP][Lcap] | partial outputs [16][GRP][128].
-template <int GRP>
+// NORM / ROPE as lm_qkv_post_decode_kernel's (no q/k-norm: SmolLM3, Llama; a NoPE layer: no rotation, no table loads); <G, true, true> is Qwen3.
+template <int GRP, bool NORM = true, bool ROPE = true>
 __global__ __launch_bounds__(256) void dec_attn_kernel(const bf16_t* __restrict__ qkv0, const float* __restrict__ qn_w,
                                                        const float* __restrict__ kn_w, const float* __restrict__ cosT,
                                                        const float* __restrict__ sinT, const int* __restrict__ pos,
@@ -325,14 +326,21 @@ __global__ __launch_bounds__(256) void dec_attn_kernel(const bf16_t* __restrict_
     const int hh = sec == 0 ? hk * GRP + job : (sec == 1 ? Hq + hk : Hq + Hkv + hk);
     const bf16_t* src = qkv0 + (long)b * ld + (long)hh * HD;
     float y1 = bf2f(src[lane]), y2 = bf2f(src[lane + 64]);
-    if (sec < 2) {
-      const float* nw = sec == 0 ? qn_w : kn_w;
-      const float r = rsqrtf(wave_sum(y1 * y1 + y2 * y2) / (float)HD + eps);
-      const float n1 = y1 * r * nw[lane], n2 = y2 * r * nw[lane + 64];
-      const int p = pos[b];
-      const float c = cosT[(long)p * 64 + lane], s = sinT[(long)p * 64 + lane];
-      y1 = n1 * c - n2 * s;
-      y2 = n2 * c + n1 * s;
+    if ((NORM || ROPE) && sec < 2) {
+      float n1 = y1, n2 = y2;
+      if constexpr (NORM) {
+        const float* nw = sec == 0 ? qn_w : kn_w;
+        const float r = rsqrtf(wave_sum(y1 * y1 + y2 * y2) / (float)HD + eps);
+        n1 = y1 * r * nw[lane]; n2 = y2 * r * nw[lane + 64];
+      }
+      if constexpr (ROPE) {
+        const int p = pos[b];
+        const float c = cosT[(long)p * 64 + lane], s = sinT[(long)p * 64 + lane];
+        y1 = n1 * c - n2 * s;
+        y2 = n2 * c + n1 * s;
+      } else {
+        y1 = n1; y2 = n2;
+      }
     }
     const bf16_t o1 = f2bf(y1), o2 = f2bf(y2);
     if (sec == 0) { qs[job * HD + lane] = bf2f(o1); qs[job * HD + lane + 64] = bf2f(o2); }
@@ -537,8 +545,18 @@ int ta_i_dec_attn(const void* qkv0, const float* qn_w, const float* kn_w, const 
   if (smem > 64 * 1024) return TA_ERR_ARG;
   const DecPf pf = to_pf(next);
   const dim3 grid(Hkv, B + ta_cdiv(pf_wgs(next, Hkv * B), Hkv)), blk(256);
-#define DA(G_) TA_LAUNCH((dec_attn_kernel<G_>), grid, blk, smem, st, (const bf16_t*)qkv0, qn_w, kn_w, cosT, sinT, pos, slot_dev, kmask, (bf16_t*)kc, (bf16_t*)vc, (bf16_t*)out, Hq, Hkv, Lmax, Lmax, eps, scale, 1, B, pf)
-  if (grp == 1) DA(1); else if (grp == 2) DA(2); else if (grp == 4) DA(4); else return TA_ERR_ARG;
+  if (!qn_w != !kn_w || !cosT != !sinT) return TA_ERR_ARG;
+  const bool norm = qn_w != nullptr, rope = cosT != nullptr;      // NULL norm weights: no q/k-norm; NULL tables: a NoPE layer
+#define DA(...) TA_LAUNCH((dec_attn_kernel<__VA_ARGS__>), grid, blk, smem, st, (const bf16_t*)qkv0, qn_w, kn_w, cosT, sinT, pos, slot_dev, kmask, (bf16_t*)kc, (bf16_t*)vc, (bf16_t*)out, Hq, Hkv, Lmax, Lmax, eps, scale, 1, B, pf)
+#define DAG(G_)                                      \
+  do {                                               \
+    if (norm && rope) DA(G_);                        \
+    else if (norm) DA(G_, true, false);              \
+    else if (rope) DA(G_, false, true);              \
+    else DA(G_, false, false);                       \
+  } while (0)
+  if (grp == 1) DAG(1); else if (grp == 2) DAG(2); else if (grp == 4) DAG(4); else return TA_ERR_ARG;
+#undef DAG
 #undef DA
   TA_CHECK_LAUNCH();
   return TA_OK;

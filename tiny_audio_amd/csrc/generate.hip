@@ -23,7 +23,9 @@ namespace {
 constexpr int HD = 128;
 
 // One wave per (clip, q|k|v head): per-head RMSNorm + RoPE at the clip's position (as lm_qkv_post_fwd_kernel), q to a
-// dense [B, Hq, 128] buffer, k / v straight into cache slot *slot_p.
+// dense [B, Hq, 128] buffer, k / v straight into cache slot *slot_p.  NORM = false: no q_norm / k_norm (SmolLM3, Llama); ROPE = false:
+// a NoPE layer (TF:models/smollm3/modeling_smollm3.py:174-250) -- the cache row is the unrotated key, as in training and prefill.
+template <bool NORM, bool ROPE>
 __global__ __launch_bounds__(64) void lm_qkv_post_decode_kernel(const bf16_t* __restrict__ qkv0, const float* __restrict__ qn_w,
                                                                 const float* __restrict__ kn_w, const float* __restrict__ cosT,
                                                                 const float* __restrict__ sinT, const int* __restrict__ pos,
@@ -36,14 +38,21 @@ __global__ __launch_bounds__(64) void lm_qkv_post_decode_kernel(const bf16_t* __
   const long ld = (long)(Hq + 2 * Hkv) * HD;
   const bf16_t* src = qkv0 + (long)b * ld + (long)hh * HD;
   float y1 = bf2f(src[lane]), y2 = bf2f(src[lane + 64]);
-  if (sec < 2) {
-    const float* nw = sec == 0 ? qn_w : kn_w;
-    const float r = rsqrtf(wave_sum(y1 * y1 + y2 * y2) / (float)HD + eps);
-    const float n1 = y1 * r * nw[lane], n2 = y2 * r * nw[lane + 64];
-    const int p = pos[b];
-    const float c = cosT[(long)p * 64 + lane], s = sinT[(long)p * 64 + lane];
-    y1 = n1 * c - n2 * s;
-    y2 = n2 * c + n1 * s;
+  if ((NORM || ROPE) && sec < 2) {
+    float n1 = y1, n2 = y2;
+    if constexpr (NORM) {
+      const float* nw = sec == 0 ? qn_w : kn_w;
+      const float r = rsqrtf(wave_sum(y1 * y1 + y2 * y2) / (float)HD + eps);
+      n1 = y1 * r * nw[lane]; n2 = y2 * r * nw[lane + 64];
+    }
+    if constexpr (ROPE) {
+      const int p = pos[b];
+      const float c = cosT[(long)p * 64 + lane], s = sinT[(long)p * 64 + lane];
+      y1 = n1 * c - n2 * s;
+      y2 = n2 * c + n1 * s;
+    } else {
+      y1 = n1; y2 = n2;
+    }
   }
   bf16_t* dst;
   if (sec == 0) dst = q_out + ((long)b * Hq + head) * HD;
@@ -354,6 +363,8 @@ extern "C" int ta_lm_decode_step(const ta_lm_weights* w, const long* ids, const 
   if (w->head_dim != HD || w->n_layers > 64 || !ids || !pos || !kmask || !slot_dev || !kcache || !vcache || !logits ||
       w->heads % w->kv_heads)
     return TA_ERR_ARG;
+  for (int l = 0; l < w->n_layers; ++l)
+    if (!w->layers[l].qn_w != !w->layers[l].kn_w) return TA_ERR_ARG;      // both q_norm and k_norm, or neither
   const bool lora = w->lora_rank > 0;
   if (lora && !lora_img) return TA_ERR_ARG;
   const int D = w->hidden, F = w->ffn, Hq = w->heads, Hkv = w->kv_heads, bq = Hq * HD, NQKV = (Hq + 2 * Hkv) * HD;
@@ -386,6 +397,8 @@ extern "C" int ta_lm_decode_step(const ta_lm_weights* w, const long* ids, const 
   else RC(ta_embed_scatter(ids, nullptr, w->embed_f32, nullptr, s.x, nullptr, B, D, w->vocab, st));
   for (int l = 0; l < w->n_layers; ++l) {
     const ta_lm_layer& Lw = w->layers[l];
+    const bool norm = Lw.qn_w != nullptr, rope = !((w->nope_layers >> l) & 1);      // per layer: q/k-norm (Qwen3), RoPE (off in a NoPE layer)
+    const float *rcos = rope ? w->rope_cos : nullptr, *rsin = rope ? w->rope_sin : nullptr;
     bf16_t* kc = (bf16_t*)kcache + (size_t)l * layer_elems;
     bf16_t* vc = (bf16_t*)vcache + (size_t)l * layer_elems;
     if (fused) {
@@ -401,7 +414,7 @@ extern "C" int ta_lm_decode_step(const ta_lm_weights* w, const long* ids, const 
                                         last ? (head_bytes < ((long)16 << 20) ? head_bytes : (long)16 << 20) : (long)NQKV * D * 2, nullptr, 0, 0, pw};
       const bool pfon = g_decode_prefetch;
       RC(ta_i_dec_norm_linear(s.x, Lw.ln_in_w, w->eps, Lw.wqkv, s.qkv0, B, NQKV, D, false, pfon ? &p_kv : nullptr, st));
-      RC(ta_i_dec_attn(s.qkv0, Lw.qn_w, Lw.kn_w, w->rope_cos, w->rope_sin, pos, slot_dev, kmask, kc, vc, s.ao, B, Hq, Hkv, Lmax,
+      RC(ta_i_dec_attn(s.qkv0, Lw.qn_w, Lw.kn_w, rcos, rsin, pos, slot_dev, kmask, kc, vc, s.ao, B, Hq, Hkv, Lmax,
                        w->eps, scale, pfon ? &p_o : nullptr, st));
       RC(ta_i_dec_linear_res(s.ao, Lw.wo, s.x1, s.x, B, D, bq, pfon ? &p_gu : nullptr, st));
       RC(ta_i_dec_norm_linear(s.x1, Lw.ln_post_w, w->eps, Lw.wgu, s.act, B, F, D, true, pfon ? &p_d : nullptr, st));
@@ -410,8 +423,14 @@ extern "C" int ta_lm_decode_step(const ta_lm_weights* w, const long* ids, const 
     }
     RC(ta_rmsnorm_fwd(s.x, Lw.ln_in_w, s.xn, nullptr, s.r, B, D, w->eps, 0, st));
     RC(linear(s.xn, Lw.wqkv, s.qkv0, NQKV, D, nullptr, true, (lgm & 1) ? &imgs[l].g[0] : nullptr));
-    TA_LAUNCH(lm_qkv_post_decode_kernel, dim3(Hq + 2 * Hkv, B), dim3(64), 0, st, s.qkv0, Lw.qn_w, Lw.kn_w, w->rope_cos,
-              w->rope_sin, pos, slot_dev, s.q, kc, vc, Hq, Hkv, Lmax, w->eps);
+#define QPD(N_, R_)                                                                                                          \
+  TA_LAUNCH((lm_qkv_post_decode_kernel<N_, R_>), dim3(Hq + 2 * Hkv, B), dim3(64), 0, st, s.qkv0, Lw.qn_w, Lw.kn_w, rcos, rsin, pos, \
+            slot_dev, s.q, kc, vc, Hq, Hkv, Lmax, w->eps)
+    if (norm && rope) QPD(true, true);
+    else if (norm) QPD(true, false);
+    else if (rope) QPD(false, true);
+    else QPD(false, false);
+#undef QPD
     TA_CHECK_LAUNCH();
     TA_LAUNCH(attn_decode_kernel, dim3(Hq, B), dim3(256), smem, st, s.q, kc, vc, kmask, slot_dev, s.ao, Hq, Hkv, Lmax, scale);
     TA_CHECK_LAUNCH();

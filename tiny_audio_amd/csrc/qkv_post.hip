@@ -106,6 +106,9 @@ __global__ __launch_bounds__(256) void enc_qkv_post_kernel(const bf16_t* __restr
 // qkv0 token-major [B*L, (Hq+2Hkv)*128] (pre-norm q | k | v).  Position of token (b,l) = pos ? pos[b*L+l] : l.
 // One workgroup = 64 tokens x one (section, head).  Eight lanes share a row: lane j of the octet owns dims
 // [8j, 8j+8) and [64+8j, 64+8j+8) -- two 16-B chunks that are each other's RoPE partners (pairs d <-> d+64).
+// NORM = false: a decoder without q_norm / k_norm (SmolLM3, Llama; TF:models/smollm3/modeling_smollm3.py:174-250): no statistics, no
+// rq / rk rows.  ROPE = false: a NoPE layer (use_rope false there): no rotation, no table loads.  <true, true> is Qwen3.
+template <bool NORM, bool ROPE>
 __global__ __launch_bounds__(256) void lm_qkv_post_fwd_kernel(const bf16_t* __restrict__ qkv0, const float* __restrict__ qn_w,
                                                               const float* __restrict__ kn_w, const float* __restrict__ cosT,
                                                               const float* __restrict__ sinT, const int* __restrict__ pos,
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void lm_qkv_post_fwd_kernel(const bf16_t* __re
   bf16_t* outT_base = sec == 0 ? QTo : (sec == 1 ? KTo : VTo);      // null: that transposed image is not wanted (Q^T / K^T since the
   bf16_t* outT = outT_base + ((long)b * Hs + head) * HD * Lp;       // backward reads them out of its row tiles; V^T feeds the forward)
   float w1[8], w2[8];
-  if (sec < 2) { const float* nw = sec == 0 ? qn_w : kn_w; load8f(nw + 8 * j, w1); load8f(nw + 64 + 8 * j, w2); }
+  if (NORM && sec < 2) { const float* nw = sec == 0 ? qn_w : kn_w; load8f(nw + 8 * j, w1); load8f(nw + 64 + 8 * j, w2); }
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int tl = (tid >> 3) + it * 32, l = l0 + tl;
@@ -136,22 +139,27 @@ __global__ __launch_bounds__(256) void lm_qkv_post_fwd_kernel(const bf16_t* __re
       const bf16_t* src = qkv0 + ((long)b * L + l) * ld + coff;
       v1 = *(const uint4*)(src + 8 * j); v2 = *(const uint4*)(src + 64 + 8 * j);
     }
-    if (sec < 2) {                                  // whole octets take the same branch; rows >= L carry zeros
+    if ((NORM || ROPE) && sec < 2) {                // whole octets take the same branch; rows >= L carry zeros
       float x1[8], x2[8], c[8], sn[8];
       unpack8(v1, x1); unpack8(v2, x2);
-      float ss = 0.f;
+      float r = 1.f;
+      if constexpr (NORM) {
+        float ss = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) ss += x1[e] * x1[e] + x2[e] * x2[e];
-      const float r = rsqrtf(oct_sum(ss) / (float)HD + eps);
+        for (int e = 0; e < 8; ++e) ss += x1[e] * x1[e] + x2[e] * x2[e];
+        r = rsqrtf(oct_sum(ss) / (float)HD + eps);
+      }
       if (l < L) {
-        if (j == 0) (sec == 0 ? rq : rk)[((long)b * L + l) * Hs + head] = r;
-        const int p = pos ? pos[(long)b * L + l] : l;
-        load8f(cosT + (long)p * 64 + 8 * j, c); load8f(sinT + (long)p * 64 + 8 * j, sn);
+        if (NORM && j == 0) (sec == 0 ? rq : rk)[((long)b * L + l) * Hs + head] = r;
+        if constexpr (ROPE) {
+          const int p = pos ? pos[(long)b * L + l] : l;
+          load8f(cosT + (long)p * 64 + 8 * j, c); load8f(sinT + (long)p * 64 + 8 * j, sn);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float n1 = x1[e] * r * w1[e], n2 = x2[e] * r * w2[e];
-          x1[e] = n1 * c[e] - n2 * sn[e];
-          x2[e] = n2 * c[e] + n1 * sn[e];
+          const float n1 = NORM ? x1[e] * r * w1[e] : x1[e], n2 = NORM ? x2[e] * r * w2[e] : x2[e];
+          x1[e] = ROPE ? n1 * c[e] - n2 * sn[e] : n1;
+          x2[e] = ROPE ? n2 * c[e] + n1 * sn[e] : n2;
         }
         v1 = pack8(x1); v2 = pack8(x2);
       }
@@ -173,7 +181,9 @@ __global__ __launch_bounds__(256) void lm_qkv_post_fwd_kernel(const bf16_t* __re
 
 // ---------------------------------------------------------------------------- LM backward
 // dQ/dK/dV head-major -> dqkv token-major [B*L, (Hq+2Hkv)*128]; same octet-per-row mapping as the forward.
-template <bool WGRAD>      // WGRAD: also accumulate the q_norm / k_norm weight gradients (trainable LM)
+// NORM / ROPE as in the forward: without the norm d(q), d(k) = RoPE^T(dQ), no RMSNorm term, qkv0 / rq / rk are not read; a NoPE
+// layer skips RoPE^T and its table loads.
+template <bool WGRAD, bool NORM, bool ROPE>      // WGRAD: also accumulate the q_norm / k_norm weight gradients (trainable LM)
 __global__ __launch_bounds__(256) void lm_qkv_post_bwd_kernel(const bf16_t* __restrict__ dQ, const bf16_t* __restrict__ dK,
                                                               const bf16_t* __restrict__ dV, const bf16_t* __restrict__ qkv0,
                                                               const float* __restrict__ rq, const float* __restrict__ rk,
@@ -194,34 +204,49 @@ __global__ __launch_bounds__(256) void lm_qkv_post_bwd_kernel(const bf16_t* __re
   const long coff = (long)hh * HD;
   const bf16_t* din = (sec == 0 ? dQ : (sec == 1 ? dK : dV)) + ((long)b * Hs + head) * L * HD;
   float w1[8], w2[8];
-  if (sec < 2) { const float* nw = sec == 0 ? qn_w : kn_w; load8f(nw + 8 * j, w1); load8f(nw + 64 + 8 * j, w2); }
+  if (NORM && sec < 2) { const float* nw = sec == 0 ? qn_w : kn_w; load8f(nw + 8 * j, w1); load8f(nw + 64 + 8 * j, w2); }
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int l = l0 + (tid >> 3) + it * 32;
     const bool live = l < L;
     const int lc = live ? l : L - 1;                // clamped rows compute (octet shuffles stay uniform) but never store
     uint4 g1 = *(const uint4*)(din + (long)lc * HD + 8 * j), g2 = *(const uint4*)(din + (long)lc * HD + 64 + 8 * j);
-    if (sec < 2) {
-      const bf16_t* src = qkv0 + ((long)b * L + lc) * ld + coff;
-      float d1[8], d2[8], x1[8], x2[8], c[8], sn[8];
-      unpack8(g1, d1); unpack8(g2, d2);
-      unpack8(*(const uint4*)(src + 8 * j), x1); unpack8(*(const uint4*)(src + 64 + 8 * j), x2);
-      const int p = pos ? pos[(long)b * L + lc] : lc;
-      load8f(cosT + (long)p * 64 + 8 * j, c); load8f(sinT + (long)p * 64 + 8 * j, sn);
-      const float r = (sec == 0 ? rq : rk)[((long)b * L + lc) * Hs + head];
-      float dot = 0.f;
+    if ((NORM || ROPE) && sec < 2) {
+      if constexpr (NORM) {
+        const bf16_t* src = qkv0 + ((long)b * L + lc) * ld + coff;
+        float d1[8], d2[8], x1[8], x2[8], c[8], sn[8];
+        unpack8(g1, d1); unpack8(g2, d2);
+        unpack8(*(const uint4*)(src + 8 * j), x1); unpack8(*(const uint4*)(src + 64 + 8 * j), x2);
+        if constexpr (ROPE) {
+          const int p = pos ? pos[(long)b * L + lc] : lc;
+          load8f(cosT + (long)p * 64 + 8 * j, c); load8f(sinT + (long)p * 64 + 8 * j, sn);
+        }
+        const float r = (sec == 0 ? rq : rk)[((long)b * L + lc) * Hs + head];
+        float dot = 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float dn1 = d1[e] * c[e] + d2[e] * sn[e], dn2 = d2[e] * c[e] - d1[e] * sn[e];     // RoPE^T
-        x1[e] *= r; x2[e] *= r;                                                             // x-hat
-        if (WGRAD && live) { gw1[e] += dn1 * x1[e]; gw2[e] += dn2 * x2[e]; }                 // d loss / d norm weight
-        d1[e] = dn1 * w1[e]; d2[e] = dn2 * w2[e];
-        dot += d1[e] * x1[e] + d2[e] * x2[e];
+        for (int e = 0; e < 8; ++e) {
+          const float dn1 = ROPE ? d1[e] * c[e] + d2[e] * sn[e] : d1[e], dn2 = ROPE ? d2[e] * c[e] - d1[e] * sn[e] : d2[e];     // RoPE^T
+          x1[e] *= r; x2[e] *= r;                                                             // x-hat
+          if (WGRAD && live) { gw1[e] += dn1 * x1[e]; gw2[e] += dn2 * x2[e]; }                 // d loss / d norm weight
+          d1[e] = dn1 * w1[e]; d2[e] = dn2 * w2[e];
+          dot += d1[e] * x1[e] + d2[e] * x2[e];
+        }
+        const float md = oct_sum(dot) / (float)HD;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { d1[e] = r * (d1[e] - x1[e] * md); d2[e] = r * (d2[e] - x2[e] * md); }
+        g1 = pack8(d1); g2 = pack8(d2);
+      } else {                                              // RoPE^T alone (ROPE holds here)
+        float d1[8], d2[8], c[8], sn[8];
+        unpack8(g1, d1); unpack8(g2, d2);
+        const int p = pos ? pos[(long)b * L + lc] : lc;
+        load8f(cosT + (long)p * 64 + 8 * j, c); load8f(sinT + (long)p * 64 + 8 * j, sn);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float dn1 = d1[e] * c[e] + d2[e] * sn[e], dn2 = d2[e] * c[e] - d1[e] * sn[e];
+          d1[e] = dn1; d2[e] = dn2;
+        }
+        g1 = pack8(d1); g2 = pack8(d2);
       }
-      const float md = oct_sum(dot) / (float)HD;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d1[e] = r * (d1[e] - x1[e] * md); d2[e] = r * (d2[e] - x2[e] * md); }
-      g1 = pack8(d1); g2 = pack8(d2);
     }
     if (live) {
       bf16_t* dst = dqkv + ((long)b * L + l) * ld + coff;
@@ -298,9 +323,17 @@ extern "C" int ta_lm_qkv_post_fwd(const void* qkv0, const float* qn_w, const flo
                                   hipStream_t st) {
   if (B <= 0 || L <= 0) return TA_OK;
   if (Lp % 64 || Lp < L) return TA_ERR_ARG;
-  TA_LAUNCH(lm_qkv_post_fwd_kernel, dim3(Lp / 64, Hq + 2 * Hkv, B), dim3(256), 0, st, (const bf16_t*)qkv0, qn_w,
-                     kn_w, cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, (bf16_t*)QT, (bf16_t*)KT, (bf16_t*)VT, rq,
-                     rk, Hq, Hkv, L, Lp, eps);
+  if (!qn_w != !kn_w || !cosT != !sinT) return TA_ERR_ARG;      // both norm weights or neither (no q/k-norm); both tables or neither (NoPE)
+  const bool norm = qn_w != nullptr, rope = cosT != nullptr;
+  if (norm && (!rq || !rk)) return TA_ERR_ARG;
+#define POSTF(N_, R_)                                                                                                   \
+  TA_LAUNCH((lm_qkv_post_fwd_kernel<N_, R_>), dim3(Lp / 64, Hq + 2 * Hkv, B), dim3(256), 0, st, (const bf16_t*)qkv0, qn_w, \
+            kn_w, cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, (bf16_t*)QT, (bf16_t*)KT, (bf16_t*)VT, rq, rk, Hq, Hkv, L, Lp, eps)
+  if (norm && rope) POSTF(true, true);
+  else if (norm) POSTF(true, false);
+  else if (rope) POSTF(false, true);
+  else POSTF(false, false);
+#undef POSTF
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
@@ -310,14 +343,18 @@ extern "C" int ta_lm_qkv_post_bwd(const void* dQ, const void* dK, const void* dV
                                   const float* sinT, const int* pos, void* dqkv, float* dqn_accum, float* dkn_accum,
                                   int B, int Hq, int Hkv, int L, hipStream_t st) {
   if (B <= 0 || L <= 0) return TA_OK;
-  if (dqn_accum || dkn_accum)
-    TA_LAUNCH(lm_qkv_post_bwd_kernel<true>, dim3(ta_cdiv(L, 64), Hq + 2 * Hkv, B), dim3(256), 0, st, (const bf16_t*)dQ,
-              (const bf16_t*)dK, (const bf16_t*)dV, (const bf16_t*)qkv0, rq, rk, qn_w, kn_w, cosT, sinT, pos,
-              (bf16_t*)dqkv, dqn_accum, dkn_accum, Hq, Hkv, L);
-  else
-    TA_LAUNCH(lm_qkv_post_bwd_kernel<false>, dim3(ta_cdiv(L, 64), Hq + 2 * Hkv, B), dim3(256), 0, st, (const bf16_t*)dQ,
-              (const bf16_t*)dK, (const bf16_t*)dV, (const bf16_t*)qkv0, rq, rk, qn_w, kn_w, cosT, sinT, pos,
-              (bf16_t*)dqkv, dqn_accum, dkn_accum, Hq, Hkv, L);
+  if (!qn_w != !kn_w || !cosT != !sinT) return TA_ERR_ARG;
+  const bool norm = qn_w != nullptr, rope = cosT != nullptr, wgrad = dqn_accum || dkn_accum;
+  if (norm ? (!rq || !rk || !qkv0) : wgrad) return TA_ERR_ARG;      // without the norm there is no norm weight to have a gradient
+#define POSTB(W_, N_, R_)                                                                                                       \
+  TA_LAUNCH((lm_qkv_post_bwd_kernel<W_, N_, R_>), dim3(ta_cdiv(L, 64), Hq + 2 * Hkv, B), dim3(256), 0, st, (const bf16_t*)dQ,    \
+            (const bf16_t*)dK, (const bf16_t*)dV, (const bf16_t*)qkv0, rq, rk, qn_w, kn_w, cosT, sinT, pos, (bf16_t*)dqkv,        \
+            dqn_accum, dkn_accum, Hq, Hkv, L)
+  if (norm && rope) { if (wgrad) POSTB(true, true, true); else POSTB(false, true, true); }
+  else if (norm) { if (wgrad) POSTB(true, true, false); else POSTB(false, true, false); }
+  else if (rope) POSTB(false, false, true);
+  else POSTB(false, false, false);
+#undef POSTB
   TA_CHECK_LAUNCH();
   return TA_OK;
 }

@@ -73,7 +73,9 @@ def whisper_encoder_state_dict(path: str) -> Dict[str, torch.Tensor]:
 
 
 def lm_state_dict(path: str) -> Dict[str, torch.Tensor]:
-    """Qwen3ForCausalLM state dict (``model.embed_tokens.weight`` ... ; a tied ``lm_head.weight`` is dropped).  The embedding
+    """Qwen3ForCausalLM / SmolLM3ForCausalLM / LlamaForCausalLM state dict (``model.embed_tokens.weight`` ... ; a tied
+    ``lm_head.weight`` is dropped).  The three families share their key names; SmolLM3 and Llama simply carry no
+    ``self_attn.q_norm`` / ``k_norm`` (``load_state_dict_hf`` checks that against ``text_config.model_type``).  The embedding
     keeps the checkpoint's row count; ``Qwen3MI355X.load_state_dict_hf`` cuts it to the tokenizer's vocabulary."""
     sd = read_tensors(path, lambda k: k.startswith("model.") or k == "lm_head.weight")
     head = sd.pop("lm_head.weight", None)

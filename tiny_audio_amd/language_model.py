@@ -1,4 +1,5 @@
-"""Frozen Qwen3 causal LM on MI355X (drop-in for ``ASRModel.language_model`` on the training path).
+"""Frozen causal LM on MI355X (drop-in for ``ASRModel.language_model`` on the training path): Qwen3, or a SmolLM3 / Llama-style
+decoder -- no q_norm / k_norm, per-layer NoPE (``LMConfig.qk_norm`` / ``no_rope_layers``; TF:models/smollm3/modeling_smollm3.py:174-250).
 
 Reference: ``Qwen3ForCausalLM.forward`` TF:models/qwen3/modeling_qwen3.py:448-508 + ``ForCausalLMLoss``
 TF:loss/loss_utils.py:33-71, called at tiny_audio/asr_modeling.py:517-526 with frozen weights
@@ -27,6 +28,10 @@ def _pad128(n):
 # LoRA adapters of linears that share an input are stacked into one GROUP (csrc/lora.hip): group -> peft target names
 LORA_GROUPS = (("qkv", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")), ("o", ("self_attn.o_proj",)),
                ("gu", ("mlp.gate_proj", "mlp.up_proj")), ("d", ("mlp.down_proj",)))
+
+
+NO_NORM_FULL_FT = ("full decoder fine-tuning (freeze_language_model=False) of a text tower without q/k-norm (smollm3, llama) is not "
+                   "built: the trainable-LM masters and gradient slots include q_norm / k_norm; train it with LoRA (use_lora=True)")
 
 
 class Qwen3MI355X(torch.nn.Module):
@@ -240,6 +245,8 @@ class Qwen3MI355X(torch.nn.Module):
         norm scales and the embedding table are read from the masters directly."""
         if self.lora_rank:
             raise NotImplementedError("LoRA on top of a trainable base LM is not built")
+        if not self.config.qk_norm:
+            raise NotImplementedError(NO_NORM_FULL_FT)
         if self._w is None:
             raise _lib.Ta355Error("load or initialise the LM weights before enable_full_finetune()")
         c, b = self.config, self._bufs
@@ -386,10 +393,24 @@ class Qwen3MI355X(torch.nn.Module):
         self._bufs["embed_bf16"] = eb
         self._bufs["embed_t_bf16"] = eb.t().contiguous()
 
+    def _check_norm_keys(self, sd, prefix=""):
+        """A q/k-norm tower (Qwen3) needs ``self_attn.q_norm.weight`` / ``k_norm.weight`` of every layer; a tower without (SmolLM3,
+        Llama) must not be handed any: either mistake would otherwise run the wrong arithmetic silently."""
+        for i in range(self.config.num_hidden_layers):
+            for n in ("q_norm", "k_norm"):
+                k = f"model.layers.{i}.self_attn.{n}.weight"
+                has = (prefix + k) in sd or k in sd
+                if self.config.qk_norm and not has:
+                    raise KeyError(f"{k} is missing: a {self.config.model_type} text tower has q/k-norm")
+                if has and not self.config.qk_norm:
+                    raise KeyError(f"{k}: a {self.config.model_type} text tower has no q/k-norm (text_config.model_type is wrong for this checkpoint)")
+
     def load_state_dict_hf(self, sd):
-        """sd: {``model.layers.N.self_attn.q_proj.weight`` ...: array-like fp32} in the reference's naming."""
+        """sd: {``model.layers.N.self_attn.q_proj.weight`` ...: array-like fp32} in the reference's naming (SmolLM3 / Llama: the same
+        names minus ``q_norm`` / ``k_norm``)."""
         c, dev = self.config, self.device_
         g = lambda k: torch.as_tensor(sd[k]).to(device=dev, dtype=F32)
+        self._check_norm_keys(sd)
         self._bufs = {}
         self._set_embedding(g("model.embed_tokens.weight"))
         self._bufs["norm_w"] = g("model.norm.weight").contiguous()
@@ -403,8 +424,9 @@ class Qwen3MI355X(torch.nn.Module):
             self._pack_matrix(q + "wd", g(p + "mlp.down_proj.weight"))
             self._bufs[q + "ln_in_w"] = g(p + "input_layernorm.weight").contiguous()
             self._bufs[q + "ln_post_w"] = g(p + "post_attention_layernorm.weight").contiguous()
-            self._bufs[q + "qn_w"] = g(a + "q_norm.weight").contiguous()
-            self._bufs[q + "kn_w"] = g(a + "k_norm.weight").contiguous()
+            if c.qk_norm:
+                self._bufs[q + "qn_w"] = g(a + "q_norm.weight").contiguous()
+                self._bufs[q + "kn_w"] = g(a + "k_norm.weight").contiguous()
         self._finalize()
         return self
 
@@ -426,8 +448,9 @@ class Qwen3MI355X(torch.nn.Module):
             self._pack_matrix(q + "wd", rn(D, F, std=0.5 / math.sqrt(F)))
             self._bufs[q + "ln_in_w"] = 1 + rn(D, std=0.1)
             self._bufs[q + "ln_post_w"] = 1 + rn(D, std=0.1)
-            self._bufs[q + "qn_w"] = 1 + rn(hd, std=0.1)
-            self._bufs[q + "kn_w"] = 1 + rn(hd, std=0.1)
+            if c.qk_norm:
+                self._bufs[q + "qn_w"] = 1 + rn(hd, std=0.1)
+                self._bufs[q + "kn_w"] = 1 + rn(hd, std=0.1)
         self._finalize()
         return self
 
@@ -439,12 +462,14 @@ class Qwen3MI355X(torch.nn.Module):
         arr = (_lib.LmLayer * L)()
         for i in range(L):
             for f, _ in _lib.LmLayer._fields_:
+                if f in ("qn_w", "kn_w") and not c.qk_norm:
+                    continue                                   # NULL = no q/k-norm (include/ta355.h ta_lm_layer)
                 if not f.startswith(("la_", "lb_")):
                     setattr(arr[i], f, b[f"layers.{i}.{f}"].data_ptr())
         w = _lib.LmWeights(vocab=c.vocab_size, vocab_pad=self.vocab_pad, hidden=c.hidden_size, ffn=c.intermediate_size,
                            n_layers=L, heads=c.num_attention_heads, kv_heads=c.num_key_value_heads, head_dim=c.head_dim,
                            max_pos=c.max_position_embeddings, eps=c.rms_norm_eps, res_f32=int(self._res_f32),
-                           dx_f32=int(self._dx_f32))
+                           dx_f32=int(self._dx_f32), nope_layers=c.nope_mask)
         for f in ("embed_f32", "embed_bf16", "embed_t_bf16", "norm_w", "rope_cos", "rope_sin"):
             setattr(w, f, b[f].data_ptr())
         w.layers = C.cast(arr, C.POINTER(_lib.LmLayer))
@@ -473,7 +498,8 @@ class Qwen3MI355X(torch.nn.Module):
             sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"] = gu[:F], gu[F:]
             sd[p + "mlp.down_proj.weight"] = f(b[q + "wd"])
             sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = f(b[q + "ln_in_w"]), f(b[q + "ln_post_w"])
-            sd[a + "q_norm.weight"], sd[a + "k_norm.weight"] = f(b[q + "qn_w"]), f(b[q + "kn_w"])
+            if c.qk_norm:
+                sd[a + "q_norm.weight"], sd[a + "k_norm.weight"] = f(b[q + "qn_w"]), f(b[q + "kn_w"])
         return sd
 
     def get_input_embeddings_weight(self):
