@@ -409,6 +409,44 @@ int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, const int* kma
                       const int* label_rows, int n_label_rows, float* d_audio, long n_audio_rows, float* d_embeds,
                       const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wgrads, const long* ids, const void* tape, void* ws,
                       long ws_bytes, const ta_lora_dropout* drop, hipStream_t st);
+/* ---- Sequence packing: several clips per LM row, block-diagonal causal attention.  A packed row holds S >= 1 segments back to back
+ * (one segment = one clip's whole chat sequence) and right padding; segment_ids int32 [R, L] is 0 on padding and 1..S, non-decreasing
+ * and gap-free, on the tokens.  The query at (r, q) sees the key at (r, k) iff both carry the same non-zero id and k <= q.
+ * ta_segment_table: seg int32 [2, R*L] -- plane 0 the index of the first token of q's segment (q + 1 on padding), plane 1 one past
+ * the last token of k's segment (k on padding) -- and, unless NULL, pos int32 [R*L], the RoPE positions restarting at 0 in every
+ * segment.  The attention kernels test  seg[q] <= k <= q  next to the key mask and skip the KV / query tiles outside those bounds.
+ * ta_audio_index_seg: ta_audio_index for packed rows.  counts i64 [C] and the projector output [C, N, D] are per CLIP, clip c being the
+ * c-th segment row-major over (row, segment); the j-th <audio> token of that segment takes row c*N + j while j < counts[c] and j < N,
+ * -2 (a zero row) beyond, exactly as ta_audio_index treats surplus placeholders; every other token -1.
+ * ta_lm_forward_loss_seg / ta_lm_backward_seg: the _ex calls with the table next to kmask / pos (the backward needs the forward's
+ * table: it is not on the tape, and ta_lm_tape_bytes / ta_lm_workspace_bytes do not change).  seg NULL is exactly the _ex call.  The
+ * caller masks the label at the first token of every segment, so that the last token of one clip never predicts the next clip. */
+int ta_segment_table(const int* segment_ids, int* seg, int* pos, int R, int L, hipStream_t st);
+int ta_audio_index_seg(const long* ids, const int* segment_ids, const long* counts, int* src_row, int R, int L, int C, int N,
+                       long audio_id, hipStream_t st);
+int ta_lm_forward_loss_seg(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                           const int* kmask, const int* pos, const int* seg, int B, int L, const int* label_rows,
+                           const long* label_targets, int n_label_rows, float loss_scale, float* loss,
+                           float* nll_rows, void* logits_out, void* tape, void* ws, long ws_bytes,
+                           const ta_lora_dropout* drop, hipStream_t st);
+int ta_lm_backward_seg(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B, int L,
+                       const int* label_rows, int n_label_rows, float* d_audio, long n_audio_rows, float* d_embeds,
+                       const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wgrads, const long* ids, const void* tape, void* ws,
+                       long ws_bytes, const ta_lora_dropout* drop, hipStream_t st);
+/* The attention entry points of the LM over packed rows (causal, head_dim 128; seg NULL = the plain call). */
+int ta_attention_fwd_seg(const void* Q, const void* K, const void* VT, void* O, float* LSE, const int* kmask, const int* seg,
+                         int B, int Hq, int Hkv, int L, int Lp, float scale, hipStream_t st);
+int ta_attention_fwd_qkv_seg(const void* qkv0, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
+                             const int* pos, void* Q, void* K, void* V, float* rq, float* rk, void* O, float* LSE,
+                             const int* kmask, const int* seg, int B, int Hq, int Hkv, int L, float scale, float eps,
+                             hipStream_t st);
+int ta_attention_bwd_seg(const void* Q, const void* K, const void* V, const void* dO, long dO_stride, const float* LSE,
+                         const float* Delta, const int* kmask, const int* seg, void* dQ, void* dK, void* dV, int B, int Hq,
+                         int Hkv, int L, int Lp, float scale, hipStream_t st);
+int ta_attention_bwd_qkv_seg(const void* Q, const void* K, const void* V, const void* dO, long dO_stride, const float* LSE,
+                             const float* Delta, const int* kmask, const int* seg, const void* qkv0, const float* rq,
+                             const float* rk, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
+                             const int* pos, void* dqkv, int B, int Hq, int Hkv, int L, int Lp, float scale, hipStream_t st);
 /* The keep mask of linear `linear` (0..6, peft order) in layer `layer` over M rows x in columns: out u8 [M, in] (1 = kept). */
 int ta_lora_dropout_keep(const ta_lora_dropout* drop, int layer, int linear, int M, int in, unsigned char* out, hipStream_t st);
 

@@ -327,8 +327,15 @@ class ASRModel(nn.Module):
                 labels: Optional[torch.Tensor] = None, audio_token_counts: Optional[torch.Tensor] = None,
                 num_items_in_batch=None, return_logits: bool = True, frame_keep=None, after_encoder=None,
                 position_ids: Optional[torch.Tensor] = None, past_key_values=None, inputs_embeds=None,
-                use_cache: Optional[bool] = None, cache_position=None, **kwargs):
+                use_cache: Optional[bool] = None, cache_position=None, segment_ids: Optional[torch.Tensor] = None, **kwargs):
         """Training/eval forward (tiny_audio/asr_modeling.py:481-533).
+
+        ``segment_ids`` [R, L] (sequence packing, ``DataCollator(pack_to=...)``; not in the reference): a row holds several clips'
+        chat sequences back to back -- 0 on the right padding, 1, 2, ... on the tokens of the row's clips.  Attention stays inside a
+        clip (same id, causal), RoPE positions restart at 0 in every clip unless ``position_ids`` is given, the label at the first
+        token of a clip is never a target, and the <audio> placeholders of the c-th clip (row-major over (row, clip)) take the projector
+        rows of clip c: ``input_features`` / ``audio_token_counts`` stay per clip, [C, ...].  One host check per call validates the
+        layout.  ``None``: one clip per row, nothing changes.
 
         ``position_ids`` [B, L] (or [1, L] / [L], broadcast over the batch): the RoPE position of every token, handed to the LM
         as the reference does (asr_modeling.py:517-526 -> TF:models/qwen3/modeling_qwen3.py:386-389, default arange(L)).
@@ -369,17 +376,42 @@ class ASRModel(nn.Module):
             if lo < 0 or hi >= max_pos:
                 raise ValueError(f"position_ids must lie in [0, {max_pos}) (max_position_embeddings); got [{lo}, {hi}]")
             pos = pos.expand(B, L).contiguous().reshape(-1)
+        seg, sid = None, None
+        if segment_ids is not None:
+            sid, n_clips = self._check_segment_ids(segment_ids, attention_mask, B, L)
+            sid = sid.to(dev).contiguous()
+            seg, seg_pos = ops.segment_table(sid)
+            if pos is None:
+                pos = seg_pos
+            if attention_mask is None:
+                attention_mask = sid != 0
+            if labels is not None:                        # the last token of one clip never predicts the first token of the next
+                if kwargs.get("label_meta") is not None:
+                    raise ValueError("label_meta cannot be combined with segment_ids: the labels at segment starts are masked here")
+                first = torch.ones_like(sid, dtype=torch.bool)
+                first[:, 1:] = sid[:, 1:] != sid[:, :-1]
+                labels = labels.to(device=dev, dtype=torch.int64).masked_fill(first, -100)
         audio, src_row = None, None
         if input_features is None and after_encoder is not None:
             after_encoder()
         if input_features is not None:
             y = self._encode_audio(input_features.to(dev), frame_keep, after_encoder)     # [B, N, D]
             N = y.shape[1]
-            if audio_token_counts is None:
-                audio_token_counts = (ids == self.audio_token_id).sum(dim=-1)
-            counts = audio_token_counts.to(device=dev, dtype=torch.int64).contiguous()
-            src_row = ops.audio_index(ids, counts, N, self.audio_token_id)
-            audio = y.reshape(B * N, -1)
+            if sid is not None:
+                placed = self._segment_placeholder_counts(ids, sid, n_clips)
+                if audio_token_counts is None:
+                    audio_token_counts = placed
+                counts = audio_token_counts.to(device=dev, dtype=torch.int64).contiguous()
+                if y.shape[0] != n_clips or counts.numel() != n_clips or not bool((placed == counts).all()):
+                    raise ValueError(f"segment_ids holds {n_clips} clips with {placed.tolist()} <audio> placeholders; input_features has "
+                                     f"{y.shape[0]} clips and audio_token_counts is {counts.tolist()}")
+                src_row = ops.audio_index_seg(ids, sid, counts, N, self.audio_token_id)
+            else:
+                if audio_token_counts is None:
+                    audio_token_counts = (ids == self.audio_token_id).sum(dim=-1)
+                counts = audio_token_counts.to(device=dev, dtype=torch.int64).contiguous()
+                src_row = ops.audio_index(ids, counts, N, self.audio_token_id)
+            audio = y.reshape(y.shape[0] * N, -1)
         kmask = None if attention_mask is None else attention_mask.to(device=dev, dtype=torch.int32).contiguous()
         n_lab, rows, targets = 0, None, None
         if labels is not None:
@@ -394,7 +426,8 @@ class ASRModel(nn.Module):
             audio = torch.zeros((1, self.config.llm_dim), device=dev, dtype=F32)
         loss, nll, logits = FrozenLMLoss.apply(audio, self.language_model, ids, src_row, kmask, rows, targets, n_lab,
                                                scale, bool(return_logits),
-                                               *(self.language_model.lora_parameters() or self.language_model.ft_parameters()), pos=pos)
+                                               *(self.language_model.lora_parameters() or self.language_model.ft_parameters()), pos=pos,
+                                               **({} if seg is None else {"seg": seg}))
         V = self.config.text_config.vocab_size
         logits = logits.reshape(B, L, -1)[:, :, :V] if return_logits else None
         aux, loss_ce = None, loss
@@ -406,6 +439,35 @@ class ASRModel(nn.Module):
                 loss = loss + aux.to(loss.device)                                          # asr_modeling.py:528-531
         return CausalLMOutput(loss=loss, logits=logits, nll=nll[:n_lab] if labels is not None else None,
                               n_label_tokens=n_lab, aux_loss=aux, loss_ce=loss_ce)
+
+    # ------------------------------------------------------------------ sequence packing
+    @staticmethod
+    def _check_segment_ids(segment_ids, attention_mask, B, L):
+        """-> (int32 [B, L] on the host, number of clips).  ValueError unless every row is 1, 2, ..., S (non-decreasing, no gaps, at
+        least one clip) followed by zeros only, and -- when an attention mask is given -- the mask is exactly ``segment_ids != 0``."""
+        sid = torch.as_tensor(segment_ids).detach().to("cpu")
+        if sid.dim() != 2 or tuple(sid.shape) != (B, L) or sid.dtype.is_floating_point:
+            raise ValueError(f"segment_ids must be an integer tensor [{B}, {L}] like input_ids; got {sid.dtype} {tuple(sid.shape)}")
+        sid = sid.to(torch.int32)
+        real = sid != 0
+        step = sid[:, 1:] - sid[:, :-1]
+        ok = bool((sid >= 0).all()) and bool((sid[:, 0] == 1).all())
+        # inside the tokens the id stays or grows by one; after the first 0 everything is 0 (right padding only)
+        ok = ok and bool(((step == 0) | (step == 1))[real[:, 1:]].all()) and bool((~real[:, 1:] | real[:, :-1]).all())
+        if not ok:
+            raise ValueError("segment_ids must be 1, 2, ..., S along every row (non-decreasing, no gaps), then 0 on the right padding")
+        if attention_mask is not None:
+            att = torch.as_tensor(attention_mask).detach().to("cpu")
+            if tuple(att.shape) != (B, L) or not bool(((att != 0) == real).all()):
+                raise ValueError("attention_mask disagrees with segment_ids: it must be 1 exactly where segment_ids != 0")
+        return sid, int(sid.max(dim=1).values.sum())
+
+    def _segment_placeholder_counts(self, ids, sid, n_clips):
+        """<audio> placeholders of every clip of a packed batch, in clip order (row-major over (row, segment)) -> int64 [C], device."""
+        per_row = sid.max(dim=1).values.to(torch.int64)
+        clip = (torch.cumsum(per_row, 0) - per_row)[:, None] + sid.to(torch.int64) - 1          # clip index of every token (junk on padding)
+        m = (ids == self.audio_token_id) & (sid != 0)
+        return torch.bincount(clip[m], minlength=n_clips)[:n_clips]
 
     # ------------------------------------------------------------------ checkpoints (SURVEY.md section 8(f) rank 3)
     def save_pretrained(self, save_directory, **kwargs):

@@ -99,15 +99,65 @@ class ChatMLTextCollator:
                 "prompts": self._pad(p_ids, pad), "prompt_attention_mask": self._pad(p_att, 0)}
 
 
+def first_fit(lengths, pack_to: int):
+    """First-fit in arrival order: sequence i goes to the first row that still has ``lengths[i]`` free slots out of ``pack_to``, else
+    opens a new row; a sequence longer than ``pack_to`` gets a row of its own.  -> list of rows, each the list of sequence indices."""
+    rows, free = [], []
+    for i, n in enumerate(lengths):
+        for r in range(len(rows)):
+            if n <= free[r]:
+                rows[r].append(i); free[r] -= n
+                break
+        else:
+            rows.append([i]); free.append(max(pack_to - n, 0))
+    return rows
+
+
+def pack_sequences(seqs, labels, pack_to: int, pad_id: int, ignore_index: int = -100):
+    """Unpadded token / label sequences -> the packed text batch: right-padded ``input_ids, labels, attention_mask, segment_ids,
+    position_ids`` [R, Lp] (Lp = the longest row) and ``order``, the sequence indices in packed order (row-major over (row, segment)).
+    ``segment_ids`` is 0 on padding and 1..S on the tokens; positions restart at 0 in every segment; the label at the first token of
+    every segment is ``ignore_index`` (the last token of one clip must not predict the first of the next)."""
+    rows = first_fit([len(s) for s in seqs], pack_to)
+    Lp = max(sum(len(seqs[i]) for i in row) for row in rows)
+    R = len(rows)
+    out = {"input_ids": torch.full((R, Lp), int(pad_id), dtype=torch.int64), "labels": torch.full((R, Lp), ignore_index, dtype=torch.int64),
+           "attention_mask": torch.zeros((R, Lp), dtype=torch.int64), "segment_ids": torch.zeros((R, Lp), dtype=torch.int64),
+           "position_ids": torch.zeros((R, Lp), dtype=torch.int64)}
+    for r, row in enumerate(rows):
+        at = 0
+        for s, i in enumerate(row):
+            n = len(seqs[i])
+            out["input_ids"][r, at:at + n] = torch.as_tensor(seqs[i], dtype=torch.int64)
+            lab = torch.as_tensor(labels[i], dtype=torch.int64).clone()
+            if n:
+                lab[0] = ignore_index
+            out["labels"][r, at:at + n] = lab
+            out["attention_mask"][r, at:at + n] = 1
+            out["segment_ids"][r, at:at + n] = s + 1
+            out["position_ids"][r, at:at + n] = torch.arange(n)
+            at += n
+    return out, [i for row in rows for i in row]
+
+
 class DataCollator:
-    """Drop-in for scripts/train.py:DataCollator with the feature extraction on the device."""
+    """Drop-in for scripts/train.py:DataCollator with the feature extraction on the device.
+
+    ``pack_to`` (sequence packing, not in the reference): instead of padding every clip's chat sequence to the longest of the batch,
+    place the sequences first-fit, in arrival order, into rows of ``pack_to`` tokens (``pack_sequences``) and emit ``segment_ids`` /
+    ``position_ids`` next to the usual keys; ``ASRModel.forward`` then attends within each clip only.  The audio keys stay per clip,
+    in the order the clips were placed.  ``None`` (default) is the padded batch, key for key."""
 
     def __init__(self, tokenizer: Any, feature_extractor: Any, sample_rate: int, system_prompt: Optional[str] = None,
-                 projector: Any = None, encoder_conv_layers: Optional[list] = None, text_collator: Optional[Callable] = None):
+                 projector: Any = None, encoder_conv_layers: Optional[list] = None, text_collator: Optional[Callable] = None,
+                 pack_to: Optional[int] = None):
         self.tokenizer, self.feature_extractor, self.sample_rate = tokenizer, feature_extractor, sample_rate
         self.system_prompt, self.projector = system_prompt, projector
         self.encoder_conv_layers = encoder_conv_layers or DEFAULT_ENCODER_CONV_LAYERS
         self.text_collator = text_collator or ChatMLTextCollator(tokenizer, max_length=2048)
+        if pack_to is not None and int(pack_to) <= 0:
+            raise ValueError(f"pack_to must be a positive row length; got {pack_to}")
+        self.pack_to = None if pack_to is None else int(pack_to)
 
     def _extract_audio_arrays(self, features):
         """The reference's row filter (scripts/train.py:274-311): drop empty / non-finite audio, labels that normalise to
@@ -150,10 +200,24 @@ class DataCollator:
         mel_lengths = audio["attention_mask"].sum(dim=-1)
         enc_lengths = compute_encoder_output_length(mel_lengths, self.encoder_conv_layers)
         counts = self.projector.get_output_length(enc_lengths).to(torch.long)
-        batch = self.text_collator([self._build_sample(f, n) for f, n in zip(kept, counts.tolist())])
-        batch["input_features"] = audio["input_features"]
-        batch["audio_attention_mask"] = audio["attention_mask"]
-        batch["audio_token_counts"] = counts
+        samples = [self._build_sample(f, n) for f, n in zip(kept, counts.tolist())]
+        if self.pack_to is None:
+            batch = self.text_collator(samples)
+            batch["input_features"] = audio["input_features"]
+            batch["audio_attention_mask"] = audio["attention_mask"]
+            batch["audio_token_counts"] = counts
+            return batch
+        # every clip's sequence exactly as the padded batch would hold it, minus the padding: one clip at a time through the same collator
+        seqs, labs = [], []
+        for s in samples:
+            one = self.text_collator([s])
+            keep = one["attention_mask"][0].bool()
+            seqs.append(one["input_ids"][0][keep]); labs.append(one["labels"][0][keep])
+        batch, order = pack_sequences(seqs, labs, self.pack_to, int(self.tokenizer.pad_token_id))
+        order = torch.as_tensor(order, dtype=torch.long)
+        batch["input_features"] = audio["input_features"][order]
+        batch["audio_attention_mask"] = audio["attention_mask"][order]
+        batch["audio_token_counts"] = counts[order]
         return batch
 
 

@@ -404,7 +404,8 @@ extern "C" long ta_lm_workspace_bytes(const ta_lm_weights* w, int B, int L, int 
 // tape (generation keeps them across decode steps); kcache/vcache: see ta_lm_prefill.
 static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int L, const int* kmask, const int* pos,
                              LmLayerTape* store, bool alias, float* x_final, LmWs& s, const ta_i_lora_layer_imgs* ext,
-                             bf16_t* kcache, bf16_t* vcache, int Lmax, hipStream_t st, const LoraDropDev* drop = nullptr) {
+                             bf16_t* kcache, bf16_t* vcache, int Lmax, hipStream_t st, const LoraDropDev* drop = nullptr,
+                             const int* seg = nullptr) {
   const int M = (int)d.M;
   const float scale = 1.0f / sqrtf((float)d.hd);
   const bool lora = w->lora_rank > 0;
@@ -488,7 +489,10 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
     RC(gemm_opt(xn, Lw.wqkv, p.qkv0, M, d.NQKV, d.D, nullptr, nullptr, 0, 1, take_ext(), st));
     // short causal sequences: QK-norm + RoPE + head split ride in the attention kernel's staging; longer ones take two kernels
     const bool fused_fwd = lm_attn_fused(d, L);
-    if (fused_fwd)
+    if (fused_fwd && seg)                            // packed rows: the segment-aware instantiation of the same kernel
+      RC(ta_attention_fwd_qkv_seg(p.qkv0, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, p.q, p.k, (kcache || w->train_base) ? p.v : nullptr, p.rq, p.rk, p.ao, p.lse, kmask,
+                                  seg, B, d.nq, d.nkv, L, scale, w->eps, st));
+    else if (fused_fwd)
       // the head-major copy of V exists for the KV cache (prefill) and for the un-fused backward (trainable q_norm / k_norm); the fused
       // backward reads V in place from qkv0, which the tape keeps anyway
       RC(ta_attention_fwd_qkv(p.qkv0, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, p.q, p.k, (kcache || w->train_base) ? p.v : nullptr, p.rq, p.rk, p.ao, p.lse, kmask,
@@ -502,7 +506,8 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
           hipMemcpy2DAsync(vcache + (size_t)l * rows * Lmax * d.hd, pitch, p.v, row, row, rows, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return TA_ERR_LAUNCH;
     }
-    if (!fused_fwd) RC(ta_attention_fwd(p.q, p.k, p.vt, p.ao, p.lse, kmask, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
+    if (!fused_fwd && seg) RC(ta_attention_fwd_seg(p.q, p.k, p.vt, p.ao, p.lse, kmask, seg, B, d.nq, d.nkv, L, d.Lp, scale, st));
+    else if (!fused_fwd) RC(ta_attention_fwd(p.q, p.k, p.vt, p.ao, p.lse, kmask, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
     if (lgm & 2) RC(lora_fwd(p.ao, d.nq * d.hd, p.i_o, p.xa_o, 1, 8 * l + 3));
     RC(res_gemm(p.ao, Lw.wo, p.x1, d.nq * d.hd, p.x_in));
     bf16_t* xn2 = keep ? p.xn2_s : s.xn;
@@ -534,11 +539,11 @@ static int lm_lora_drop(const ta_lm_weights* w, const ta_lora_dropout* drop, Lor
   *out = dd;
   return TA_OK;
 }
-extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
-                                     const int* kmask, const int* pos, int B, int L, const int* label_rows,
-                                     const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
-                                     void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
-                                     hipStream_t st) {
+static int lm_forward_loss_impl(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                                const int* kmask, const int* pos, const int* seg, int B, int L, const int* label_rows,
+                                const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
+                                void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
+                                hipStream_t st) {
   LoraDropDev dd;
   const LoraDropDev* dp = nullptr;
   RC(lm_lora_drop(w, drop, &dd, &dp));
@@ -556,7 +561,7 @@ extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, co
   // inputs_embeds = embed_tokens(ids) with the <audio> rows replaced by projector rows (asr_modeling.py:498,511-515)
   if (lm_res_bf16(w)) RC(ta_embed_scatter(ids, src_row, w->embed_f32, audio, nullptr, x, M, d.D, w->vocab, st));
   else RC(ta_embed_scatter(ids, src_row, w->embed_f32, audio, x, nullptr, M, d.D, w->vocab, st));
-  RC(lm_layers_forward(w, d, B, L, kmask, pos, store, false, t.x_final, s, nullptr, nullptr, nullptr, 0, st, dp));
+  RC(lm_layers_forward(w, d, B, L, kmask, pos, store, false, t.x_final, s, nullptr, nullptr, nullptr, 0, st, dp, seg));
   if (lm_res_bf16(w)) RC(ta_rmsnorm_fwd_bf16(t.x_final, w->norm_w, t.hn, nullptr, t.r_f, M, d.D, w->eps, st));
   else RC(ta_rmsnorm_fwd(t.x_final, w->norm_w, t.hn, nullptr, t.r_f, M, d.D, w->eps, 0, st));
   if (logits_out)   // the reference's outputs.logits (bf16 under autocast), all positions
@@ -572,6 +577,25 @@ extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, co
                         t.dlogits, w->vocab_pad, st));
   }
   return TA_OK;
+}
+
+extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                                     const int* kmask, const int* pos, int B, int L, const int* label_rows,
+                                     const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
+                                     void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
+                                     hipStream_t st) {
+  return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, nullptr, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
+                              nll_rows, logits_out, tape, ws, ws_bytes, drop, st);
+}
+// Sequence packing: rows that hold several clips back to back (include/ta355.h).  `seg` is the table ta_segment_table wrote for these
+// rows; everything but attention is row-local, so it reaches the attention launches only.  NULL = ta_lm_forward_loss_ex.
+extern "C" int ta_lm_forward_loss_seg(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                                      const int* kmask, const int* pos, const int* seg, int B, int L, const int* label_rows,
+                                      const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
+                                      void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
+                                      hipStream_t st) {
+  return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, seg, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
+                              nll_rows, logits_out, tape, ws, ws_bytes, drop, st);
 }
 
 // ---------------------------------------------------------------------------- greedy decoding: prompt pass
@@ -627,10 +651,29 @@ extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const 
   return ta_lm_backward_ex(w, src_row, kmask, pos, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids, tape,
                            ws, ws_bytes, nullptr, st);
 }
+static int lm_backward_impl(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B, int L,
+                            const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                            const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                            void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st);
 extern "C" int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
                                  const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
                                  const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
                                  void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
+  return lm_backward_impl(w, src_row, kmask, pos, nullptr, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
+                          tape, ws, ws_bytes, drop, st);
+}
+// the backward of a ta_lm_forward_loss_seg forward: the same table (the tape does not hold it)
+extern "C" int ta_lm_backward_seg(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B,
+                                  int L, const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                                  const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                                  void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
+  return lm_backward_impl(w, src_row, kmask, pos, seg, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
+                          tape, ws, ws_bytes, drop, st);
+}
+static int lm_backward_impl(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B, int L,
+                            const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                            const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                            void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
   LoraDropDev dd;
   const LoraDropDev* dp = nullptr;
   RC(lm_lora_drop(w, drop, &dd, &dp));
@@ -804,7 +847,16 @@ extern "C" int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, con
     // K / V resident -- 92.8 us warm / 117.5 cold per layer against 91.8 / 106.0 here --, and Delta = rowsum(dO o O) inside this
     // kernel -- 87.3 us against 67.2 + 9.5; profiles/r04_g/h_*, r04_zj_*.)
     RC(ta_attn_bwd_prep(s.dao, p.ao, s.delta, s.dot, B, d.nq, L, d.Lp, st));
-    if (!(g && (g->dqn || g->dkn))) {
+    const bf16_t* v_hm = (w->train_base || !lm_attn_fused(d, L)) ? p.v : nullptr;     // the head-major V, where the forward wrote one
+    if (seg && !(g && (g->dqn || g->dkn))) {           // packed rows: the segment-aware instantiations of the same kernel
+      RC(ta_attention_bwd_qkv_seg(p.q, p.k, v_hm, s.dao, (long)d.nq * d.hd, p.lse, s.delta, kmask, seg, p.qkv0, p.rq, p.rk, Lw.qn_w, Lw.kn_w,
+                                  lm_rope_cos(w, l), lm_rope_sin(w, l), pos, s.dqkv, B, d.nq, d.nkv, L, d.Lp, scale, st));
+    } else if (seg) {
+      RC(ta_attention_bwd_seg(p.q, p.k, p.v, s.dao, (long)d.nq * d.hd, p.lse, s.delta, kmask, seg, s.dq, s.dk, s.dv, B, d.nq, d.nkv, L,
+                              d.Lp, scale, st));
+      RC(ta_lm_qkv_post_bwd(s.dq, s.dk, s.dv, p.qkv0, p.rq, p.rk, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, s.dqkv,
+                            g ? g->dqn : nullptr, g ? g->dkn : nullptr, B, d.nq, d.nkv, L, st));
+    } else if (!(g && (g->dqn || g->dkn))) {
       RC(ta_attention_bwd_qkv(p.q, p.k, (w->train_base || !lm_attn_fused(d, L)) ? p.v : nullptr, s.dao, (long)d.nq * d.hd, p.lse, s.delta, kmask, p.qkv0, p.rq, p.rk, Lw.qn_w, Lw.kn_w,
                               lm_rope_cos(w, l), lm_rope_sin(w, l), pos, s.dqkv, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
     } else {

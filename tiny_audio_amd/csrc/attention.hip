@@ -194,16 +194,33 @@ __device__ __forceinline__ float group_max(float x) {
   return fmaxf(__uint_as_float(q[0]), __uint_as_float(q[1]));
 }
 
+// Sequence packing (SEG instantiations): a row holds several clips back to back.  `seg` is the table ta_segment_table writes, two planes of
+// [B * L] ints: seg[b, q] = first key index of q's segment (q + 1 for a padding token: an empty key range), seg[B * L + (b, k)] = one
+// past the last row of k's segment (k for padding).  Query q sees key k iff seg[q] <= k <= q -- equivalently k <= q < seg_end[k], the
+// key-side form the dK / dV body uses -- so both tests are one compare on a per-lane value, next to the key mask.  The same values
+// bound the tile loops: a query tile starts at the KV tile of its smallest seg[q], a key tile stops at the query tile of its largest end.
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return __builtin_amdgcn_readfirstlane(v);
+}
+
 // One workgroup = 128 query rows of one head (4 waves x 2 sub-tiles of 16 rows): every K / V^T fragment read from LDS
 // feeds two MFMAs.  The softmax denominator is NOT summed on the VALU: the V^T image carries 16 extra rows whose
 // first is all ones, so one extra MFMA block per k-step accumulates l = sum_k P[q,k] next to O (and is rescaled
 // with it).  Per score element that leaves: 1 FMA + 1 v_exp + 1/2 v_max3 + 1/2 v_cvt_pk on the VALU.
-template <int HD, bool CAUSAL, int QSUB>
+template <int HD, bool CAUSAL, int QSUB, bool SEG = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                        const bf16_t* __restrict__ VT, bf16_t* __restrict__ O,
                                                        float* __restrict__ LSE, const int* __restrict__ kmask,
                                                        int B, int Hq, int Hkv, int L, int Lp, float scale,
-                                                       const ta_attn_layout lay, const int valign) {
+                                                       const ta_attn_layout lay, const int valign,
+                                                       const int* __restrict__ seg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ND = HD / 16;                        // O^T row blocks; block ND is the row-sum block
   char* Ks = smem;
@@ -245,11 +262,20 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
 
   int ntiles = (L + KV_TILE - 1) / KV_TILE;
   if (CAUSAL) { const int lim = (qt * QROWS + QROWS - 1) / KV_TILE + 1; if (lim < ntiles) ntiles = lim; }
+  // SEG: the first key each query row may see, and the first KV tile any row of the workgroup needs (every wave computes the same)
+  int t0 = 0, qseg[QSUB];
+  if constexpr (SEG) {
+    int mn = L;
+    for (int i = lane; i < QROWS; i += 64) mn = min(mn, seg[(long)b * L + min(qt * QROWS + i, L - 1)]);
+    t0 = min(wave_min_i(mn) / KV_TILE, ntiles - 1);
+#pragma unroll
+    for (int sub = 0; sub < QSUB; ++sub) qseg[sub] = seg[(long)b * L + min(q0 + sub * 16 + l15, L - 1)];
+  }
 
   RowStage<HD> ks_reg; ColStage<HD> vs_reg; int mk_reg = 1;
-  ks_reg.load(Kb, lay.k_rs, 0, L, tid);
-  vs_reg.load(Vb, lay.v_rs, 0, tid, valign & 3);
-  if (kmask && tid < 64) mk_reg = (tid < L) ? kmask[(long)b * L + tid] : 0;
+  ks_reg.load(Kb, lay.k_rs, t0 * KV_TILE, L, tid);
+  vs_reg.load(Vb, lay.v_rs, t0 * KV_TILE, tid, valign & 3);
+  if (kmask && tid < 64) mk_reg = (t0 * KV_TILE + tid < L) ? kmask[(long)b * L + t0 * KV_TILE + tid] : 0;
 
   // The tile body exists twice: MASKED = false has no masking code at all (the compiler otherwise hoists the index
   // compares of the masked path in front of the branch: ~40 VALU per tile in a VALU-bound loop), MASKED = true is the
@@ -295,6 +321,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
             bool v = key < L;
             if (CAUSAL) v = v & (key <= qrow);
             if (kmask) v = v & (mkv[r] != 0);
+            if constexpr (SEG) v = v & (key >= qseg[sub]);
             s[sub][kt][r] = v ? s[sub][kt][r] : -INFINITY;
           }
         }
@@ -340,8 +367,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
   if (CAUSAL) nfull = min(nfull, (qt * QROWS) / KV_TILE);      // keys of tiles below the first query row of the workgroup
   nfull = min(nfull, ntiles);
   if (valign & 4) nfull = 0;                                   // experiment (TA355_ATTN_NOPEEL=1): every tile takes the general body
-  for (int t = 0; t < nfull; ++t) tile(t, std::false_type{});
-  for (int t = nfull; t < ntiles; ++t) tile(t, std::true_type{});
+  if constexpr (SEG) {                                          // every tile from the first one needed takes the general body
+    for (int t = t0; t < ntiles; ++t) tile(t, std::true_type{});
+  } else {
+    for (int t = 0; t < nfull; ++t) tile(t, std::false_type{});
+    for (int t = nfull; t < ntiles; ++t) tile(t, std::true_type{});
+  }
 #pragma unroll
   for (int sub = 0; sub < QSUB; ++sub) {
     const int qrow = q0 + sub * 16 + l15;
@@ -579,14 +610,14 @@ constexpr int BWD_BUF = 2 * 64 * 128 * 2 + 512;      // one staging buffer of th
 // NORM / ROPE (compile-time, chosen by the host per layer; <true, true> = Qwen3): NORM = false is a decoder without q_norm / k_norm
 // (SmolLM3, Llama; TF:models/smollm3/modeling_smollm3.py:174-250) -- q and k go to RoPE unscaled, rq / rk are not written; ROPE = false
 // is a NoPE layer (use_rope false there) -- no rotation and none of its table loads.  With neither, K stays as the DMA left it.
-template <int HD, int MAXT, int QSUB, int NW, bool PAIR = false, bool NORM = true, bool ROPE = true>
+template <int HD, int MAXT, int QSUB, int NW, bool PAIR = false, bool NORM = true, bool ROPE = true, bool SEG = false>
 __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t* __restrict__ qkv0, const float* __restrict__ qn_w,
                                                                const float* __restrict__ kn_w, const float* __restrict__ cosT,
                                                                const float* __restrict__ sinT, const int* __restrict__ pos,
                                                                bf16_t* __restrict__ Qo, bf16_t* __restrict__ Ko, bf16_t* __restrict__ Vo,
                                                                float* __restrict__ rq, float* __restrict__ rk, bf16_t* __restrict__ O,
                                                                float* __restrict__ LSE, const int* __restrict__ kmask, int B, int Hq,
-                                                               int Hkv, int L, float scale, float eps) {
+                                                               int Hkv, int L, float scale, float eps, const int* __restrict__ seg) {
   static_assert(HD == 128, "Qwen3 head_dim");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ND = HD / 16, NT_ = NW * 64;
@@ -785,8 +816,19 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
 #pragma unroll
   for (int sub = 0; sub < QSUB; ++sub) m_run[sub] = NEG_BIG;
   const int my_tiles = min(ntiles, (q0 + (PAIR ? 16 : 16 * QSUB) - 1) / KV_TILE + 1);      // causal: keys beyond the wave's last query never count
+  // SEG: the first key of each row's segment; tiles that end before the smallest of them hold nothing this wave may see
+  int qseg[QSUB], t_first = 0;
+  if constexpr (SEG) {
+    int mn = L;
+#pragma unroll
+    for (int sub = 0; sub < QSUB; ++sub) {
+      qseg[sub] = seg[(long)b * L + min(q0 + sub * RSTEP + l15, L - 1)];
+      mn = min(mn, qseg[sub]);
+    }
+    t_first = wave_min_i(mn) / KV_TILE;
+  }
   ATTN_STAMP(blockIdx.x + 6144, 5 + 3 * pass, 0);                                   // wave 0: queries staged (pass 0: 1 tile, pass 1: 3 tiles)
-  for (int t = 0; t < my_tiles; ++t) {
+  for (int t = t_first; t < my_tiles; ++t) {
     const int key0 = t * KV_TILE;
     const char* Kt = Ks + t * RowTile<HD>::BYTES;
     const char* Vt = Vs + t * RowTile<HD>::BYTES;
@@ -807,7 +849,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
 #pragma unroll
     for (int sub = 0; sub < QSUB; ++sub) {
       const int qrow = q0 + sub * RSTEP + l15;
-      const bool full = (key0 + KV_TILE <= L) && (kmask == nullptr) && (key0 + KV_TILE - 1 <= q0 + sub * RSTEP);
+      const bool full = !SEG && (key0 + KV_TILE <= L) && (kmask == nullptr) && (key0 + KV_TILE - 1 <= q0 + sub * RSTEP);
       if (!full) {
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
@@ -816,7 +858,8 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = key0 + kt * 16 + g * 4 + r;
-            const bool v = (key <= qrow) & (mkv[r] != 0);
+            bool v = (key <= qrow) & (mkv[r] != 0);
+            if constexpr (SEG) v = v & (key >= qseg[sub]);
             s[sub][kt][r] = v ? s[sub][kt][r] : -INFINITY;
           }
         }
@@ -992,13 +1035,14 @@ __device__ __forceinline__ void qkv_post_bwd_tile(const char* st, const QkvPostB
 
 // ============================================================================ backward: dQ
 // grid (q tiles, Hq, B).  dQ^T[d,q] = sum_key K^T[d,key] dS^T[key,q],  dS = P o (dP - Delta) * scale
-template <int HD, bool CAUSAL, bool NORM, bool ROPE>
+template <int HD, bool CAUSAL, bool NORM, bool ROPE, bool SEG>
 __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                  const bf16_t* __restrict__ V, const bf16_t* __restrict__ KT,
                                                  const bf16_t* __restrict__ dO, long dO_stride,
                                                  const float* __restrict__ LSE, const float* __restrict__ Delta,
                                                  const int* __restrict__ kmask, bf16_t* __restrict__ dQ,
-                                                 int B, int Hq, int Hkv, int L, int Lp, float scale, const QkvPostBwd& F) {
+                                                 int B, int Hq, int Hkv, int L, int Lp, float scale, const QkvPostBwd& F,
+                                                 const int* __restrict__ seg) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const int nq = (L + 63) / 64, grp = Hq / Hkv;
   int group, member;
@@ -1030,6 +1074,12 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
   for (int i = 0; i < HD / 16; ++i) dq[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
   int ntiles = (L + KV_TILE - 1) / KV_TILE;
   if (CAUSAL) { const int lim = qt + 1; if (lim < ntiles) ntiles = lim; }
+  // SEG: this row's first key, and the first KV tile any of the workgroup's 64 query rows needs
+  int qseg = 0, t0 = 0;
+  if constexpr (SEG) {
+    qseg = seg[(long)b * L + qr];
+    t0 = wave_min_i(seg[(long)b * L + min(qt * 64 + lane, L - 1)]) / KV_TILE;
+  }
   // Round 3: K / V tiles by DMA into a double buffer, the next tile issued before this tile's arithmetic (the kernel runs at
   // 2 waves per SIMD -- 216 VGPRs -- and load -> store -> barrier -> compute exposed the full fetch latency in every iteration)
   static_assert(HD == 128, "the DMA staging of the backward is written for head_dim 128");
@@ -1042,8 +1092,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
     if (tid < 64) { const int kk = t * KV_TILE + tid; pm = (kk < L) ? (kmask ? kmask[(long)b * L + kk] : 1) : 0; }
   };
   ATTN_STAMP(gridDim.x - 1 - blockIdx.x + 4096, 0, 0);   // (dq blocks are stamped from 4096 up, by their distance from the grid's end)
-  if (ntiles > 0) issue(0);
-  for (int t = 0; t < ntiles; ++t) {
+  if (ntiles > t0) issue(t0);
+  for (int t = t0; t < ntiles; ++t) {
     const int key0 = t * KV_TILE;
     char* Ks = smem + (t & 1) * BWD_BUF;
     char* Vs = Ks + RowTile<HD>::BYTES;
@@ -1051,7 +1101,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
     if (tid < 64) Ms[tid] = pm;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                   // tile t has landed; every wave is done with tile t - 1 (the other buffer)
-    if (t == 0) ATTN_STAMP(gridDim.x - 1 - blockIdx.x + 4096, 1, 0);
+    if (t == t0) ATTN_STAMP(gridDim.x - 1 - blockIdx.x + 4096, 1, 0);
     if (t + 1 < ntiles) issue(t + 1);
     f32x4 s[4], dp[4];
 #pragma unroll
@@ -1074,6 +1124,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
         const int key = key0 + kt * 16 + g * 4 + r;
         bool v = (mkv[r] != 0) && (qrow < L);
         if (CAUSAL) v = v && (key <= qrow);
+        if constexpr (SEG) v = v && (key >= qseg);
         const float p = v ? __builtin_amdgcn_exp2f(s[kt][r] * sl2 - lse2) : 0.f;
         s[kt][r] = p * (dp[kt][r] - delta) * scale;
       }
@@ -1117,7 +1168,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
 // ============================================================================ backward: dK, dV
 // grid (key tiles, Hkv, B); loops over the Hq/Hkv query heads of the group and over query tiles.
 //   dV^T[d,key] += dO^T[d,q] P[q,key]      dK^T[d,key] += Q^T[d,q] dS[q,key]
-template <int HD, bool CAUSAL, bool NORM, bool ROPE>
+template <int HD, bool CAUSAL, bool NORM, bool ROPE, bool SEG>
 __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ QT,
                                                   const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                   const bf16_t* __restrict__ dO, long dO_stride,
@@ -1125,7 +1176,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
                                                   const float* __restrict__ LSE, const float* __restrict__ Delta,
                                                   const int* __restrict__ kmask, bf16_t* __restrict__ dK,
                                                   bf16_t* __restrict__ dV, int B, int Hq, int Hkv, int L, int Lp,
-                                                  float scale, const QkvPostBwd& F) {
+                                                  float scale, const QkvPostBwd& F, const int* __restrict__ seg) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const int grp = Hq / Hkv;
   int group, kt_idx;
@@ -1148,8 +1199,15 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
   f32x4 dk[HD / 16], dv[HD / 16];
 #pragma unroll
   for (int i = 0; i < HD / 16; ++i) { dk[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  const int nq = (L + 63) / 64;
+  int nq = (L + 63) / 64;
   const int qt_begin = CAUSAL ? kt_idx : 0;
+  // SEG: one past the last query row that may see this key, and the query tiles behind the largest of them over the 64 keys are skipped
+  int kend = 0;
+  if constexpr (SEG) {
+    const int* seg_end = seg + (long)B * L;
+    kend = seg_end[(long)b * L + kr];
+    nq = min(nq, (wave_max_i(seg_end[(long)b * L + min(kt_idx * 64 + lane, L - 1)]) + 63) / 64);
+  }
   // Round 3: Q / dO tiles by DMA into a double buffer; the (head, query tile) pairs of this key tile form ONE sequence of
   // iterations, the next one's tiles are in flight while this one computes
   static_assert(HD == 128, "the DMA staging of the backward is written for head_dim 128");
@@ -1208,6 +1266,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
           const int q = q0 + qs * 16 + g * 4 + r;
           bool v = kvalid && (q < L);
           if (CAUSAL) v = v && (krow <= q);
+          if constexpr (SEG) v = v && (q < kend);
           const float p = v ? __builtin_amdgcn_exp2f(s[qs][r] * sl2 - lsv[r]) : 0.f;
           s[qs][r] = p;
           ds[qs][r] = p * (dp[qs][r] - dlv[r]) * scale;
@@ -1262,7 +1321,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
 // One launch for both halves of the backward: blocks [0, n_dkv) run the dK / dV body, the rest the dQ body.  The two
 // are independent (both only read Q, K, V, dO), so a single grid lets the dQ workgroups fill the CUs while the longer
 // dK / dV ones drain, without a second stream or a kernel boundary in between.  The heavier dK / dV blocks go first.
-template <int HD, bool CAUSAL, bool NORM = true, bool ROPE = true>      // NORM / ROPE: the fused epilogue's variant (qkv_post_bwd_tile)
+template <int HD, bool CAUSAL, bool NORM = true, bool ROPE = true, bool SEG = false>      // NORM / ROPE: the fused epilogue's variant (qkv_post_bwd_tile)
 __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ QT,
                                                        const bf16_t* __restrict__ K, const bf16_t* __restrict__ KT,
                                                        const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO, long dO_stride,
@@ -1270,12 +1329,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restri
                                                        const float* __restrict__ Delta, const int* __restrict__ kmask,
                                                        bf16_t* __restrict__ dQ, bf16_t* __restrict__ dK, bf16_t* __restrict__ dV,
                                                        int B, int Hq, int Hkv, int L, int Lp, float scale, int n_dkv,
-                                                       const QkvPostBwd F) {
+                                                       const QkvPostBwd F, const int* __restrict__ seg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if ((int)blockIdx.x < n_dkv)
-    attn_bwd_dkv_body<HD, CAUSAL, NORM, ROPE>(smem, blockIdx.x, Q, QT, K, V, dO, dO_stride, dOT, LSE, Delta, kmask, dK, dV, B, Hq, Hkv, L, Lp, scale, F);
+    attn_bwd_dkv_body<HD, CAUSAL, NORM, ROPE, SEG>(smem, blockIdx.x, Q, QT, K, V, dO, dO_stride, dOT, LSE, Delta, kmask, dK, dV, B, Hq, Hkv, L, Lp, scale, F, seg);
   else
-    attn_bwd_dq_body<HD, CAUSAL, NORM, ROPE>(smem, blockIdx.x - n_dkv, Q, K, V, KT, dO, dO_stride, LSE, Delta, kmask, dQ, B, Hq, Hkv, L, Lp, scale, F);
+    attn_bwd_dq_body<HD, CAUSAL, NORM, ROPE, SEG>(smem, blockIdx.x - n_dkv, Q, K, V, KT, dO, dO_stride, LSE, Delta, kmask, dQ, B, Hq, Hkv, L, Lp, scale, F, seg);
 }
 
 
@@ -1320,20 +1379,38 @@ extern "C" int ta_attention_fwd_ex(const void* Q, const void* K, const void* VT,
   dim3 grid(grouped_grid((Hq / Hkv) * ta_cdiv(L, 64 * qsub), B * Hkv)), blk(256);
 #define FWD(HD_, C_)                                                                                              \
   TA_LAUNCH((attn_fwd_kernel<HD_, C_, (HD_ == 64 ? 2 : 1)>), grid, blk, fwd_lds<HD_>(), st, (const bf16_t*)Q, (const bf16_t*)K, \
-                     (const bf16_t*)VT, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, Lp, scale, lay, valign)
+                     (const bf16_t*)VT, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, Lp, scale, lay, valign, (const int*)nullptr)
   if (head_dim == 64 && !causal) FWD(64, false);
   else if (head_dim == 64 && causal) FWD(64, true);
   else if (head_dim == 128 && causal) FWD(128, true);
   else if (head_dim == 128 && !causal) FWD(128, false);
   else return TA_ERR_ARG;
+#undef FWD
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// The LM's causal head_dim-128 forward over packed rows (seg: the table of ta_segment_table): the tiled kernel at every L -- a query
+// tile walks the KV tiles of its own segments only, so there is nothing for the resident-K/V form to share.  seg NULL = ta_attention_fwd.
+extern "C" int ta_attention_fwd_seg(const void* Q, const void* K, const void* VT, void* O, float* LSE, const int* kmask, const int* seg,
+                                    int B, int Hq, int Hkv, int L, int Lp, float scale, hipStream_t st) {
+  if (!seg) return ta_attention_fwd(Q, K, VT, O, LSE, kmask, B, Hq, Hkv, L, Lp, 128, 1, scale, st);
+  if (B <= 0 || L <= 0) return TA_OK;
+  if (Hkv <= 0 || Hq % Hkv || Lp % 64 || Lp < L || (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)VT) & 15)) return TA_ERR_ARG;
+  const long hd = 128;
+  const ta_attn_layout lay = {Hq * L * hd, L * hd, hd, Hkv * L * hd, L * hd, hd, Hkv * hd * Lp, hd * Lp, Lp};
+  dim3 grid(grouped_grid((Hq / Hkv) * ta_cdiv(L, 64), B * Hkv)), blk(256);
+  TA_LAUNCH((attn_fwd_kernel<128, true, 1, true>), grid, blk, fwd_lds<128>(), st, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)VT,
+            (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, Lp, scale, lay, 0, seg);
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
 
 static int attention_bwd_launch(const void* Q, const void* K, const void* V, const void* dO, long dO_stride, const float* LSE,
                                 const float* Delta, const int* kmask, void* dQ, void* dK, void* dV, int B, int Hq, int Hkv, int L,
-                                int Lp, int head_dim, int causal, float scale, const QkvPostBwd& F, hipStream_t st) {
-  if (!Delta) return TA_ERR_ARG;
+                                int Lp, int head_dim, int causal, float scale, const QkvPostBwd& F, hipStream_t st,
+                                const int* seg = nullptr) {
+  if (!Delta || (seg && !causal)) return TA_ERR_ARG;
   if (B <= 0 || L <= 0) return TA_OK;
   if (Hq % Hkv || Lp % 64 || Lp < L || head_dim != 128) return TA_ERR_ARG;
   constexpr int HD = 128;
@@ -1349,6 +1426,10 @@ static int attention_bwd_launch(const void* Q, const void* K, const void* V, con
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
+    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
     attr_done = true;
   }
   const int n_dq = grouped_grid((Hq / Hkv) * ta_cdiv(L, 64), B * Hkv), n_dkv = grouped_grid(ta_cdiv(L, 64), B * Hkv);
@@ -1359,8 +1440,14 @@ static int attention_bwd_launch(const void* Q, const void* K, const void* V, con
   const bf16_t* nul = nullptr;
 #define BWD(...)                                                                                                                    \
   TA_LAUNCH((attn_bwd_kernel<HD, __VA_ARGS__>), grid, blk, lds_kv, st, (const bf16_t*)Q, nul, (const bf16_t*)K, nul, (const bf16_t*)V, \
-            (const bf16_t*)dO, dO_stride, nul, LSE, Delta, kmask, (bf16_t*)dQ, (bf16_t*)dK, (bf16_t*)dV, B, Hq, Hkv, L, Lp, scale, n_dkv, F)
-  if (!causal) BWD(false);
+            (const bf16_t*)dO, dO_stride, nul, LSE, Delta, kmask, (bf16_t*)dQ, (bf16_t*)dK, (bf16_t*)dV, B, Hq, Hkv, L, Lp, scale, n_dkv, F, seg)
+  if (seg) {                                         // packed rows: the same four epilogue variants, segment-aware
+    if (norm && rope) BWD(true, true, true, true);
+    else if (norm) BWD(true, true, false, true);
+    else if (rope) BWD(true, false, true, true);
+    else BWD(true, false, false, true);
+  }
+  else if (!causal) BWD(false);
   else if (norm && rope) BWD(true);
   else if (norm) BWD(true, true, false);
   else if (rope) BWD(true, false, true);
@@ -1373,9 +1460,9 @@ static int attention_bwd_launch(const void* Q, const void* K, const void* V, con
 // ta_lm_qkv_post_fwd + ta_attention_fwd in one launch for the LM's short causal sequences (head_dim 128, L <= 192, GQA group x
 // ceil(L / 32) <= 12): reads the pre-norm q | k | v GEMM output, writes O, LSE and the backward's operands (Q, K, V head-major,
 // rq, rk).  Returns TA_ERR_ARG when the shape is outside that envelope (callers fall back to the two-kernel path).
-extern "C" int ta_attention_fwd_qkv(const void* qkv0, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
+static int attention_fwd_qkv_launch(const void* qkv0, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
                                     const int* pos, void* Q, void* K, void* V, float* rq, float* rk, void* O, float* LSE,
-                                    const int* kmask, int B, int Hq, int Hkv, int L, float scale, float eps, hipStream_t st) {
+                                    const int* kmask, const int* seg, int B, int Hq, int Hkv, int L, float scale, float eps, hipStream_t st) {
   if (B <= 0 || L <= 0) return TA_OK;
   if (!qkv0 || !Q || !K || !O || Hkv <= 0 || Hq % Hkv) return TA_ERR_ARG;     // V may be NULL: no head-major copy of V
   if (!qn_w != !kn_w || !cosT != !sinT) return TA_ERR_ARG;      // both norm weights or neither (no q/k-norm); both tables or neither (NoPE)
@@ -1391,21 +1478,42 @@ extern "C" int ta_attention_fwd_qkv(const void* qkv0, const float* qn_w, const f
     FQ_ATTR(false); FQ_ATTR(true);
     FQ_ATTR(false, true, false); FQ_ATTR(true, true, false); FQ_ATTR(false, false, true); FQ_ATTR(true, false, true);
     FQ_ATTR(false, false, false); FQ_ATTR(true, false, false);
+    FQ_ATTR(false, true, true, true); FQ_ATTR(true, true, true, true);
+    FQ_ATTR(false, true, false, true); FQ_ATTR(true, true, false, true); FQ_ATTR(false, false, true, true); FQ_ATTR(true, false, true, true);
+    FQ_ATTR(false, false, false, true); FQ_ATTR(true, false, false, true);
     attr = true;
   }
 #undef FQ_ATTR
 #define FQ(...)                                                                                                                       \
   TA_LAUNCH((attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, __VA_ARGS__>), dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)qkv0, qn_w, kn_w, \
-            cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps)
+            cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps, seg)
   // groups of two (Qwen3 16 / 8): both heads of the group on the same 16 rows per wave (one fetch of the rows' cos / sin entries)
   const bool pair = grp == 2;
-  if (norm && rope) { if (pair) FQ(true); else FQ(false); }
+  if (seg) {                                         // packed rows: the same eight variants, segment-aware
+    if (norm && rope) { if (pair) FQ(true, true, true, true); else FQ(false, true, true, true); }
+    else if (norm) { if (pair) FQ(true, true, false, true); else FQ(false, true, false, true); }
+    else if (rope) { if (pair) FQ(true, false, true, true); else FQ(false, false, true, true); }
+    else { if (pair) FQ(true, false, false, true); else FQ(false, false, false, true); }
+  }
+  else if (norm && rope) { if (pair) FQ(true); else FQ(false); }
   else if (norm) { if (pair) FQ(true, true, false); else FQ(false, true, false); }
   else if (rope) { if (pair) FQ(true, false, true); else FQ(false, false, true); }
   else { if (pair) FQ(true, false, false); else FQ(false, false, false); }
 #undef FQ
   TA_CHECK_LAUNCH();
   return TA_OK;
+}
+extern "C" int ta_attention_fwd_qkv(const void* qkv0, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
+                                    const int* pos, void* Q, void* K, void* V, float* rq, float* rk, void* O, float* LSE,
+                                    const int* kmask, int B, int Hq, int Hkv, int L, float scale, float eps, hipStream_t st) {
+  return attention_fwd_qkv_launch(qkv0, qn_w, kn_w, cosT, sinT, pos, Q, K, V, rq, rk, O, LSE, kmask, nullptr, B, Hq, Hkv, L, scale, eps, st);
+}
+// ... over packed rows (seg: the table of ta_segment_table; NULL = ta_attention_fwd_qkv).  Same envelope, same outputs.
+extern "C" int ta_attention_fwd_qkv_seg(const void* qkv0, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
+                                        const int* pos, void* Q, void* K, void* V, float* rq, float* rk, void* O, float* LSE,
+                                        const int* kmask, const int* seg, int B, int Hq, int Hkv, int L, float scale, float eps,
+                                        hipStream_t st) {
+  return attention_fwd_qkv_launch(qkv0, qn_w, kn_w, cosT, sinT, pos, Q, K, V, rq, rk, O, LSE, kmask, seg, B, Hq, Hkv, L, scale, eps, st);
 }
 
 extern "C" int ta_attention_bwd(const void* Q, const void* QT, const void* K, const void* KT, const void* V,
@@ -1428,4 +1536,21 @@ extern "C" int ta_attention_bwd_qkv(const void* Q, const void* K, const void* V,
   QkvPostBwd F = {(const bf16_t*)qkv0, rq, rk, qn_w, kn_w, cosT, sinT, pos, (bf16_t*)dqkv};
   return attention_bwd_launch(Q, K, V, dO, dO_stride, LSE, Delta, kmask, nullptr, nullptr, nullptr, B, Hq, Hkv, L, Lp, head_dim, causal,
                               scale, F, st);
+}
+
+// The two backward entry points over packed rows (seg: the table of ta_segment_table, NULL = the plain call); causal, head_dim 128.
+extern "C" int ta_attention_bwd_seg(const void* Q, const void* K, const void* V, const void* dO, long dO_stride, const float* LSE,
+                                    const float* Delta, const int* kmask, const int* seg, void* dQ, void* dK, void* dV, int B, int Hq,
+                                    int Hkv, int L, int Lp, float scale, hipStream_t st) {
+  QkvPostBwd F = {};
+  return attention_bwd_launch(Q, K, V, dO, dO_stride, LSE, Delta, kmask, dQ, dK, dV, B, Hq, Hkv, L, Lp, 128, 1, scale, F, st, seg);
+}
+extern "C" int ta_attention_bwd_qkv_seg(const void* Q, const void* K, const void* V, const void* dO, long dO_stride, const float* LSE,
+                                        const float* Delta, const int* kmask, const int* seg, const void* qkv0, const float* rq,
+                                        const float* rk, const float* qn_w, const float* kn_w, const float* cosT, const float* sinT,
+                                        const int* pos, void* dqkv, int B, int Hq, int Hkv, int L, int Lp, float scale, hipStream_t st) {
+  if (!qkv0 || !dqkv || !qn_w != !kn_w || !cosT != !sinT || (qn_w && (!rq || !rk))) return TA_ERR_ARG;
+  QkvPostBwd F = {(const bf16_t*)qkv0, rq, rk, qn_w, kn_w, cosT, sinT, pos, (bf16_t*)dqkv};
+  return attention_bwd_launch(Q, K, V, dO, dO_stride, LSE, Delta, kmask, nullptr, nullptr, nullptr, B, Hq, Hkv, L, Lp, 128, 1, scale, F,
+                              st, seg);
 }

@@ -224,6 +224,55 @@ __global__ __launch_bounds__(1024) void audio_index_kernel(const long* __restric
     __syncthreads();
   }
 }
+// ---------------------------------------------------------------------------- sequence packing (several clips per LM row)
+// segment_ids [R, L]: 0 = padding, 1..S = the clips of the row, back to back.  One thread per token walks to the two ends of its
+// segment (rows are a few hundred tokens): seg_start = index of the segment's first token (q + 1 for padding: an empty key range),
+// seg_end = one past its last (k for padding), pos = distance from the first token -- the RoPE position, restarting in every clip.
+__global__ __launch_bounds__(256) void segment_table_kernel(const int* __restrict__ sid, int* __restrict__ seg_start,
+                                                            int* __restrict__ seg_end, int* __restrict__ pos, int R, int L) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= (long)R * L) return;
+  const int l = (int)(p % L);
+  const int* row = sid + (p - l);
+  const int s = row[l];
+  int a = l, e = l + 1;
+  if (s == 0) { a = l + 1; e = l; }
+  else {
+    while (a > 0 && row[a - 1] == s) --a;
+    while (e < L && row[e] == s) ++e;
+  }
+  seg_start[p] = a;
+  seg_end[p] = e;
+  if (pos) pos[p] = s == 0 ? 0 : l - a;
+}
+// The placeholder -> projector-row map of packed rows: clip c = the c-th segment, row-major over (row, segment); the j-th <audio>
+// token of segment c takes row c * N + j of the projector output while j < counts[c] and j < N, and -2 (a zero row) beyond -- what
+// ta_audio_index does with the surplus placeholders of a clip.  Everything else, padding included: -1.  One block per row.
+__global__ __launch_bounds__(256) void audio_index_seg_kernel(const long* __restrict__ ids, const int* __restrict__ sid,
+                                                              const long* __restrict__ counts, int* __restrict__ src_row, int R, int L,
+                                                              int C_, int N, long audio_id) {
+  __shared__ int clip0;
+  const int r = blockIdx.x;
+  if (threadIdx.x == 0) {                           // segments in the rows above = the largest id of each (ids are gap-free)
+    int c = 0;
+    for (int i = 0; i < r; ++i) { int m = 0; for (int l = 0; l < L; ++l) m = max(m, sid[(long)i * L + l]); c += m; }
+    clip0 = c;
+  }
+  __syncthreads();
+  const int* srow = sid + (long)r * L;
+  const long* irow = ids + (long)r * L;
+  for (int l = threadIdx.x; l < L; l += 256) {
+    int out = -1;
+    const int s = srow[l];
+    if (s > 0 && irow[l] == audio_id) {
+      int j = 0;
+      for (int k = l - 1; k >= 0 && srow[k] == s; --k) j += irow[k] == audio_id;
+      const int c = clip0 + s - 1;
+      out = (c < C_ && j < N && j < counts[c]) ? c * N + j : -2;
+    }
+    src_row[(long)r * L + l] = out;
+  }
+}
 // x0[p,:] = src_row[p] >= 0 ? audio[src_row[p],:] : (src_row[p] == -2 ? 0 : emb[ids[p],:])     (f32, D % 4 == 0)
 __global__ __launch_bounds__(256) void embed_scatter_kernel(const long* __restrict__ ids, const int* __restrict__ src_row,
                                                             const float* __restrict__ emb, const float* __restrict__ audio,
@@ -342,6 +391,20 @@ extern "C" int ta_audio_index(const long* ids, const long* counts, int* src_row,
   if (B <= 0 || L <= 0) return TA_OK;
   if (B > 1024) return TA_ERR_ARG;
   TA_LAUNCH(audio_index_kernel, dim3(1), dim3(1024), 0, st, ids, counts, src_row, B, L, N, audio_id);
+  TA_CHECK_LAUNCH(); return TA_OK;
+}
+extern "C" int ta_segment_table(const int* segment_ids, int* seg, int* pos, int R, int L, hipStream_t st) {
+  if (R <= 0 || L <= 0) return TA_OK;
+  if (!segment_ids || !seg) return TA_ERR_ARG;
+  const long n = (long)R * L;
+  TA_LAUNCH(segment_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, segment_ids, seg, seg + n, pos, R, L);
+  TA_CHECK_LAUNCH(); return TA_OK;
+}
+extern "C" int ta_audio_index_seg(const long* ids, const int* segment_ids, const long* counts, int* src_row, int R, int L, int C,
+                                  int N, long audio_id, hipStream_t st) {
+  if (R <= 0 || L <= 0) return TA_OK;
+  if (!ids || !segment_ids || !counts || !src_row || C < 0) return TA_ERR_ARG;
+  TA_LAUNCH(audio_index_seg_kernel, dim3(R), dim3(256), 0, st, ids, segment_ids, counts, src_row, R, L, C, N, audio_id);
   TA_CHECK_LAUNCH(); return TA_OK;
 }
 extern "C" int ta_embed_scatter(const long* ids, const int* src_row, const float* emb, const float* audio, float* x0,

@@ -522,9 +522,11 @@ class Qwen3MI355X(torch.nn.Module):
 
     # ------------------------------------------------------------------ raw forward / backward (no autograd)
     def forward_loss(self, input_ids, src_row, audio, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-                     want_logits=False, pos=None, lora_dropout=None):
+                     want_logits=False, pos=None, lora_dropout=None, seg=None):
         """Returns (loss[1] f32, nll[n] f32, logits or None, ctx) -- ctx feeds ``backward_from_ctx``.
-        ``lora_dropout``: (p, seed, offset) of ``next_lora_dropout()`` or None; kept in ctx for the backward."""
+        ``lora_dropout``: (p, seed, offset) of ``next_lora_dropout()`` or None; kept in ctx for the backward.
+        ``seg``: int32 [2, B*L], the table of ``ops.segment_table`` for packed rows (several clips per row, block-diagonal
+        attention), or None; kept in ctx for the backward too."""
         if self._w is None:
             raise _lib.Ta355Error("LM weights not loaded")
         L_ = _lib.lib()
@@ -540,7 +542,14 @@ class Qwen3MI355X(torch.nn.Module):
         nll = torch.empty(max(n_label_rows, 1), device=dev, dtype=F32)
         logits = torch.empty((B * L, self.vocab_pad), device=dev, dtype=BF16) if want_logits else None
         drop = _lora_drop_desc(lora_dropout)
-        if drop is None:
+        if seg is not None:
+            if seg.dtype != torch.int32 or seg.numel() != 2 * B * L or not seg.is_contiguous():
+                raise ValueError(f"seg must be a contiguous int32 [2, {B * L}] segment table; got {seg.dtype} {tuple(seg.shape)}")
+            _lib.check(L_.ta_lm_forward_loss_seg(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos), ptr(seg),
+                                                 B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
+                                                 ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(),
+                                                 None if drop is None else C.byref(drop), stream()), "ta_lm_forward_loss_seg")
+        elif drop is None:
             _lib.check(L_.ta_lm_forward_loss(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos),
                                              B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
                                              ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), stream()),
@@ -551,7 +560,7 @@ class Qwen3MI355X(torch.nn.Module):
                                                 ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), C.byref(drop), stream()),
                        "ta_lm_forward_loss_ex")
         ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
-                   n_label_rows=n_label_rows, ids=input_ids, lora_dropout=lora_dropout)
+                   n_label_rows=n_label_rows, ids=input_ids, lora_dropout=lora_dropout, seg=seg)
         # The tape's residual-stream rows are in the storage dtype this handle carried NOW: the backward must read them as that even
         # if the owner flips ``res_f32`` in between.  Keyed by the tape's address, since the custom operator hands the backward only
         # tensors.
@@ -601,7 +610,14 @@ class Qwen3MI355X(torch.nn.Module):
             w = _lib.LmWeights.from_buffer_copy(self._w)          # same pointers, the modes the forward ran in
             w.res_f32, w.dx_f32 = recorded
         drop = _lora_drop_desc(ctx.get("lora_dropout"))       # the descriptor its forward ran with
-        if drop is None:
+        if ctx.get("seg") is not None:                        # ... and the segment table
+            _lib.check(_lib.lib().ta_lm_backward_seg(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]), ptr(ctx["seg"]),
+                                                     ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
+                                                     ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
+                                                     None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
+                                                     ptr(ctx["ws"]), ctx["ws"].numel(), None if drop is None else C.byref(drop), stream()),
+                       "ta_lm_backward_seg")
+        elif drop is None:
             _lib.check(_lib.lib().ta_lm_backward(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]),
                                                  ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
                                                  ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
@@ -770,10 +786,14 @@ class FrozenLMLoss:
 
     @staticmethod
     def apply(audio_embeds, lm, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-              want_logits, *trainable, pos=None):
+              want_logits, *trainable, pos=None, seg=None):
         from . import torch_ops
         drop = lm.next_lora_dropout()                 # training forwards of a p > 0 model only: a fresh Philox offset each
-        if drop is None:
+        if seg is not None:                           # packed rows: one operator pair, with or without dropout (p = 0: off)
+            loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss_seg(
+                audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
+                int(n_label_rows), float(loss_scale), bool(want_logits), pos, seg, *(drop or (0.0, 0, 0)))
+        elif drop is None:
             loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss(
                 audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
                 int(n_label_rows), float(loss_scale), bool(want_logits), pos)

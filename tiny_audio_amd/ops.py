@@ -329,6 +329,25 @@ def audio_index(ids, counts, N, audio_id):
     return src
 
 
+def segment_table(segment_ids):
+    """segment_ids int32 [R, L] (0 = padding, 1..S the clips of a packed row) -> (seg int32 [2, R*L]: first key index / one past the
+    last row of every token's segment, pos int32 [R*L]: positions restarting at 0 in every segment).  See include/ta355.h."""
+    R, L = segment_ids.shape
+    seg = torch.empty((2, R * L), device=segment_ids.device, dtype=torch.int32)
+    pos = torch.empty(R * L, device=segment_ids.device, dtype=torch.int32)
+    check(lib().ta_segment_table(ptr(segment_ids), ptr(seg), ptr(pos), R, L, stream()), "ta_segment_table")
+    return seg, pos
+
+
+def audio_index_seg(ids, segment_ids, counts, N, audio_id):
+    """``audio_index`` for packed rows: clip c (row of ``counts``) is the c-th segment, row-major over (row, segment)."""
+    R, L = ids.shape
+    src = torch.empty(R * L, device=ids.device, dtype=torch.int32)
+    check(lib().ta_audio_index_seg(ptr(ids), ptr(segment_ids), ptr(counts), ptr(src), R, L, int(counts.numel()), N, audio_id, stream()),
+          "ta_audio_index_seg")
+    return src
+
+
 def label_rows(labels):
     B, L = labels.shape
     rows = torch.empty(B * L, device=labels.device, dtype=torch.int32)

@@ -494,5 +494,74 @@ def _lm_drop_bwd(ctx, g_loss, _g_nll, _g_logits, _g_tape, _g_ws):
 
 lm_forward_loss_drop.register_autograd(_lm_drop_bwd, setup_context=_lm_drop_setup)
 
+# ---- the same pair over packed rows (sequence packing): ``seg`` int32 [2, B*L] is the table of ops.segment_table.  One pair serves
+# both dropout settings -- lora_p == 0 is "no dropout", the library's _seg entry points take an optional descriptor.
+@torch.library.custom_op("ta355::lm_forward_loss_seg", mutates_args=())
+def lm_forward_loss_seg(audio: Tensor, trainable: Sequence[Tensor], handle: int, input_ids: Tensor, src_row: Optional[Tensor],
+                        kmask: Optional[Tensor], label_rows: Optional[Tensor], label_targets: Optional[Tensor], n_label_rows: int,
+                        loss_scale: float, want_logits: bool, pos: Optional[Tensor], seg: Tensor, lora_p: float, lora_seed: int,
+                        lora_offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """``lm_forward_loss`` with block-diagonal attention inside every row."""
+    lm = module_of(handle)
+    a = audio.detach().to(F32).contiguous()
+    loss, nll, logits, c = lm.forward_loss(input_ids, src_row, a, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits,
+                                           pos=pos, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg)
+    return loss.reshape(()), nll, (logits if logits is not None else _empty(a.device)), c["tape"], c["ws"]
+
+
+@lm_forward_loss_seg.register_fake
+def _(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits, pos, seg,
+      lora_p, lora_seed, lora_offset):
+    return _lm_fwd_fake(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
+                        want_logits, pos)
+
+
+@torch.library.custom_op("ta355::lm_backward_seg", mutates_args=())
+def lm_backward_seg(tape: Tensor, ws: Tensor, handle: int, input_ids: Tensor, src_row: Optional[Tensor], kmask: Optional[Tensor],
+                    label_rows: Optional[Tensor], n_label_rows: int, n_audio_rows: int, want_d_audio: bool,
+                    pos: Optional[Tensor], seg: Tensor, lora_p: float, lora_seed: int, lora_offset: int) -> List[Tensor]:
+    """``lm_backward`` of a ``lm_forward_loss_seg`` forward: the same table, the same (p, seed, offset)."""
+    lm = module_of(handle)
+    B, L = input_ids.shape
+    ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
+               n_label_rows=n_label_rows, ids=input_ids, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg)
+    d_audio, _, lg = lm.backward_from_ctx(ctx, n_audio_rows, want_d_audio=want_d_audio)
+    dev = tape.device
+    out = [d_audio if d_audio is not None else _empty(dev)]
+    for g in (lg or []):
+        out.append(g if g is not None else _empty(dev))
+    return out
+
+
+@lm_backward_seg.register_fake
+def _(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos, seg, lora_p, lora_seed,
+      lora_offset):
+    return _lm_bwd_fake(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos)
+
+
+def _lm_seg_setup(ctx, inputs, output):
+    _lm_setup(ctx, inputs[:12], output)
+    ctx.drop = tuple(inputs[13:16])
+    src_row, kmask, label_rows, pos = inputs[4], inputs[5], inputs[6], inputs[11]
+    ctx.save_for_backward(output[3], output[4], inputs[3], inputs[12], *[t for t in (src_row, kmask, label_rows, pos) if t is not None])
+
+
+def _lm_seg_bwd(ctx, g_loss, _g_nll, _g_logits, _g_tape, _g_ws):
+    if g_loss is None:
+        return (None, [None] * ctx.n_train) + (None,) * 14
+    tape, ws, ids, seg, *rest = ctx.saved_tensors
+    it = iter(rest)
+    src_row, kmask, label_rows, pos = (next(it) if p else None for p in ctx.present)
+    out = torch.ops.ta355.lm_backward_seg(tape, ws, ctx.handle, ids, src_row, kmask, label_rows, ctx.n_label_rows, ctx.n_audio,
+                                          ctx.want_d_audio, pos, seg, *ctx.drop)
+    d_audio = out[0] * g_loss if ctx.want_d_audio else None
+    tg = [(g * g_loss if g.numel() else None) for g in out[1:]]
+    tg += [None] * (ctx.n_train - len(tg))
+    return (d_audio, tg[: ctx.n_train]) + (None,) * 14
+
+
+lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
+
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
-             "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward")
+             "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
+             "lm_forward_loss_seg", "lm_backward_seg")
