@@ -326,9 +326,6 @@ def test_segment_table_against_a_loop():
 # ============================================================================ 4. padded query rows
 def test_padding_rows_are_finite_and_take_no_gradient():
     """Attention backward alone on the row that ends in padding: dK / dV of padding keys exactly zero, outputs finite."""
-    import ctypes as C
-    from tiny_audio_amd import _lib
-    from tiny_audio_amd.ops import ptr, stream
     B, Hq, Hkv, L, hd = 1, 4, 2, 192, 128
     g = torch.Generator(device=DEV); g.manual_seed(3)
     rn = lambda *s: torch.randn(*s, device=DEV, generator=g).to(torch.bfloat16)
@@ -337,15 +334,12 @@ def test_padding_rows_are_finite_and_take_no_gradient():
     seg, _ = ops.segment_table(sid)
     km = (sid != 0).int().contiguous()
     VT = V.transpose(2, 3).contiguous()
-    O = torch.empty((B * L, Hq * hd), device=DEV, dtype=torch.bfloat16)
-    lse = torch.empty((B, Hq, L), device=DEV)
-    L_ = _lib.lib()
     sc = hd ** -0.5
-    _lib.check(L_.ta_attention_fwd_seg(ptr(Q), ptr(K), ptr(VT), ptr(O), ptr(lse), ptr(km), ptr(seg), B, Hq, Hkv, L, L, sc, stream()))
+    O = torch.full((B * L, Hq * hd), 7.0, device=DEV, dtype=torch.bfloat16)        # pre-filled: a row nobody writes keeps its 7s
+    O, lse = ops.attention_fwd_seg(Q, K, VT, L, sc, kmask=km, seg=seg, out=O)
     delta = (O.float() * dO.float()).reshape(L, Hq, hd).sum(-1).t().contiguous().reshape(B, Hq, L)
     dQ, dK, dV = torch.full_like(Q, 7), torch.full_like(K, 7), torch.full_like(V, 7)
-    _lib.check(L_.ta_attention_bwd_seg(ptr(Q), ptr(K), ptr(V), ptr(dO), Hq * hd, ptr(lse), ptr(delta), ptr(km), ptr(seg), ptr(dQ), ptr(dK),
-                                       ptr(dV), B, Hq, Hkv, L, L, sc, stream()))
+    ops.attention_bwd_seg(Q, K, V, dO, lse, delta, L, sc, kmask=km, seg=seg, out=(dQ, dK, dV))
     torch.cuda.synchronize()
     assert torch.isfinite(O.float()).all() and torch.isfinite(dQ.float()).all()
     assert not O[140:].float().any() and not dQ[:, :, 140:].float().any()

@@ -169,11 +169,19 @@ def pad64(n):
     return (n + 63) // 64 * 64
 
 
-def attention_fwd(Q, K, VT, L, causal, scale, kmask=None, want_lse=True):
-    """Q [B,Hq,L,hd], K [B,Hkv,L,hd], VT [B,Hkv,hd,Lp] bf16 -> O [B*L, Hq*hd] bf16, LSE [B,Hq,L]."""
+def _out(out, shape, device, dtype=BF16):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype
+    return _req(out)
+
+
+def attention_fwd(Q, K, VT, L, causal, scale, kmask=None, want_lse=True, out=None):
+    """Q [B,Hq,L,hd], K [B,Hkv,L,hd], VT [B,Hkv,hd,Lp] bf16 -> O [B*L, Hq*hd] bf16, LSE [B,Hq,L].  ``out``: the tensor to write O
+    into (here and in the wrappers below: a caller that wants to see which rows a kernel wrote passes its own, pre-filled)."""
     B, Hq, _, hd = Q.shape
     Hkv, Lp = K.shape[1], VT.shape[3]
-    O = torch.empty((B * L, Hq * hd), device=Q.device, dtype=BF16)
+    O = _out(out, (B * L, Hq * hd), Q.device)
     lse = torch.empty((B, Hq, L), device=Q.device, dtype=F32) if want_lse else None
     check(lib().ta_attention_fwd(ptr(Q), ptr(K), ptr(VT), ptr(O), ptr(lse), ptr(kmask), B, Hq, Hkv, L, Lp, hd,
                                  int(causal), scale, stream()), "ta_attention_fwd")
@@ -191,10 +199,17 @@ def attention_fwd_strided(Q, K, VT, B, Hq, Hkv, L, hd, causal, scale, layout, km
     return O
 
 
-def attention_bwd(Q, QT, K, KT, V, dO, dOT, lse, delta, L, causal, scale, kmask=None):
+def _out3(out, Q, K, V):
+    if out is None:
+        return torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    return tuple(_out(o, t.shape, t.device) for o, t in zip(out, (Q, K, V)))
+
+
+def attention_bwd(Q, QT, K, KT, V, dO, dOT, lse, delta, L, causal, scale, kmask=None, out=None):
+    """QT / KT / dOT: the transposed images the library no longer reads (None is fine).  ``out``: (dQ, dK, dV) to write into."""
     B, Hq, _, hd = Q.shape
-    Hkv, Lp = K.shape[1], KT.shape[3]
-    dQ = torch.empty_like(Q); dK = torch.empty_like(K); dV = torch.empty_like(V)
+    Hkv, Lp = K.shape[1], (pad64(L) if KT is None else KT.shape[3])
+    dQ, dK, dV = _out3(out, Q, K, V)
     check(lib().ta_attention_bwd(ptr(Q), ptr(QT), ptr(K), ptr(KT), ptr(V), ptr(dO), dO.shape[-1], ptr(dOT), ptr(lse),
                                  ptr(delta), ptr(kmask), ptr(dQ), ptr(dK), ptr(dV), B, Hq, Hkv, L, Lp, hd, int(causal),
                                  scale, stream()), "ta_attention_bwd")
@@ -211,27 +226,65 @@ def attention_enc_fwd(qkv, B, heads, S):
     return out
 
 
-def attention_fwd_qkv(qkv0, qn_w, kn_w, cosT, sinT, B, Hq, Hkv, L, scale, eps=1e-6, kmask=None, pos=None):
-    """ta_lm_qkv_post_fwd + ta_attention_fwd in one launch (short causal sequences): returns O, LSE, Q, K, V, rq, rk."""
+def attention_fwd_seg(Q, K, VT, L, scale, kmask=None, seg=None, want_lse=True, out=None):
+    """ta_attention_fwd_seg: the causal head_dim-128 forward over packed rows (``seg``: the table of ``segment_table``; None = the
+    plain causal ``attention_fwd``).  Shapes as ``attention_fwd``."""
+    B, Hq, _, hd = Q.shape
+    Hkv, Lp = K.shape[1], VT.shape[3]
+    assert hd == 128
+    O = _out(out, (B * L, Hq * hd), Q.device)
+    lse = torch.empty((B, Hq, L), device=Q.device, dtype=F32) if want_lse else None
+    check(lib().ta_attention_fwd_seg(ptr(Q), ptr(K), ptr(VT), ptr(O), ptr(lse), ptr(kmask), ptr(seg), B, Hq, Hkv, L, Lp, scale,
+                                     stream()), "ta_attention_fwd_seg")
+    return O, lse
+
+
+def attention_bwd_seg(Q, K, V, dO, lse, delta, L, scale, kmask=None, seg=None, out=None):
+    """ta_attention_bwd_seg: the causal head_dim-128 backward over packed rows (``seg`` None = the plain causal call).
+    ``out``: (dQ, dK, dV) to write into."""
+    B, Hq, _, hd = Q.shape
+    Hkv, Lp = K.shape[1], pad64(L)
+    dQ, dK, dV = _out3(out, Q, K, V)
+    check(lib().ta_attention_bwd_seg(ptr(Q), ptr(K), ptr(V), ptr(dO), dO.shape[-1], ptr(lse), ptr(delta), ptr(kmask), ptr(seg), ptr(dQ),
+                                     ptr(dK), ptr(dV), B, Hq, Hkv, L, Lp, scale, stream()), "ta_attention_bwd_seg")
+    return dQ, dK, dV
+
+
+def attention_fwd_qkv(qkv0, qn_w, kn_w, cosT, sinT, B, Hq, Hkv, L, scale, eps=1e-6, kmask=None, pos=None, seg=None, out=None):
+    """ta_lm_qkv_post_fwd + ta_attention_fwd in one launch (short causal sequences): returns O, LSE, Q, K, V, rq, rk.
+    qn_w / kn_w None: no q/k-norm (rq / rk are not written); cosT / sinT None: a NoPE layer; ``seg``: packed rows (the table of
+    ``segment_table``), dispatching to ta_attention_fwd_qkv_seg."""
     hd, dev = 128, qkv0.device
     mk = lambda h: torch.empty((B, h, L, hd), device=dev, dtype=BF16)
     Q, K, V = mk(Hq), mk(Hkv), mk(Hkv)
     rq = torch.empty((B * L, Hq), device=dev, dtype=F32); rk = torch.empty((B * L, Hkv), device=dev, dtype=F32)
-    O = torch.empty((B * L, Hq * hd), device=dev, dtype=BF16)
+    O = _out(out, (B * L, Hq * hd), dev)
     lse = torch.empty((B, Hq, L), device=dev, dtype=F32)
-    check(lib().ta_attention_fwd_qkv(ptr(qkv0), ptr(qn_w), ptr(kn_w), ptr(cosT), ptr(sinT), ptr(pos), ptr(Q), ptr(K), ptr(V), ptr(rq),
-                                     ptr(rk), ptr(O), ptr(lse), ptr(kmask), B, Hq, Hkv, L, scale, eps, stream()), "ta_attention_fwd_qkv")
+    if seg is None:
+        check(lib().ta_attention_fwd_qkv(ptr(qkv0), ptr(qn_w), ptr(kn_w), ptr(cosT), ptr(sinT), ptr(pos), ptr(Q), ptr(K), ptr(V), ptr(rq),
+                                         ptr(rk), ptr(O), ptr(lse), ptr(kmask), B, Hq, Hkv, L, scale, eps, stream()), "ta_attention_fwd_qkv")
+    else:
+        check(lib().ta_attention_fwd_qkv_seg(ptr(qkv0), ptr(qn_w), ptr(kn_w), ptr(cosT), ptr(sinT), ptr(pos), ptr(Q), ptr(K), ptr(V), ptr(rq),
+                                             ptr(rk), ptr(O), ptr(lse), ptr(kmask), ptr(seg), B, Hq, Hkv, L, scale, eps, stream()),
+              "ta_attention_fwd_qkv_seg")
     return O, lse, Q, K, V, rq, rk
 
 
-def attention_bwd_qkv(Q, K, V, dO, lse, delta, qkv0, rq, rk, qn_w, kn_w, cosT, sinT, L, scale, kmask=None, pos=None):
-    """Causal GQA attention backward with the q|k|v post-processing backward in its epilogue: returns d(qkv0) token-major."""
+def attention_bwd_qkv(Q, K, V, dO, lse, delta, qkv0, rq, rk, qn_w, kn_w, cosT, sinT, L, scale, kmask=None, pos=None, seg=None, out=None):
+    """Causal GQA attention backward with the q|k|v post-processing backward in its epilogue: returns d(qkv0) token-major.
+    V None: the V rows are read in place from qkv0.  qn_w / kn_w / cosT / sinT None as in ``attention_fwd_qkv``; ``seg``: packed rows,
+    dispatching to ta_attention_bwd_qkv_seg."""
     B, Hq, _, hd = Q.shape
     Hkv, Lp = K.shape[1], pad64(L)
-    dqkv = torch.empty_like(qkv0)
-    check(lib().ta_attention_bwd_qkv(ptr(Q), ptr(K), ptr(V), ptr(dO), dO.shape[-1], ptr(lse), ptr(delta), ptr(kmask), ptr(qkv0),
-                                     ptr(rq), ptr(rk), ptr(qn_w), ptr(kn_w), ptr(cosT), ptr(sinT), ptr(pos), ptr(dqkv), B, Hq, Hkv,
-                                     L, Lp, hd, 1, scale, stream()), "ta_attention_bwd_qkv")
+    dqkv = _out(out, qkv0.shape, qkv0.device)
+    if seg is None:
+        check(lib().ta_attention_bwd_qkv(ptr(Q), ptr(K), ptr(V), ptr(dO), dO.shape[-1], ptr(lse), ptr(delta), ptr(kmask), ptr(qkv0),
+                                         ptr(rq), ptr(rk), ptr(qn_w), ptr(kn_w), ptr(cosT), ptr(sinT), ptr(pos), ptr(dqkv), B, Hq, Hkv,
+                                         L, Lp, hd, 1, scale, stream()), "ta_attention_bwd_qkv")
+    else:
+        check(lib().ta_attention_bwd_qkv_seg(ptr(Q), ptr(K), ptr(V), ptr(dO), dO.shape[-1], ptr(lse), ptr(delta), ptr(kmask), ptr(seg),
+                                             ptr(qkv0), ptr(rq), ptr(rk), ptr(qn_w), ptr(kn_w), ptr(cosT), ptr(sinT), ptr(pos), ptr(dqkv),
+                                             B, Hq, Hkv, L, Lp, scale, stream()), "ta_attention_bwd_qkv_seg")
     return dqkv
 
 
@@ -247,9 +300,9 @@ def lm_qkv_post_fwd(qkv0, qn_w, kn_w, cosT, sinT, B, Hq, Hkv, L, eps=1e-6, pos=N
     return Q, K, V, QT, KT, VT, rq, rk
 
 
-def lm_qkv_post_bwd(dQ, dK, dV, qkv0, rq, rk, qn_w, kn_w, cosT, sinT, B, Hq, Hkv, L, pos=None, dqn=None, dkn=None):
+def lm_qkv_post_bwd(dQ, dK, dV, qkv0, rq, rk, qn_w, kn_w, cosT, sinT, B, Hq, Hkv, L, pos=None, dqn=None, dkn=None, out=None):
     """dqn / dkn f32 [128]: += the q_norm / k_norm weight gradients (trainable LM)."""
-    dqkv = torch.empty_like(qkv0)
+    dqkv = _out(out, qkv0.shape, qkv0.device)
     check(lib().ta_lm_qkv_post_bwd(ptr(dQ), ptr(dK), ptr(dV), ptr(qkv0), ptr(rq), ptr(rk), ptr(qn_w), ptr(kn_w),
                                    ptr(cosT), ptr(sinT), ptr(pos), ptr(dqkv), ptr(dqn), ptr(dkn), B, Hq, Hkv, L, stream()),
           "ta_lm_qkv_post_bwd")
