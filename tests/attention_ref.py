@@ -234,24 +234,25 @@ def backward_model(qkv0, dO, B, L, Hq, Hkv, rounded=True, qn_w=None, kn_w=None, 
 
 
 # ----------------------------------------------------------------------------- the metric
-def rows_of(t):
-    """Any tensor whose last dimension is a multiple of HD -> float64 [rows, HD]: one (b, head, token) vector per row."""
+def rows_of(t, width=HD):
+    """Any tensor whose last dimension is a multiple of ``width`` -> float64 [rows, width].  Attention: width = HD, one (b, head, token)
+    vector per row; other users (tests/moe_ref.py) pass the row length of their own matrices."""
     t = t.detach().cpu().to(F64)
-    return t.reshape(-1, HD)
+    return t.reshape(-1, width)
 
 
-def row_errors(got, exact):
+def row_errors(got, exact, width=HD):
     """e_r = |got_r - exact_r|_2 / (|exact_r|_2 + rho),  rho = 1e-2 * the median row norm of ``exact``."""
-    g, e = rows_of(got), rows_of(exact)
+    g, e = rows_of(got, width), rows_of(exact, width)
     assert g.shape == e.shape, (g.shape, e.shape)
     n = e.norm(dim=-1)
     rho = 1e-2 * n.median()
     return (g - e).norm(dim=-1) / (n + rho)
 
 
-def gate(got, exact, model, factor=2.0):
+def gate(got, exact, model, factor=2.0, width=HD):
     """(passes, ratio, worst row index):  max_r e_r <= factor * max_r m_r, the bound coming from the reference's two forms alone."""
-    e, m = row_errors(got, exact), row_errors(model, exact)
+    e, m = row_errors(got, exact, width), row_errors(model, exact, width)
     bound = float(m.max())
     worst = int(e.argmax())
     if not torch.isfinite(e).all():

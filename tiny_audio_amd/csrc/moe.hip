@@ -301,14 +301,18 @@ __global__ void moe_router_bwd_kernel(const float* __restrict__ dtopw, const flo
   dp[i1] = g1 / den - common;
   float dl[MOE_MAX_E];
   for (int e = 0; e < E; ++e) dl[e] = 0.f;
+  // <dp, p> of the top-2 share in closed form: r0 (g0 / den - common) + r1 (g1 / den - common) = common (den - r0 - r1) = 1e-6 common.
+  // Summed term by term it cancels to f32 rounding noise (~2^-24 |g|) around a value of 1e-6 |g|, and that noise WAS the whole
+  // gradient of every expert a token did not choose (dlogits[e] = -p[e] * dot there): tests/test_gpu_moe_grid.py, router.weight rows
+  float dot = common * 1e-6f;
   if (training) {
     for (int e = 0; e < E; ++e) {
-      dp[e] += d_aux * coef * 2.0f * (psum[e] / (float)T - 1.0f / (float)E) / (float)T;
+      const float a = d_aux * coef * 2.0f * (psum[e] / (float)T - 1.0f / (float)E) / (float)T;
+      dp[e] += a;
+      dot += a * p[e];
       dl[e] += d_aux * zcoef * 2.0f * lse[t] * p[e] / (float)T;
     }
   }
-  float dot = 0.f;
-  for (int e = 0; e < E; ++e) dot += dp[e] * p[e];
   for (int e = 0; e < E; ++e) {
     float v = dl[e] + p[e] * (dp[e] - dot);
     if (noise) v *= noise[(long)t * E + e];
