@@ -657,6 +657,52 @@ int ta_adamw_step_multi(float* p, const float* g, float* m, float* v, long n, co
                         const float* seg_wd, int nseg, float lr_mult, float beta1, float beta2, float eps, int step,
                         const float* sqnorm, float max_norm, float grad_scale, const float* denom, hipStream_t st);
 
+/* ---- device-side waveform augmentation, between the upload of wav [B, Ls] and ta_logmel_f32 (tiny_audio_amd/csrc/augment.hip).
+ * Replaces the numeric stages that the reference's production recipe (configs/training/production.yaml:67-140) runs in CPU
+ * dataloader workers through audiomentations (tiny_audio/augmentation.py:71-223, wired at scripts/train.py:530-587), in the
+ * reference's order: ApplyImpulseResponse, AddBackgroundNoise, AddGaussianSNR, ClippingDistortion.  Semantics: DESIGN.md section 3
+ * "Device-side augmentation", defined by tests/augment_ref.py.  Every stage acts on clip b over [0, lens[b]); the padding stays
+ * zero; a stage that is off for a clip leaves that clip bit-identical.  All per-clip descriptors are DEVICE arrays of B entries.
+ *
+ * RIR convolution (replaces RIRAugmentation.__call__, tiny_audio/augmentation.py:71-93): uniformly partitioned overlap-save in f32,
+ * hop TA_WAVE_CONV_HOP, complex FFT of 2 * TA_WAVE_CONV_HOP points in LDS.
+ *   ta_wave_fft_twiddles: tw float[2 * TA_WAVE_CONV_HOP] = exp(-2 pi i k / N) as (re, im), k < N / 2, rounded once from float64.
+ *   ta_wave_ir_spectra: the pool's partition spectra, computed ONCE per pool.  ir: the impulse responses back to back; response r
+ *      is ir[ir_off[r] .. ir_off[r + 1]) (device long[n_ir + 1]) and owns partitions part_off[r] .. part_off[r + 1] (device
+ *      int[n_ir + 1]; ceil(taps / hop) each); max_parts = the largest partition count; spectra: float[part_off[n_ir] * 2 *
+ *      (TA_WAVE_CONV_HOP + 1)].
+ *   ta_wave_conv_f32: out[b] = the convolution of clip b with response ir_idx[b] (>= 0), kept on [0, lens[b]) and scaled by
+ *      rir_peak / max|full convolution| (rir_peak <= 0: no scaling) -- or the copy of wav[b] when ir_idx[b] < 0 (or ir_idx is
+ *      NULL: every clip copied, no workspace needed).  max_taps = the longest response of the pool; ws: ta_wave_conv_ws_bytes
+ *      bytes, no initial contents required; out must not alias wav.  Where the clip or the response has at most
+ *      TA_WAVE_CONV_DIRECT samples the convolution is formed directly from ir (the same array ta_wave_ir_spectra read), each
+ *      sample as a sum of <= TA_WAVE_CONV_DIRECT products in double, rounded once: cheaper than the transforms there, and exact
+ *      to the last bit where a transform is not. */
+#define TA_WAVE_CONV_HOP 2048
+#define TA_WAVE_CONV_DIRECT 32
+int ta_wave_fft_twiddles(float* tw, hipStream_t st);
+int ta_wave_ir_spectra(const float* ir, const long* ir_off, const int* part_off, int n_ir, int max_parts, const float* tw,
+                       float* spectra, hipStream_t st);
+long ta_wave_conv_ws_bytes(int B, int Ls, int max_taps);
+int ta_wave_conv_f32(const float* wav, const long* lens, int B, int Ls, const int* ir_idx, const float* ir, const long* ir_off,
+                     const int* part_off, int n_ir, int max_taps, const float* tw, const float* spectra, float rir_peak,
+                     float* out, void* ws, long ws_bytes, hipStream_t st);
+/* Background noise at an SNR, then the Gaussian floor at an SNR, in place (replaces AddBackgroundNoise and AddGaussianSNR inside
+ * NoiseAugmentation.__call__, tiny_audio/augmentation.py:154-185,218-223).  Clip b with noise_idx[b] = j >= 0 gets
+ * x + (rms_x * noise_amp[b] / rms_v) v,  v[t] = noise_j[(noise_start[b] + t) mod len_j],  noise_amp = 10^(-snr_dB / 20), the rms
+ * over [0, lens[b]); skipped when rms_v < 1e-9.  noise: the pool back to back, clip j = noise[noise_off[j] .. noise_off[j + 1]).
+ * Then, where gauss_amp[b] > 0:  + rms * gauss_amp[b] * z[b, t]  with rms taken after the background stage and z the Philox4x32-10
+ * Box-Muller normals of (seed, offset, b, t) documented in csrc/philox.h.  noise_idx / gauss_amp may be NULL (stage off everywhere).
+ * scratch: float[ta_wave_mix_scratch_floats(B, Ls)], no initial contents required. */
+long ta_wave_mix_scratch_floats(int B, int Ls);
+int ta_wave_mix_f32(float* wav, const long* lens, int B, int Ls, const int* noise_idx, const long* noise_start,
+                    const float* noise_amp, const float* noise, const long* noise_off, int n_noise, const float* gauss_amp,
+                    unsigned long long seed, unsigned long long offset, float* scratch, hipStream_t st);
+/* Percentile clipping in place (replaces ClippingDistortion inside NoiseAugmentation.__call__, tiny_audio/augmentation.py:190-195):
+ * where pct[b] > 0, q = pct[b] / 2 (integer),  lo, hi = numpy.percentile(x[0:n], [q, 100 - q]) (linear interpolation),
+ * x = clip(x, lo, hi).  The order statistics are found exactly by bisection on the ordered-integer image of the floats. */
+int ta_wave_clip_f32(float* wav, const long* lens, int B, int Ls, const int* pct, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

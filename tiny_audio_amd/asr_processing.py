@@ -97,7 +97,9 @@ class LogMelFeatureExtractor:
         return feats, mask
 
     def __call__(self, raw_speech, sampling_rate=None, padding="longest", return_attention_mask=True,
-                 return_tensors="pt", **_):
+                 return_tensors="pt", augment=None, augment_plan=None, **_):
+        """``augment``: a ``DeviceWaveAugment`` applied to the uploaded waveforms before the log-mel (``augment_plan``: the
+        descriptor to use instead of a freshly drawn one).  None, the default, is the plain extraction."""
         if sampling_rate is not None and sampling_rate != self.sampling_rate:
             raise ValueError(f"LogMelFeatureExtractor was built for {self.sampling_rate} Hz audio, got {sampling_rate}")
         if isinstance(raw_speech, np.ndarray) and raw_speech.ndim == 1:
@@ -113,7 +115,10 @@ class LogMelFeatureExtractor:
         for i, w in enumerate(raw_speech):
             host[i, : lens[i]] = np.asarray(w, dtype=np.float32)[: lens[i]]
         wav = torch.from_numpy(host).to(self.device, non_blocking=True)
-        feats, mask = self.extract(wav, torch.from_numpy(lens).to(self.device))
+        lens_dev = torch.from_numpy(lens).to(self.device)
+        if augment is not None:
+            wav = augment.apply(wav, lens_dev, augment_plan if augment_plan is not None else augment.plan(lens))
+        feats, mask = self.extract(wav, lens_dev)
         out = {"input_features": feats}
         if return_attention_mask:
             out["attention_mask"] = mask

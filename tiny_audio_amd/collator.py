@@ -146,11 +146,16 @@ class DataCollator:
     ``pack_to`` (sequence packing, not in the reference): instead of padding every clip's chat sequence to the longest of the batch,
     place the sequences first-fit, in arrival order, into rows of ``pack_to`` tokens (``pack_sequences``) and emit ``segment_ids`` /
     ``position_ids`` next to the usual keys; ``ASRModel.forward`` then attends within each clip only.  The audio keys stay per clip,
-    in the order the clips were placed.  ``None`` (default) is the padded batch, key for key."""
+    in the order the clips were placed.  ``None`` (default) is the padded batch, key for key.
+
+    ``augment`` (a ``DeviceWaveAugment``): handed to the feature extractor with every batch, which applies it to the uploaded
+    waveforms before the log-mel -- the place of the reference's ``rir_augmentation`` / ``noise_augmentation`` dataset transforms
+    (scripts/train.py:530-587).  ``None`` (default): the feature extractor is called exactly as before."""
 
     def __init__(self, tokenizer: Any, feature_extractor: Any, sample_rate: int, system_prompt: Optional[str] = None,
                  projector: Any = None, encoder_conv_layers: Optional[list] = None, text_collator: Optional[Callable] = None,
-                 pack_to: Optional[int] = None):
+                 pack_to: Optional[int] = None, augment: Any = None):
+        self.augment = augment
         self.tokenizer, self.feature_extractor, self.sample_rate = tokenizer, feature_extractor, sample_rate
         self.system_prompt, self.projector = system_prompt, projector
         self.encoder_conv_layers = encoder_conv_layers or DEFAULT_ENCODER_CONV_LAYERS
@@ -195,8 +200,9 @@ class DataCollator:
 
     def __call__(self, features):
         arrays, kept = self._extract_audio_arrays(features)
+        extra = {} if self.augment is None else {"augment": self.augment}
         audio = self.feature_extractor(arrays, sampling_rate=self.sample_rate, padding="longest", return_attention_mask=True,
-                                       return_tensors="pt")
+                                       return_tensors="pt", **extra)
         mel_lengths = audio["attention_mask"].sum(dim=-1)
         enc_lengths = compute_encoder_output_length(mel_lengths, self.encoder_conv_layers)
         counts = self.projector.get_output_length(enc_lengths).to(torch.long)

@@ -1,6 +1,6 @@
 // Philox4x32-10 (Salmon et al. 2011, "Parallel random numbers: as easy as 1, 2, 3"): a counter-based generator, so every
 // draw is a pure function of (counter, key) and any thread can regenerate any draw without state.  Shared by the sampler
-// (generate.hip) and the LoRA dropout masks (lora.hip).
+// (generate.hip), the LoRA dropout masks (lora.hip) and the Gaussian floor of the waveform augmentation (augment.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -39,4 +39,25 @@ __device__ __forceinline__ unsigned lora_keep8(const LoraDropDev& d, unsigned lj
     bits |= (u >= d.thr ? 1u : 0u) << e;
   }
   return bits;
+}
+
+// ---- Gaussian floor of the waveform augmentation (augment.hip; audiomentations AddGaussianSNR).  The standard normal z[b, t] added
+// to sample t of clip b is a pure function of (seed, offset, b, t):
+//   w  = philox4x32_10(counter = (t >> 2,  b,  lo32(offset),  hi32(offset)),  key = (lo32(seed), hi32(seed)))
+//   samples 4 q, 4 q + 1 come from (wa, wb) = (w.x, w.y), samples 4 q + 2, 4 q + 3 from (w.z, w.w), by Box-Muller:
+//   u1 = ((wa >> 8) + 1) 2^-24  in (0, 1],   u2 = (wb >> 8) 2^-24  in [0, 1),   r = sqrt(-2 ln u1),
+//   z  = r cos(2 pi u2),  r sin(2 pi u2)
+// i.e. one Philox call gives 4 consecutive samples, |z| <= sqrt(48 ln 2) = 5.77.  logf / sincosf are the accurate ones (the product
+// 2 pi u2 is rounded to f32 first).  Nothing depends on the launch geometry.  Valid for t < 2^34 and b < 2^32.
+__device__ __forceinline__ void wave_normal4(const uint4 w, float z[4]) {
+  const unsigned ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = (float)((ws[2 * h] >> 8) + 1u) * 5.9604644775390625e-8f, u2 = (float)(ws[2 * h + 1] >> 8) * 5.9604644775390625e-8f;
+    const float r = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    z[2 * h] = r * cs;
+    z[2 * h + 1] = r * sn;
+  }
 }

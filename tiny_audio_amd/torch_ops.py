@@ -4,6 +4,7 @@ north_star: "exposed as PyTorch-ROCm custom ops so ASRModel/ASRProcessor and scr
 reference has no FFI; its seams are nn.Module boundaries, and each operator below sits on one:
 
     ta355::logmel              WhisperFeatureExtractor.__call__           scripts/train.py:327-333
+    ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
     ta355::whisper_encoder_forward  the same seam with a Whisper tower    tiny_audio/asr_modeling.py:203-237
     ta355::mlp_projector       MLPAudioProjector.forward   (+ autograd)   tiny_audio/projectors.py:57-71
@@ -91,6 +92,20 @@ def _(wav, lens, handle):
     B, Ls = wav.shape
     n = module_of(handle).feature_size
     return wav.new_empty((B, n, Ls // 160)), wav.new_empty((B, Ls // 160), dtype=torch.int32)
+
+
+# ============================================================================ waveform augmentation
+@torch.library.custom_op("ta355::wave_augment", mutates_args=())
+def wave_augment(wav: Tensor, lens: Tensor, desc: Tensor, stages: int, seed: int, offset: int, handle: int) -> Tensor:
+    """wav f32 [B, Ls] (zero padded), lens i64 [B], desc u8: the packed per-clip descriptor (``WaveAugmentPlan.pack``) -> the augmented
+    f32 [B, Ls].  ``stages``: bit mask of the stages some clip uses; (seed, offset): the Philox triple of the Gaussian floor.  No
+    autograd: the waveform is data."""
+    return module_of(handle)._apply(wav, lens, desc, stages, seed, offset)
+
+
+@wave_augment.register_fake
+def _(wav, lens, desc, stages, seed, offset, handle):
+    return torch.empty_like(wav)
 
 
 # ============================================================================ frozen encoder
@@ -564,4 +579,4 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
-             "lm_forward_loss_seg", "lm_backward_seg")
+             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment")
