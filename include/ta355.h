@@ -637,6 +637,7 @@ int ta_bernoulli_keep(float* keep, long n, float keep_prob, unsigned long long s
  * uses it to choose the N > 1 default (overlapped vs synchronous all-reduce) on a one-GPU box. */
 int ta_debug_occupy(int workgroups, double micros, void* buf, long bytes, hipStream_t st);
 
+/* TA_ERR_ARG unless ldl % 4 == 0 and V <= ldl, and, with dlogits, ldd % 4 == 0 and ldd >= V. */
 int ta_cross_entropy(const void* logits, int logits_bf16, long ldl, const int* rows, const long* targets, int n, int V,
                      float scale, float* nll, float* loss_accum, void* dlogits_bf16, long ldd, hipStream_t st);
 int ta_label_rows(const long* labels, int B, int L, int* rows, long* targets, int* n_out, hipStream_t st);

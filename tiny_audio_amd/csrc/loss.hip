@@ -138,6 +138,7 @@ extern "C" int ta_cross_entropy(const void* logits, int logits_bf16, long ldl, c
                                 hipStream_t st) {
   if (n <= 0) return TA_OK;
   if ((ldl % 4) || (dlogits_bf16 && (ldd % 4))) return TA_ERR_ARG;
+  if (V > ldl || (dlogits_bf16 && ldd < V)) return TA_ERR_ARG;      // a row of logits / dlogits holds fewer than V columns
   // with an nll buffer the loss is summed from it in row order (nll_sum_kernel); without one, each row adds itself atomically
   float* atomic_loss = nll ? nullptr : loss_accum;
   if (logits_bf16)
