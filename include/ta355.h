@@ -703,6 +703,37 @@ int ta_wave_mix_f32(float* wav, const long* lens, int B, int Ls, const int* nois
  * where pct[b] > 0, q = pct[b] / 2 (integer),  lo, hi = numpy.percentile(x[0:n], [q, 100 - q]) (linear interpolation),
  * x = clip(x, lo, hi).  The order statistics are found exactly by bisection on the ordered-integer image of the floats. */
 int ta_wave_clip_f32(float* wav, const long* lens, int B, int Ls, const int* pct, hipStream_t st);
+/* Short noises in place (replaces AddShortNoises inside NoiseAugmentation.__call__, tiny_audio/augmentation.py:172-177; it sits
+ * between the background noise and the Gaussian floor).  Clip b has ev_count[b] <= min(ev_stride, TA_WAVE_MAX_EVENTS) events; the
+ * descriptor arrays are [B, ev_stride].  Event e = the window [ev_off, ev_off + ev_len) of pool clip ev_pool (pool_off as noise_off
+ * above; no tiling: the window lies inside the clip), laid at ev_t0 >= 0:
+ *   y[t0 + i] += g a_in[i] a_out[i] v[i],  i < ev_len, t0 + i < lens[b];   g = R ev_amp / r,  ev_amp = 10^(-snr_dB / 20),
+ *   R = rms of the stage's input over [0, lens[b]) taken once before any event, r = rms of the whole window before the fades (an
+ *   event with r < 1e-9 is skipped);  a_in[i] = 10^(-(D / 20)(1 - (i + 1) / fade_in)) for i < fade_in, a_out[i] =
+ *   10^(-(D / 20)(1 - (ev_len - i) / fade_out)) for i >= ev_len - fade_out, else 1;  D = fade_floor_db.
+ * Overlapping events add in list order: no atomics, the result does not depend on launch order.  An event longer than
+ * max_event_len (which sizes the scratch) or not inside its pool clip is skipped.
+ * scratch: float[ta_wave_events_scratch_floats(B, Ls, ev_stride, max_event_len)], no initial contents required. */
+#define TA_WAVE_MAX_EVENTS 64
+long ta_wave_events_scratch_floats(int B, int Ls, int ev_stride, long max_event_len);
+int ta_wave_events_f32(float* wav, const long* lens, int B, int Ls, const int* ev_count, int ev_stride, const int* ev_pool,
+                       const long* ev_off, const long* ev_len, const long* ev_t0, const int* ev_fade_in, const int* ev_fade_out,
+                       const float* ev_amp, const float* pool, const long* pool_off, int n_pool, long max_event_len,
+                       float fade_floor_db, float* scratch, hipStream_t st);
+/* A cascade of second-order sections in place (replaces SevenBandParametricEQ and OneOf{LowPassFilter, BandPassFilter} inside
+ * NoiseAugmentation.__call__, tiny_audio/augmentation.py:186-215).  Clip b is filtered over [0, lens[b]) by its n_sec[b] <=
+ * TA_WAVE_IIR_MAX_SECTIONS sections sos[b][k] = (b0, b1, b2, a1, a2), a0 = 1 (device double[B][TA_WAVE_IIR_MAX_SECTIONS][5]); a
+ * first-order section has b2 = a2 = 0; n_sec[b] = 0 leaves the clip untouched.  The result is scipy.signal.sosfilt's in float64
+ * from a zero state, rounded to f32 once per sample: the recurrence is carried in f64 and evaluated EXACTLY in parallel over time
+ * (per chunk of `chunk` samples: the final state from zero; per clip: the chunk map of the 2 S states and the entry state of every
+ * chunk; per chunk again: the run from its entry state).  chunk: 0 = TA_WAVE_IIR_CHUNK, else a multiple of 32; chunk >= Ls is the
+ * sequential one-thread-per-clip form (for measurements).  The caller guarantees stable sections.
+ * ws: ta_wave_sos_ws_bytes(B, Ls, chunk) bytes, no initial contents required. */
+#define TA_WAVE_IIR_MAX_SECTIONS 8
+#define TA_WAVE_IIR_CHUNK 256
+long ta_wave_sos_ws_bytes(int B, int Ls, int chunk);
+int ta_wave_sos_f32(float* wav, const long* lens, int B, int Ls, const int* n_sec, const double* sos, int chunk, void* ws,
+                    long ws_bytes, hipStream_t st);
 
 #ifdef __cplusplus
 }

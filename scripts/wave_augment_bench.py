@@ -1,5 +1,9 @@
 """Per-stage cost of the device-side waveform augmentation at the production batch: B = 32 clips of 10 s, impulse responses of 1 s
-and 2 s, every stage on for every clip, then each stage alone, then all stages off (the copy).  Device events around ``--iters``
+and 2 s, every stage on for every clip, then each stage alone, then all stages off (the copy); then the three members that
+``DeviceProductionAugment`` adds (short noises, EQ, band-limit) each alone on every clip, the whole chain on every clip, and the whole
+chain with each stage drawn at the production recipe's probability (configs/training/production.yaml:67-140).  The cascade kernel is also
+timed by itself (after a copy of the batch, which is timed beside it) in its time-parallel form and in the one-thread-per-clip form of
+the same kernel (chunk length = the clip).  Device events around ``--iters``
 calls after ``--warmup`` calls; the log-mel of the same batch is timed the same way beside it.  ``--cpu``: the same chain in float32
 scipy / numpy on this process's CPUs (one clip per worker thread), the yardstick for "what the host would pay".
 
@@ -60,7 +64,7 @@ def main():
     a = ap.parse_args()
     import torch
     from tiny_audio_amd.asr_processing import LogMelFeatureExtractor
-    from tiny_audio_amd.augmentation import DeviceWaveAugment
+    from tiny_audio_amd.augmentation import DeviceProductionAugment
     if not torch.cuda.is_available():
         raise SystemExit("wave_augment_bench.py measures on the GPU; none found")
     rng = np.random.default_rng(0)
@@ -69,8 +73,9 @@ def main():
     clips = [rng.standard_normal(n).astype(np.float32) * 0.1 for _ in range(B)]
     wav = torch.from_numpy(np.stack(clips)).cuda()
     lens = torch.full((B,), n, dtype=torch.int64, device="cuda")
-    aug = DeviceWaveAugment(rir_pool=irs, rir_prob=1.0, noise_pool=noises, prob=1.0, gaussian_min_snr_db=20.0, gaussian_max_snr_db=40.0,
-                            clipping_prob=1.0, device="cuda", seed=0)
+    events = [(rng.standard_normal(m) * np.exp(-np.arange(m) / (m / 4.0))).astype(np.float32) for m in (8000, 24000, 64000)]
+    every = dict(rir_pool=irs, noise_pool=noises, short_noises_pool=events, gaussian_min_snr_db=20.0, gaussian_max_snr_db=40.0, device="cuda", seed=0)
+    aug = DeviceProductionAugment(rir_prob=1.0, prob=1.0, clipping_prob=1.0, short_noises_prob=1.0, eq_prob=1.0, bandlimit_prob=1.0, **every)
     full = aug.plan([n] * B)
     full.ir_idx[:] = np.arange(B) % 2                    # half the clips the 1 s response, half the 2 s one
 
@@ -81,12 +86,22 @@ def main():
         p.noise_idx[:] = full.noise_idx if keep.get("bg") else -1
         p.gauss_snr_db[:] = full.gauss_snr_db if keep.get("gauss") else np.nan
         p.clip_pct[:] = full.clip_pct if keep.get("clip") else 0
+        p.ev_count[:] = full.ev_count if keep.get("events") else 0
+        p.eq_nsec[:] = full.eq_nsec if keep.get("eq") else 0
+        p.bl_nsec[:] = full.bl_nsec if keep.get("bl") else 0
+        for f in ("ev_pool", "ev_off", "ev_len", "ev_t0", "ev_fade_in", "ev_fade_out", "ev_snr_db", "eq_sos", "bl_sos"):
+            getattr(p, f)[:] = getattr(full, f)
         return p
 
     fe = LogMelFeatureExtractor(128, "cuda")
-    cases = {"all stages": full, "rir only (1 s + 2 s)": only(rir=True), "rir only, 1 s": only(rir_idx=0), "rir only, 2 s": only(rir_idx=1),
+    four = dict(rir=True, bg=True, gauss=True, clip=True)
+    recipe = DeviceProductionAugment(rir_prob=0.5, prob=0.6, clipping_prob=0.1, short_noises_prob=0.5, eq_prob=0.5, bandlimit_prob=0.3, **every)
+    drawn = recipe.plan([n] * B)
+    cases = {"all stages": only(**four), "rir only (1 s + 2 s)": only(rir=True), "rir only, 1 s": only(rir_idx=0), "rir only, 2 s": only(rir_idx=1),
              "background only": only(bg=True), "gaussian only": only(gauss=True), "clipping only (every clip)": only(clip=True),
-             "all off (copy)": only()}
+             "all off (copy)": only(), "short noises only (every clip)": only(events=True), "eq only (every clip)": only(eq=True),
+             "band-limit only (every clip)": only(bl=True), "all seven stages, every clip": full,
+             "production chain at the recipe's probabilities": drawn}
 
     def timed(fn):
         for _ in range(a.warmup):
@@ -103,9 +118,22 @@ def main():
     res = {"batch": B, "seconds": a.seconds, "iters": a.iters, "us": {}}
     for name, plan in cases.items():
         desc = torch.from_numpy(plan.pack()).cuda()
-        st = plan.stages()
-        res["us"][name] = timed(lambda: aug._apply(wav, lens, desc, st, plan.seed, plan.offset))
+        st, E, ml = plan.stages(), plan.ev_stride(), plan.max_event_len()
+        res["us"][name] = timed(lambda: aug._apply_chain(wav, lens, desc, st, plan.seed, plan.offset, E, ml))
+    res["drawn"] = {"events": int(drawn.ev_count.sum()), "clips with events": int((drawn.ev_count > 0).sum()), "eq": int((drawn.eq_nsec > 0).sum()),
+                    "band-limit": int((drawn.bl_nsec > 0).sum()), "rir": int((drawn.ir_idx >= 0).sum()),
+                    "background": int((drawn.noise_idx >= 0).sum()), "clipped": int((drawn.clip_pct > 0).sum())}
+    res["events in 'every clip'"] = int(full.ev_count.sum())
     res["us"]["logmel"] = timed(lambda: fe._extract(wav, lens))
+    # the cascade kernel by itself: seven EQ sections on every clip, after a copy of the batch (timed alone beside it)
+    buf = torch.empty_like(wav)
+    nsec, sos = torch.from_numpy(full.eq_nsec).cuda(), torch.from_numpy(full.eq_sos).cuda()
+    res["us"]["copy_ (torch)"] = timed(lambda: buf.copy_(wav))
+    res["us"]["copy_ + sos, 7 sections, time-parallel (chunk 256)"] = timed(lambda: (buf.copy_(wav), aug._sos(buf, lens, nsec, sos)))
+    seq = (n + 31) // 32 * 32
+    a.iters, keep = max(a.iters // 10, 3), a.iters
+    res["us"]["copy_ + sos, 7 sections, one thread per clip (chunk = the clip)"] = timed(lambda: (buf.copy_(wav), aug._sos(buf, lens, nsec, sos, seq)))
+    a.iters = keep
     if a.cpu:
         cpu_chain(clips[:a.threads], irs, noises, full, a.threads)
         res["us"][f"cpu float32 scipy chain, {a.threads} threads"] = min(cpu_chain(clips, irs, noises, full, a.threads) for _ in range(3))

@@ -555,3 +555,367 @@ extern "C" int ta_wave_clip_f32(float* wav, const long* lens, int B, int Ls, con
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
+
+// ---- short noises (audiomentations AddShortNoises): per clip a list of <= WE_MAX events, each a window [o, o + l) of a pool clip laid
+// at t0 with a fade in / out that is linear in dB from -D to 0, at an SNR against the rms R of the stage's input over [0, n), taken
+// once before any event.  Three launches, no atomics: the per-chunk sums of x^2, the per-(event, chunk) sums of the event's own
+// samples (both f32 trees inside a chunk of 4096, the chunk partials summed in one fixed order in double by whoever needs them), then
+// one pass over (chunk, clip) that adds, in list order, the events touching the chunk.  Descriptor arrays are [B, ev_stride].
+// An event that names no pool clip, reaches outside it, starts before 0, is empty or is longer than max_event_len is skipped.
+#define WE_MAX 64
+
+struct WeEvent {
+  const float* v;      // pool_j + o, or nullptr when the event is not valid
+  long l, t0;
+  int fin, fout;
+};
+__device__ __forceinline__ WeEvent we_event(int idx, const int* ev_pool, const long* ev_off, const long* ev_len, const long* ev_t0,
+                                            const int* ev_fin, const int* ev_fout, const float* pool, const long* pool_off, int n_pool,
+                                            long max_event_len) {
+  WeEvent e;
+  e.v = nullptr; e.l = ev_len[idx]; e.t0 = ev_t0[idx]; e.fin = ev_fin[idx]; e.fout = ev_fout[idx];
+  const int j = ev_pool[idx];
+  const long o = ev_off[idx];
+  if (j < 0 || j >= n_pool || o < 0 || e.l < 1 || e.l > max_event_len || e.t0 < 0 || e.fin < 0 || e.fout < 0) return e;
+  if (o + e.l > pool_off[j + 1] - pool_off[j]) return e;
+  e.v = pool + pool_off[j] + o;
+  return e;
+}
+__device__ __forceinline__ int we_count(const int* ev_count, int b, int ev_stride) {
+  const int c = ev_count[b], m = ev_stride < WE_MAX ? ev_stride : WE_MAX;
+  return c < 0 ? 0 : (c > m ? m : c);
+}
+
+// grid (nchunk, B): xpart[b][c] = sum x^2 of chunk c, for the clips that have events
+__global__ __launch_bounds__(WA_T) void wave_events_xsum_kernel(const float* __restrict__ wav, const long* __restrict__ lens, int Ls,
+                                                                const int* __restrict__ ev_count, int ev_stride, int nchunk,
+                                                                float* __restrict__ xpart) {
+  __shared__ float red[WA_T / 64];
+  const int b = blockIdx.y;
+  const long n = wa_clip_len(lens, b, Ls), t0 = (long)blockIdx.x * WM_CHUNK;
+  if (we_count(ev_count, b, ev_stride) <= 0 || t0 >= n) return;
+  const float* x = wav + (long)b * Ls;
+  float sx = 0.f;
+  for (int i = threadIdx.x; i < WM_CHUNK; i += WA_T) { const long t = t0 + i; if (t < n) { const float xv = x[t]; sx += xv * xv; } }
+  sx = wm_block_sum(sx, red);
+  if (threadIdx.x == 0) xpart[(long)b * nchunk + blockIdx.x] = sx;
+}
+
+// grid (nchunk_e, events, B): epart[b][e][c] = sum v^2 of chunk c of event e's own window
+__global__ __launch_bounds__(WA_T) void wave_events_rms_kernel(const int* __restrict__ ev_count, int ev_stride, const int* __restrict__ ev_pool,
+                                                               const long* __restrict__ ev_off, const long* __restrict__ ev_len,
+                                                               const long* __restrict__ ev_t0, const int* __restrict__ ev_fin,
+                                                               const int* __restrict__ ev_fout, const float* __restrict__ pool,
+                                                               const long* __restrict__ pool_off, int n_pool, long max_event_len,
+                                                               int nchunk_e, float* __restrict__ epart) {
+  __shared__ float red[WA_T / 64];
+  const int b = blockIdx.z, e = blockIdx.y;
+  if (e >= we_count(ev_count, b, ev_stride)) return;
+  const WeEvent ev = we_event(b * ev_stride + e, ev_pool, ev_off, ev_len, ev_t0, ev_fin, ev_fout, pool, pool_off, n_pool, max_event_len);
+  const long i0 = (long)blockIdx.x * WM_CHUNK;
+  if (!ev.v || i0 >= ev.l) return;
+  float sv = 0.f;
+  for (int i = threadIdx.x; i < WM_CHUNK; i += WA_T) { const long q = i0 + i; if (q < ev.l) { const float vv = ev.v[q]; sv += vv * vv; } }
+  sv = wm_block_sum(sv, red);
+  if (threadIdx.x == 0) epart[((long)b * ev_stride + e) * nchunk_e + blockIdx.x] = sv;
+}
+
+// grid (nchunk, B): y[t] = x[t] + sum over the events e in list order of g_e a_in a_out v_e[t - t0_e]
+__global__ __launch_bounds__(WA_T) void wave_events_add_kernel(float* __restrict__ wav, const long* __restrict__ lens, int Ls,
+                                                               const int* __restrict__ ev_count, int ev_stride, const int* __restrict__ ev_pool,
+                                                               const long* __restrict__ ev_off, const long* __restrict__ ev_len,
+                                                               const long* __restrict__ ev_t0, const int* __restrict__ ev_fin,
+                                                               const int* __restrict__ ev_fout, const float* __restrict__ ev_amp,
+                                                               const float* __restrict__ pool, const long* __restrict__ pool_off, int n_pool,
+                                                               long max_event_len, float fade_k, int nchunk, int nchunk_e,
+                                                               const float* __restrict__ xpart, const float* __restrict__ epart) {
+  const int b = blockIdx.y;
+  const long n = wa_clip_len(lens, b, Ls), c0 = (long)blockIdx.x * WM_CHUNK;
+  const int cnt = we_count(ev_count, b, ev_stride);
+  if (cnt <= 0 || c0 >= n) return;
+  const long c1 = c0 + WM_CHUNK < n ? c0 + WM_CHUNK : n;
+  const int ncb = (int)((n + WM_CHUNK - 1) / WM_CHUNK);
+  double sx = 0.0;
+  for (int c = 0; c < ncb; ++c) sx += (double)xpart[(long)b * nchunk + c];
+  const double R = sqrt(sx / (double)n);
+  float* x = wav + (long)b * Ls;
+  float acc[WM_CHUNK / WA_T];
+#pragma unroll
+  for (int q = 0; q < WM_CHUNK / WA_T; ++q) { const long t = c0 + threadIdx.x + q * WA_T; acc[q] = t < n ? x[t] : 0.f; }
+  for (int e = 0; e < cnt; ++e) {
+    const WeEvent ev = we_event(b * ev_stride + e, ev_pool, ev_off, ev_len, ev_t0, ev_fin, ev_fout, pool, pool_off, n_pool, max_event_len);
+    if (!ev.v || ev.t0 >= c1 || ev.t0 + ev.l <= c0) continue;
+    const float* ep = epart + ((long)b * ev_stride + e) * nchunk_e;
+    const int nce = (int)((ev.l + WM_CHUNK - 1) / WM_CHUNK);
+    double se = 0.0;
+    for (int c = 0; c < nce; ++c) se += (double)ep[c];
+    const double re = sqrt(se / (double)ev.l);
+    if (re < 1e-9) continue;                                   // a silent event: skipped
+    const float g = (float)(R * (double)ev_amp[b * ev_stride + e] / re);
+    const float rin = ev.fin > 0 ? 1.0f / (float)ev.fin : 0.f, rout = ev.fout > 0 ? 1.0f / (float)ev.fout : 0.f;
+#pragma unroll
+    for (int q = 0; q < WM_CHUNK / WA_T; ++q) {
+      const long t = c0 + threadIdx.x + q * WA_T, i = t - ev.t0;
+      if (i < 0 || i >= ev.l || t >= n) continue;
+      float a = g;
+      if (i < ev.fin) a *= exp2f(fade_k * (1.0f - (float)(i + 1) * rin));
+      if (i >= ev.l - ev.fout) a *= exp2f(fade_k * (1.0f - (float)(ev.l - i) * rout));
+      acc[q] += a * ev.v[i];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < WM_CHUNK / WA_T; ++q) { const long t = c0 + threadIdx.x + q * WA_T; if (t < n) x[t] = acc[q]; }
+}
+
+extern "C" long ta_wave_events_scratch_floats(int B, int Ls, int ev_stride, long max_event_len) {
+  if (B <= 0 || Ls <= 0 || ev_stride <= 0 || max_event_len <= 0) return 0;
+  return (long)B * ta_cdiv(Ls, WM_CHUNK) + (long)B * ev_stride * ta_cdiv(max_event_len, WM_CHUNK);
+}
+
+extern "C" int ta_wave_events_f32(float* wav, const long* lens, int B, int Ls, const int* ev_count, int ev_stride, const int* ev_pool,
+                                  const long* ev_off, const long* ev_len, const long* ev_t0, const int* ev_fade_in, const int* ev_fade_out,
+                                  const float* ev_amp, const float* pool, const long* pool_off, int n_pool, long max_event_len,
+                                  float fade_floor_db, float* scratch, hipStream_t st) {
+  if (B <= 0 || Ls <= 0 || !ev_count || ev_stride <= 0 || n_pool <= 0 || max_event_len <= 0) return TA_OK;
+  if (!wav || !lens || !ev_pool || !ev_off || !ev_len || !ev_t0 || !ev_fade_in || !ev_fade_out || !ev_amp || !pool || !pool_off || !scratch ||
+      B > 65535 || ev_stride > WE_MAX || !(fade_floor_db >= 0.f))
+    return TA_ERR_ARG;
+  const int nchunk = ta_cdiv(Ls, WM_CHUNK), nchunk_e = ta_cdiv(max_event_len, WM_CHUNK);
+  if (nchunk_e > 65535) return TA_ERR_ARG;
+  float *xpart = scratch, *epart = scratch + (long)B * nchunk;
+  const float fade_k = (float)(-(double)fade_floor_db / 20.0 * 3.321928094887362);      // a = 2^(fade_k (1 - position)), log2(10)
+  TA_LAUNCH(wave_events_xsum_kernel, dim3(nchunk, B), dim3(WA_T), 0, st, wav, lens, Ls, ev_count, ev_stride, nchunk, xpart);
+  TA_CHECK_LAUNCH();
+  TA_LAUNCH(wave_events_rms_kernel, dim3(nchunk_e, ev_stride, B), dim3(WA_T), 0, st, ev_count, ev_stride, ev_pool, ev_off, ev_len, ev_t0,
+            ev_fade_in, ev_fade_out, pool, pool_off, n_pool, max_event_len, nchunk_e, epart);
+  TA_CHECK_LAUNCH();
+  TA_LAUNCH(wave_events_add_kernel, dim3(nchunk, B), dim3(WA_T), 0, st, wav, lens, Ls, ev_count, ev_stride, ev_pool, ev_off, ev_len, ev_t0,
+            ev_fade_in, ev_fade_out, ev_amp, pool, pool_off, n_pool, max_event_len, fade_k, nchunk, nchunk_e, xpart, epart);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// ---- exact time-parallel cascade of second-order sections (the EQ and the band-limit): clip b is filtered by n_sec[b] <= WI_S
+// sections (b0, b1, b2, a1, a2), a0 = 1, given in float64; the recurrence is carried in f64 (direct form II transposed, as
+// scipy.signal.sosfilt), reads and writes f32 in place, and rounds each output sample once.
+// A cascade of S sections is ONE linear system with 2 S states, so the state after a chunk of T samples is
+//     s[c + 1] = M s[c] + z[c],   M = the chunk's zero-input map (2S x 2S),  z[c] = the final state of chunk c run from a zero state.
+//   phase 1, grid (chunk groups + 1, B), one thread per chunk: z[c] of every chunk that has a successor; the extra workgroup builds M,
+//            column j = T zero-input steps from the unit state e_j;
+//   phase 2, grid (B), one wave per clip, lane r = row r of M: the entry state of every chunk, sequentially over chunks (z is
+//            prefetched eight chunks ahead; the state is passed between lanes by v_readlane);
+//   phase 3, as phase 1: every chunk reruns from its entry state and writes.
+// This is the recurrence itself, refactored: no warm-up, no overlap.  No atomics; nothing depends on launch order.
+// A thread walks its own chunk, so neighbouring lanes are a whole chunk apart in memory: the workgroup moves tiles of 64 chunks x 32
+// samples between memory and LDS in 128-byte rows, and a thread reads its row of the tile (row stride 33 floats: no bank conflict).
+// The state array of a chunk is 2 WI_S doubles; rows [2 k, 2 k + 1] are the two delays of section k.
+#define WI_S 8
+#define WI_NS (2 * WI_S)
+#define WI_WG 64
+#define WI_TILE 32
+#define WI_LD (WI_TILE + 1)
+
+template <int S>
+__device__ __forceinline__ double wi_step(double x, const double (&cf)[WI_S][5], double (&s)[WI_NS]) {
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const double y = fma(cf[k][0], x, s[2 * k]);
+    s[2 * k] = fma(-cf[k][3], y, fma(cf[k][1], x, s[2 * k + 1]));
+    s[2 * k + 1] = fma(-cf[k][4], y, cf[k][2] * x);
+    x = y;
+  }
+  return x;
+}
+__device__ __forceinline__ void wi_load_tile(float* lds, const float* __restrict__ x, long n, long group0, long T, int k) {
+  for (int idx = threadIdx.x; idx < WI_WG * WI_TILE; idx += WI_WG) {
+    const int row = idx / WI_TILE, col = idx % WI_TILE;
+    const long t = (group0 + row) * T + (long)k * WI_TILE + col;
+    lds[row * WI_LD + col] = t < n ? x[t] : 0.f;
+  }
+}
+template <int S>
+__device__ __forceinline__ void wi_load_coef(const double* __restrict__ sos, int b, double (&cf)[WI_S][5]) {
+#pragma unroll
+  for (int k = 0; k < S; ++k)
+#pragma unroll
+    for (int q = 0; q < 5; ++q) cf[k][q] = sos[((long)b * WI_S + k) * 5 + q];
+}
+
+template <int S>
+__device__ __forceinline__ void wi_phase1(float* lds, const float* __restrict__ x, long n, int b, long T, int nck, bool build_m,
+                                          const double* __restrict__ sos, double* __restrict__ Z, double* __restrict__ M) {
+  double cf[WI_S][5], s[WI_NS];
+  wi_load_coef<S>(sos, b, cf);
+#pragma unroll
+  for (int r = 0; r < WI_NS; ++r) s[r] = 0.0;
+  if (build_m) {
+    const int j = threadIdx.x;
+    if (n <= T || j >= 2 * S) return;
+#pragma unroll
+    for (int r = 0; r < 2 * S; ++r) s[r] = r == j ? 1.0 : 0.0;
+    for (long i = 0; i < T; ++i) wi_step<S>(0.0, cf, s);
+#pragma unroll
+    for (int r = 0; r < 2 * S; ++r) M[(long)b * WI_NS * WI_NS + j * WI_NS + r] = s[r];
+    return;
+  }
+  const long group0 = (long)blockIdx.x * WI_WG, ck = group0 + threadIdx.x;
+  if (group0 * T >= n) return;
+  const bool active = (ck + 1) * T < n;            // only a chunk with a successor needs its final state
+  for (int k = 0; k < T / WI_TILE; ++k) {
+    __syncthreads();
+    wi_load_tile(lds, x, n, group0, T, k);
+    __syncthreads();
+    if (active)
+      for (int i = 0; i < WI_TILE; ++i) wi_step<S>((double)lds[threadIdx.x * WI_LD + i], cf, s);
+  }
+  if (active)
+#pragma unroll
+    for (int r = 0; r < 2 * S; ++r) Z[((long)b * nck + ck) * WI_NS + r] = s[r];
+}
+
+template <int S>
+__device__ __forceinline__ void wi_phase3(float* lds, float* __restrict__ x, long n, int b, long T, int nck,
+                                          const double* __restrict__ sos, const double* __restrict__ Z) {
+  double cf[WI_S][5], s[WI_NS];
+  wi_load_coef<S>(sos, b, cf);
+  const long group0 = (long)blockIdx.x * WI_WG, ck = group0 + threadIdx.x;
+  if (group0 * T >= n) return;
+  const bool active = ck * T < n;
+#pragma unroll
+  for (int r = 0; r < WI_NS; ++r) s[r] = 0.0;
+  if (active && ck > 0)
+#pragma unroll
+    for (int r = 0; r < 2 * S; ++r) s[r] = Z[((long)b * nck + ck) * WI_NS + r];
+  for (int k = 0; k < T / WI_TILE; ++k) {
+    if (group0 * T + (long)k * WI_TILE >= n && (group0 + 1) * T >= n) break;      // one chunk in this group, and it has ended
+    __syncthreads();
+    wi_load_tile(lds, x, n, group0, T, k);
+    __syncthreads();
+    if (active)
+      for (int i = 0; i < WI_TILE; ++i) {
+        float* p = lds + threadIdx.x * WI_LD + i;
+        *p = (float)wi_step<S>((double)*p, cf, s);
+      }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < WI_WG * WI_TILE; idx += WI_WG) {
+      const int row = idx / WI_TILE, col = idx % WI_TILE;
+      const long t = (group0 + row) * T + (long)k * WI_TILE + col;
+      if (t < n) x[t] = lds[row * WI_LD + col];
+    }
+  }
+}
+
+#define WI_DISPATCH(S, CALL)   \
+  switch (S) {                 \
+    case 1: CALL(1); break;    \
+    case 2: CALL(2); break;    \
+    case 3: CALL(3); break;    \
+    case 4: CALL(4); break;    \
+    case 5: CALL(5); break;    \
+    case 6: CALL(6); break;    \
+    case 7: CALL(7); break;    \
+    case 8: CALL(8); break;    \
+    default: break;            \
+  }
+
+__device__ __forceinline__ int wi_sections(const int* n_sec, int b) { const int S = n_sec[b]; return (S < 0 || S > WI_S) ? 0 : S; }
+
+// grid (cdiv(nck, 64) + 1, B); the last workgroup of a clip builds M
+__global__ __launch_bounds__(WI_WG) void wave_sos_local_kernel(const float* __restrict__ wav, const long* __restrict__ lens, int Ls,
+                                                               const int* __restrict__ n_sec, const double* __restrict__ sos, long T, int nck,
+                                                               double* __restrict__ Z, double* __restrict__ M) {
+  __shared__ float lds[WI_WG * WI_LD];
+  const int b = blockIdx.y, S = wi_sections(n_sec, b);
+  const long n = wa_clip_len(lens, b, Ls);
+  if (S <= 0 || n <= T) return;                    // a single chunk has no successor: nothing to prepare
+  const bool build_m = blockIdx.x == gridDim.x - 1;
+  const float* x = wav + (long)b * Ls;
+#define WI_CALL(SS) wi_phase1<SS>(lds, x, n, b, T, nck, build_m, sos, Z, M)
+  WI_DISPATCH(S, WI_CALL)
+#undef WI_CALL
+}
+
+__device__ __forceinline__ double wi_readlane(double v, int lane) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+
+// grid (B), one wave: Z[b][c] (the final state of chunk c from zero) is replaced by the entry state of chunk c
+#define WI_PF 8
+__global__ __launch_bounds__(WI_WG) void wave_sos_carry_kernel(const long* __restrict__ lens, int Ls, const int* __restrict__ n_sec, long T,
+                                                               int nck, double* __restrict__ Z, const double* __restrict__ M) {
+  const int b = blockIdx.x, S = wi_sections(n_sec, b), r = threadIdx.x;
+  const long n = wa_clip_len(lens, b, Ls);
+  if (S <= 0 || n <= T) return;
+  const int nchunks = (int)((n + T - 1) / T);
+  const bool lane_on = r < 2 * S;
+  double mrow[WI_NS];
+#pragma unroll
+  for (int j = 0; j < WI_NS; ++j) mrow[j] = (lane_on && j < 2 * S) ? M[(long)b * WI_NS * WI_NS + j * WI_NS + r] : 0.0;
+  double* zb = Z + (long)b * nck * WI_NS + (lane_on ? r : 0);
+  double s = 0.0, zcur[WI_PF], znext[WI_PF];
+  // z[c] exists for c < nchunks - 1
+#pragma unroll
+  for (int q = 0; q < WI_PF; ++q) zcur[q] = (lane_on && q < nchunks - 1) ? zb[(long)q * WI_NS] : 0.0;
+  for (int c0 = 0; c0 < nchunks; c0 += WI_PF) {
+#pragma unroll
+    for (int q = 0; q < WI_PF; ++q) { const int c = c0 + WI_PF + q; znext[q] = (lane_on && c < nchunks - 1) ? zb[(long)c * WI_NS] : 0.0; }
+#pragma unroll
+    for (int q = 0; q < WI_PF; ++q) {
+      const int c = c0 + q;
+      if (c < nchunks) {                                      // (uniform)
+        if (lane_on) zb[(long)c * WI_NS] = s;
+        double acc = zcur[q];
+#pragma unroll
+        for (int j = 0; j < WI_NS; ++j) acc = fma(mrow[j], wi_readlane(s, j), acc);
+        s = acc;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < WI_PF; ++q) zcur[q] = znext[q];
+  }
+}
+
+// grid (cdiv(nck, 64), B)
+__global__ __launch_bounds__(WI_WG) void wave_sos_apply_kernel(float* __restrict__ wav, const long* __restrict__ lens, int Ls,
+                                                               const int* __restrict__ n_sec, const double* __restrict__ sos, long T, int nck,
+                                                               const double* __restrict__ Z) {
+  __shared__ float lds[WI_WG * WI_LD];
+  const int b = blockIdx.y, S = wi_sections(n_sec, b);
+  const long n = wa_clip_len(lens, b, Ls);
+  if (S <= 0 || n <= 0) return;
+  float* x = wav + (long)b * Ls;
+#define WI_CALL(SS) wi_phase3<SS>(lds, x, n, b, T, nck, sos, Z)
+  WI_DISPATCH(S, WI_CALL)
+#undef WI_CALL
+}
+
+namespace {
+inline long wi_chunk(int chunk) { return chunk > 0 ? chunk : 256; }
+}
+
+extern "C" long ta_wave_sos_ws_bytes(int B, int Ls, int chunk) {
+  if (B <= 0 || Ls <= 0 || chunk < 0 || wi_chunk(chunk) % WI_TILE) return 0;
+  return (long)B * ((long)ta_cdiv(Ls, wi_chunk(chunk)) * WI_NS + WI_NS * WI_NS) * (long)sizeof(double);
+}
+
+extern "C" int ta_wave_sos_f32(float* wav, const long* lens, int B, int Ls, const int* n_sec, const double* sos, int chunk, void* ws,
+                               long ws_bytes, hipStream_t st) {
+  if (B <= 0 || Ls <= 0 || !n_sec) return TA_OK;
+  if (!wav || !lens || !sos || !ws || B > 65535 || chunk < 0 || wi_chunk(chunk) % WI_TILE || ws_bytes < ta_wave_sos_ws_bytes(B, Ls, chunk))
+    return TA_ERR_ARG;
+  const long T = wi_chunk(chunk);
+  const int nck = ta_cdiv(Ls, T), ngroup = ta_cdiv(nck, WI_WG);
+  if (ngroup + 1 > 65535) return TA_ERR_ARG;
+  double* Z = (double*)ws;
+  double* M = Z + (long)B * nck * WI_NS;
+  if (nck > 1) {
+    TA_LAUNCH(wave_sos_local_kernel, dim3(ngroup + 1, B), dim3(WI_WG), 0, st, wav, lens, Ls, n_sec, sos, T, nck, Z, M);
+    TA_CHECK_LAUNCH();
+    TA_LAUNCH(wave_sos_carry_kernel, dim3(B), dim3(WI_WG), 0, st, lens, Ls, n_sec, T, nck, Z, M);
+    TA_CHECK_LAUNCH();
+  }
+  TA_LAUNCH(wave_sos_apply_kernel, dim3(ngroup, B), dim3(WI_WG), 0, st, wav, lens, Ls, n_sec, sos, T, nck, Z);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}

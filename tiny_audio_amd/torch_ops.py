@@ -5,6 +5,7 @@ reference has no FFI; its seams are nn.Module boundaries,
 
     ta355::logmel              WhisperFeatureExtractor.__call__           scripts/train.py:327-333
     ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
+    ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
     ta355::whisper_encoder_forward  the same seam with a Whisper tower    tiny_audio/asr_modeling.py:203-237
     ta355::mlp_projector       MLPAudioProjector.forward   (+ autograd)   tiny_audio/projectors.py:57-71
@@ -105,6 +106,20 @@ def wave_augment(wav: Tensor, lens: Tensor, desc: Tensor, stages: int, seed: int
 
 @wave_augment.register_fake
 def _(wav, lens, desc, stages, seed, offset, handle):
+    return torch.empty_like(wav)
+
+
+@torch.library.custom_op("ta355::wave_augment_chain", mutates_args=())
+def wave_augment_chain(wav: Tensor, lens: Tensor, desc: Tensor, stages: int, seed: int, offset: int, ev_stride: int, max_event_len: int,
+                       handle: int) -> Tensor:
+    """``wave_augment`` with the whole production chain: desc u8 is ``ProductionAugmentPlan.pack``'s image (the base image, then the
+    cascades' float64 sections and the short-noise events, ``ev_stride`` per clip, none longer than ``max_event_len`` samples);
+    ``stages`` adds 16 short noises, 32 EQ, 64 band-limit.  The handle names a ``DeviceProductionAugment``.  No autograd."""
+    return module_of(handle)._apply_chain(wav, lens, desc, stages, seed, offset, ev_stride, max_event_len)
+
+
+@wave_augment_chain.register_fake
+def _(wav, lens, desc, stages, seed, offset, ev_stride, max_event_len, handle):
     return torch.empty_like(wav)
 
 
@@ -579,4 +594,4 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
-             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment")
+             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain")
