@@ -386,7 +386,7 @@ def rowscale_pattern(M):
     return ((torch.arange(M) % 3) != 1).float()
 
 
-HS_FWD = (4, 252, 256, 260, 512, 768, 1028, 1536, 1792, 2048, 2052, 2304, 5120)
+HS_FWD = (4, 252, 256, 260, 512, 768, 1024, 1028, 1280, 1536, 1792, 2048, 2052, 2304, 5120)
 HS_BWD = (4, 128, 260, 768, 1024, 1028, 1792, 2048, 2052, 5120)
 HS_LNRES = (4, 252, 260, 1024, 1028, 2048)
 LN_EPS, RMS_EPS = 1e-5, 1e-6

@@ -1,6 +1,6 @@
 """-m gpu, round 6: the kernels and paths that are new this round, against a torch fp32 reference / the oracle.
 
-* ``layernorm_f32x8_kernel``: the encoder's LayerNorm over an fp32 residual stream (the fp32-stream mode = the training recipe);
+* ``layernorm_x8_kernel<float>``: the encoder's LayerNorm over an fp32 residual stream (the fp32-stream mode = the training recipe);
 * the fp32-stream LM backward with bf16 gradients into the RMSNorm backward (``ta_i_rmsnorm_bwd_dyb``) against the oracle's fp32
   backward at reduced depth, tighter than the bf16-stream mode;
 * the fp32-residual GEMM epilogues with batched residual loads (pairs of strips / one batch), every tile variant.
@@ -44,7 +44,7 @@ def test_layernorm_f32_stream_to_bf16(M, H):
 
 @pytest.mark.parametrize("M,H", [(7, 256), (301, 1024), (6144, 1024), (333, 2048)])
 def test_rmsnorm_f32_stream_to_bf16(M, H):
-    """rmsnorm_fwd_f32x8_kernel (f32 -> bf16 only) against torch and against the generic wave-per-row kernel."""
+    """rmsnorm_fwd_x8_kernel<float> (f32 -> bf16 only) against torch and against the generic wave-per-row kernel."""
     from tiny_audio_amd import ops
     x, w = rnd(M, H, seed=1, scale=2.0), 1 + 0.1 * rnd(H, seed=2)
     r = torch.rsqrt((x * x).mean(-1, keepdim=True) + 1e-6)
