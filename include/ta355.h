@@ -110,6 +110,26 @@ long ta_encoder_workspace_bytes(const ta_encoder_weights* w, int B, int T);
 int ta_encoder_forward(const ta_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
                        void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st);
 
+/* ---- the same tower with every clip encoded at its OWN length (the "ragged encoder"; opt-in, GLM-ASR only): replaces
+ *      model.audio_tower(input_features=feats[b:b+1, :, :T_b]).last_hidden_state for every clip b of the batch -- what the reference
+ *      computes at inference, where the feature extractor's padding is off and a clip is encoded alone
+ *      (tiny_audio/asr_modeling.py:198-200) -- instead of the training-time call on the padded batch (:448-450), whose encoder has
+ *      no attention mask (TF:models/glmasr/modeling_glmasr.py:187-217), so that a short clip's frames depend on its neighbours' lengths.
+ * mel_len_host: HOST int [B], the clips' mel lengths T_b (audio_attention_mask.sum(-1)), 1 <= T_b <= T; they set the launch geometry.
+ * cu_rows_dev:   DEVICE int [B + 1], cu[0] = 0, cu[b + 1] = cu[b] + S_b with S_b = (T_b - 1) / 2 + 1, built by the caller from the
+ *               same lengths.  The host cannot read it, so a table that disagrees with mel_len_host is not detected: the copy kernels
+ *               (compaction, rotary table, expansion) skip the rows it places outside the workspace, but the attention kernel
+ *               TRUSTS it and reads and writes rows cu[b] .. cu[b + 1] unchecked.
+ * Output rows [b, 0:S_b) = the encoder applied to feats[b, :, :T_b] alone (the stem's zero padding at the clip's own end, rotary
+ * positions 0 .. S_b - 1, attention over the clip's own frames); rows [b, S_b:S) and the frames with frame_keep == 0 are exact
+ * zeros; out_bf16 / out_f32 keep ta_encoder_forward's padded [B*S, H] layout.  feats[b, :, T_b:] is never read.
+ * Internally the layer loop runs on rows = sum of S_b compact rows.  Needs ta_enc_layer.wqkv_fa / bqkv_fa and rope_il (TA_ERR_ARG
+ * without them: the three-kernel path is not extended).  Kernel launches on st only: no allocation, copy or synchronisation. */
+long ta_encoder_ragged_workspace_bytes(const ta_encoder_weights* w, int B, int T, long rows);
+int ta_encoder_forward_ragged(const ta_encoder_weights* w, const float* feats, int B, int T, const int* mel_len_host,
+                              const int* cu_rows_dev, const float* frame_keep, void* out_bf16, float* out_f32, void* ws,
+                              long ws_bytes, hipStream_t st);
+
 /* ---- frozen Whisper encoder (any openai/whisper-* checkpoint; the reference's other audio_tower, tiny_audio/asr_modeling.py:203-237):
  *      replaces WhisperEncoder.forward(input_features).last_hidden_state (TF:models/whisper/modeling_whisper.py:592-650).
  * The stem, the layer arithmetic (TF:models/whisper/modeling_whisper.py:379-407: pre-LN, q/v/out bias, k without, exact GELU,
@@ -458,6 +478,11 @@ int ta_lora_dropout_keep(const ta_lora_dropout* drop, int layer, int linear, int
  * no mask, head_dim 64).  qkv bf16 [B*S, 3*heads*64] token-major, thirds q | k | v, head h at columns h*64 of each third; the
  * q values must already carry head_dim^-0.5 * log2(e) (ta_enc_layer.wqkv_fa): out = softmax_base2(q k^T) v, bf16 [B*S, heads*64]. */
 int ta_attention_enc_fwd(const void* qkv, void* out, int B, int heads, int S, hipStream_t st);
+/* The same over clips of different lengths, for ta_encoder_forward_ragged (replaces one GlmAsrAttention.forward per clip,
+ * TF:models/glmasr/modeling_glmasr.py:187-217, on that clip's frames alone): clip b owns rows cu_rows[b] .. cu_rows[b + 1] of
+ * qkv [rows, 3*heads*64] and out [rows, heads*64]; cu_rows DEVICE int [B + 1], non-decreasing from 0; max_rows = the longest clip's
+ * row count (sizes the grid).  Clip b's rows are bit-identical to ta_attention_enc_fwd on those rows with B = 1, S = its length. */
+int ta_attention_enc_fwd_varlen(const void* qkv, void* out, const int* cu_rows, int B, int heads, int max_rows, hipStream_t st);
 
 /* C = epilogue(A[M,K] x W[N,K]^T).  A/C rows are mapped  row -> (row / rpb) * bs + (row % rpb) * ld
  * (rpb <= 0 means "no batching").  act: 0 none, 1 erf-GELU.  residual: f32, C's row map.

@@ -134,10 +134,11 @@ class ASRModel(nn.Module):
     main_input_name = "input_features"
     TRANSCRIBE_PROMPT = "Transcribe the speech to text"
 
-    def __init__(self, config: ASRConfig, device="cuda", init="random", seed=0, **kwargs):
+    def __init__(self, config: ASRConfig, device="cuda", init="random", seed=0, ragged_encoder=False, **kwargs):
         super().__init__()
         self.config = config
         self.device_ = torch.device(device)
+        self._ragged_encoder = False
         # asr_modeling.py:203-237: a Whisper encoder for every "whisper" audio_model_id, GLM-ASR's audio tower otherwise
         if isinstance(config.audio_config, WhisperEncoderConfig):
             self.audio_tower = WhisperEncoderMI355X(config.audio_config, device=device)
@@ -180,6 +181,40 @@ class ASRModel(nn.Module):
         # the reference builds its WhisperFeatureExtractor here (tiny_audio/asr_modeling.py:146, :190-201; padding disabled for
         # GLM-ASR); this one computes the log-mel on the device.  ``feature_extractor=`` hands in another one.
         self.feature_extractor = kwargs.get("feature_extractor") or self._create_feature_extractor(config)
+        self.ragged_encoder = ragged_encoder
+
+    @property
+    def ragged_encoder(self) -> bool:
+        """True: the frozen GLM-ASR tower encodes every clip at its OWN mel length (``audio_attention_mask.sum(-1)``) -- what the
+        reference computes for a clip at inference, where it is encoded alone without padding (tiny_audio/asr_modeling.py:198-200)
+        -- instead of padded to the longest clip of the batch with the padding attended to, as the reference's training forward
+        does (:448-450).  A deliberate, opt-in difference from the reference's training arithmetic, in the
+        class of sequence packing; a run-time attribute, not an ``ASRConfig`` / ``config.json`` field.  ``forward``, ``generate``
+        and ``generate_streaming`` then need ``audio_attention_mask``; the lengths are taken on the host, which costs one
+        device sync per call when the mask lives on the device (the collators emit it on the host).  Whisper towers refuse it:
+        their contract is a fixed 30 s window with attention over the padding (TF:models/whisper/modeling_whisper.py:612-616)."""
+        return self._ragged_encoder
+
+    @ragged_encoder.setter
+    def ragged_encoder(self, on):
+        if on and isinstance(self.audio_tower, WhisperEncoderMI355X):
+            raise ValueError(f"ragged_encoder is not available for the Whisper audio tower ({type(self.audio_tower).__name__}): Whisper "
+                             "encodes a fixed 30 s window and attends to its padding (TF:models/whisper/modeling_whisper.py:612-616); "
+                             "only the GLM-ASR tower encodes clips at their own lengths")
+        self._ragged_encoder = bool(on)
+
+    def _mel_lengths(self, audio_features, audio_attention_mask):
+        """The ragged encoder's per-clip mel lengths as host ints (None with the switch off); ValueError on a missing mask or a
+        length outside [1, T]."""
+        if not self._ragged_encoder:
+            return None
+        if audio_attention_mask is None:
+            raise ValueError("ragged_encoder=True needs audio_attention_mask: the clips' mel lengths are its row sums")
+        B, _, T = audio_features.shape
+        mask = torch.as_tensor(audio_attention_mask)
+        if mask.dim() != 2 or mask.shape[0] != B or mask.shape[1] != T:
+            raise ValueError(f"audio_attention_mask must be [{B}, {T}] like input_features' clips and frames; got {tuple(mask.shape)}")
+        return self.audio_tower.check_mel_lengths(mask.sum(dim=-1), B, T)        # one sync if the mask is on the device
 
     def _apply_stream_modes(self):
         """``config.model_dtype`` decides where the residual streams are STORED, as it does in the reference: "bfloat16" (the
@@ -310,14 +345,19 @@ class ASRModel(nn.Module):
         self._drop_seed += 1
         return ops.bernoulli_keep(B * S, 1.0 - p, self._drop_seed, self.device_)
 
-    def _encode_audio(self, audio_features, frame_keep=None, after_encoder=None):
+    def _encode_audio(self, audio_features, frame_keep=None, after_encoder=None, audio_attention_mask=None):
         """-> projector output [B, N, llm_dim] fp32 (packing into <audio> rows happens in the LM op).
         ``after_encoder``: called between the frozen encoder and the projector -- the last point of a step that has not
-        read a trainable weight yet (ASRTrainer applies a deferred optimizer update there)."""
+        read a trainable weight yet (ASRTrainer applies a deferred optimizer update there).
+        ``audio_attention_mask``: read only with ``ragged_encoder`` on (the clips' own lengths)."""
         B, _, T = audio_features.shape
         S = self.audio_tower.output_length(T)
+        mel_lengths = self._mel_lengths(audio_features, audio_attention_mask)
         keep = self._frame_keep_mask(B, S, frame_keep)
-        hidden = self.audio_tower(audio_features, frame_keep=keep).last_hidden_state      # no_grad inside
+        if mel_lengths is not None:
+            hidden = self.audio_tower(audio_features, frame_keep=keep, mel_lengths=mel_lengths).last_hidden_state
+        else:
+            hidden = self.audio_tower(audio_features, frame_keep=keep).last_hidden_state      # no_grad inside
         if after_encoder is not None:
             after_encoder()
         return self.projector(hidden)
@@ -395,7 +435,7 @@ class ASRModel(nn.Module):
         if input_features is None and after_encoder is not None:
             after_encoder()
         if input_features is not None:
-            y = self._encode_audio(input_features.to(dev), frame_keep, after_encoder)     # [B, N, D]
+            y = self._encode_audio(input_features.to(dev), frame_keep, after_encoder, audio_attention_mask)     # [B, N, D]
             N = y.shape[1]
             if sid is not None:
                 placed = self._segment_placeholder_counts(ids, sid, n_clips)
@@ -539,7 +579,7 @@ class ASRModel(nn.Module):
         amask = audio_attention_mask.to(dev)
         enc_len = self._compute_encoder_output_lengths(amask)
         counts = self.projector.get_output_length(enc_len).to(device=dev, dtype=torch.int64).contiguous()
-        y = self._encode_audio(feats)                                                   # [B, N, D]
+        y = self._encode_audio(feats, audio_attention_mask=audio_attention_mask)        # [B, N, D]
         N = y.shape[1]
         if input_ids is None:
             if self.tokenizer is None:

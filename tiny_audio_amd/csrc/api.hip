@@ -137,6 +137,92 @@ int enc_forward(const EncDesc& w, const float* feats, int B, int T, const float*
   RC(ln(w.norm_w, w.norm_b, out_bf16, out_f32, frame_keep));
   return TA_OK;
 }
+
+// ---- ragged encoder: every clip at its own length (GLM-ASR tower only; opt-in, not in the reference's training arithmetic)
+// The stem's buffers keep the padded shape (its two row-mapped GEMMs run as they do above); everything from the residual stream on is
+// carved at rows = sum of S_b.  The final LayerNorm's compact outputs reuse xn (bf16) and qkv (f32): both are free behind the loop.
+struct EncRaggedWs {
+  bf16_t *x0, *x1, *xn, *qkv, *ao, *hf;
+  void* c2;      // conv2's output [B*S, H] in the stream's dtype, before compaction
+  float *xr, *rope;
+  size_t bytes;
+};
+EncRaggedWs enc_ragged_carve(const EncDesc& d, int B, int T, long rows, void* base) {
+  const int H = d.H, S = (T - 1) / 2 + 1;
+  const long M = (long)B * S;
+  Carver c(base);
+  EncRaggedWs e;
+  e.x0 = c.take<bf16_t>((size_t)B * (T + 2) * d.NM + (size_t)(d.k1 - 3 * d.NM));
+  e.x1 = c.take<bf16_t>((size_t)B * (T + 2) * H);
+  e.c2 = c.take<float>((size_t)M * H);              // the fp32 size whatever the mode: sizes do not depend on res_f32 (ta355.h)
+  e.xr = c.take<float>((size_t)rows * H);
+  e.rope = c.take<float>((size_t)rows * 32);
+  e.xn = c.take<bf16_t>((size_t)rows * H);
+  e.qkv = c.take<bf16_t>((size_t)rows * 3 * H);
+  e.ao = c.take<bf16_t>((size_t)rows * H);
+  e.hf = c.take<bf16_t>((size_t)rows * d.F);
+  e.bytes = c.total();
+  return e;
+}
+
+int enc_forward_ragged(const EncDesc& w, const float* feats, int B, int T, const int* mel_len, const int* cu, const float* frame_keep,
+                       void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st) {
+  if (B <= 0 || T <= 0) return TA_OK;
+  const int H = w.H, F = w.F, NM = w.NM, nh = w.nh, K1 = w.k1;
+  if (H % 128 || F % 128 || K1 % 64 || NM % 8 || H / nh != 64 || (!out_bf16 && !out_f32) || !mel_len || !cu || !feats) return TA_ERR_ARG;
+  if (!w.rope_il) return TA_ERR_ARG;                 // the one-GEMM q|k|v path only
+  if (K1 != 3 * NM) return TA_ERR_ARG;               // no K padding behind conv1's three taps (GLM-ASR): x0 carries no slack to zero
+  for (int l = 0; l < w.L; ++l) if (!(w.layers[l].wqkv_fa && w.layers[l].bqkv_fa)) return TA_ERR_ARG;
+  const int S = (T - 1) / 2 + 1;
+  if (S > w.max_pos) return TA_ERR_ARG;
+  long rows_l = 0; int max_rows = 0;
+  for (int b = 0; b < B; ++b) {
+    if (mel_len[b] < 1 || mel_len[b] > T) return TA_ERR_ARG;
+    const int Sb = (mel_len[b] - 1) / 2 + 1;
+    rows_l += Sb; max_rows = Sb > max_rows ? Sb : max_rows;
+  }
+  if (rows_l > 0x7fffffffL / (3L * H)) return TA_ERR_ARG;
+  const int rows = (int)rows_l;
+  EncRaggedWs e = enc_ragged_carve(w, B, T, rows, ws);
+  if ((long)e.bytes > ws_bytes) return TA_ERR_ARG;
+  // stem: the padded shape, with every clip's own end as the convolutions' zero padding
+  RC(ta_i_feats_to_time_major_len(feats, e.x0, B, NM, T, mel_len, st));
+  RC(ta_gemm_bf16_nt(e.x0, w.conv1_w, e.x1, B * T, H, K1, NM, T, (long)(T + 2) * NM, H, T, (long)(T + 2) * H, H,
+                     w.conv1_b, nullptr, 1, 1, 1, nullptr, st));
+  RC(ta_i_zero_tail_rows(e.x1, B, T, H, mel_len, st));      // behind conv1: its rows t >= T_b hold gelu(bias), conv2 must meet zeros
+  const bool res_f32 = w.res_f32 != 0;
+  const int rb = res_f32 ? 0 : 1;
+  RC(ta_gemm_bf16_nt(e.x1, w.conv2_w, e.c2, B * S, H, 3 * H, 2L * H, S, (long)(T + 2) * H, H, 0, 0, 0, w.conv2_b, nullptr,
+                     1, rb, 1, nullptr, st));
+  RC(ta_i_compact_rows(e.c2, e.xr, cu, B, S, rows, H * (rb ? 2 : 4), st));
+  RC(ta_i_rope_rows(w.rope_il, e.rope, cu, B, rows, w.max_pos, st));
+  const int M = rows;
+  auto ln = [&](const float* gw, const float* gb, void* yb, float* yf) -> int {
+    return rb ? ta_layernorm_bf16(e.xr, gw, gb, yb, yf, nullptr, M, H, w.eps, st)
+              : ta_layernorm_f32(e.xr, gw, gb, yb, yf, nullptr, M, H, w.eps, st);
+  };
+  auto res_gemm = [&](const void* A, const void* Wm, int K, const float* bias) -> int {      // xr += A Wm^T + bias
+    if (rb) { ta_gemm_opts o = opts_none(); o.residual_bf16 = e.xr; return gemm_opt(A, Wm, e.xr, M, H, K, bias, nullptr, 0, 1, o, st); }
+    return gemm(A, Wm, e.xr, M, H, K, bias, e.xr, 0, 0, st);
+  };
+  for (int l = 0; l < w.L; ++l) {
+    const ta_enc_layer& L = w.layers[l];
+    RC(ln(L.ln1_w, L.ln1_b, e.xn, nullptr));
+    // the per-row table makes the epilogue's m % rope_rows the identity: row m rotates by its position inside its own clip
+    ta_gemm_opts o = opts_none(); o.rope_tab = e.rope; o.rope_rows = rows; o.rope_cols = 2 * H;
+    RC(gemm_opt(e.xn, L.wqkv_fa, e.qkv, M, 3 * H, H, L.bqkv_fa, nullptr, 2, 1, o, st));
+    RC(ta_attention_enc_fwd_varlen(e.qkv, e.ao, cu, B, nh, max_rows, st));
+    RC(res_gemm(e.ao, L.wo, H, L.bo));
+    RC(ln(L.ln2_w, L.ln2_b, e.xn, nullptr));
+    RC(gemm(e.xn, L.w1, e.hf, M, F, H, L.b1, nullptr, 1, 1, st));
+    RC(res_gemm(e.hf, L.w2, F, L.b2));
+  }
+  bf16_t* yb = out_bf16 ? e.xn : nullptr;
+  float* yf = out_f32 ? (float*)e.qkv : nullptr;
+  RC(ln(w.norm_w, w.norm_b, yb, yf));
+  RC(ta_i_expand_rows(yb, yf, out_bf16, out_f32, cu, frame_keep, B, S, rows, H, st));
+  return TA_OK;
+}
 }  // namespace
 
 extern "C" long ta_encoder_workspace_bytes(const ta_encoder_weights* w, int B, int T) {
@@ -145,6 +231,14 @@ extern "C" long ta_encoder_workspace_bytes(const ta_encoder_weights* w, int B, i
 extern "C" int ta_encoder_forward(const ta_encoder_weights* w, const float* feats, int B, int T, const float* frame_keep,
                                   void* out_bf16, float* out_f32, void* ws, long ws_bytes, hipStream_t st) {
   return enc_forward(enc_desc(w), feats, B, T, frame_keep, out_bf16, out_f32, ws, ws_bytes, st);
+}
+extern "C" long ta_encoder_ragged_workspace_bytes(const ta_encoder_weights* w, int B, int T, long rows) {
+  return (long)enc_ragged_carve(enc_desc(w), B, T, rows < 0 ? 0 : rows, nullptr).bytes;
+}
+extern "C" int ta_encoder_forward_ragged(const ta_encoder_weights* w, const float* feats, int B, int T, const int* mel_len_host,
+                                         const int* cu_rows_dev, const float* frame_keep, void* out_bf16, float* out_f32, void* ws,
+                                         long ws_bytes, hipStream_t st) {
+  return enc_forward_ragged(enc_desc(w), feats, B, T, mel_len_host, cu_rows_dev, frame_keep, out_bf16, out_f32, ws, ws_bytes, st);
 }
 extern "C" long ta_whisper_encoder_workspace_bytes(const ta_whisper_encoder_weights* w, int B, int T) {
   return (long)enc_carve(enc_desc(w), B, T, nullptr).bytes;

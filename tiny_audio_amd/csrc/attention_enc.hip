@@ -78,19 +78,30 @@ __device__ __forceinline__ bf16x8 read_vfrag_tr(const char* vt, int dt, int l15,
 }
 
 // One workgroup = 64 * QSUB query rows of one (clip, head): 4 waves x QSUB sub-tiles of 16 rows.
-template <int QSUB>
+// VARLEN (ragged encoder): clip b owns rows cu[b] .. cu[b + 1] of the token-major buffers instead of b * L .. (b + 1) * L; Lmax (the
+// longest clip) sizes the grid, a workgroup whose query tile lies past its own clip's end returns, and everything below runs on
+// the clip's own L -- the clamps of the ragged last key tile and of the query rows included, so no row of another clip is ever
+// loaded.  Per (clip, head, query tile) the arithmetic is that of the fixed-length instantiation at B = 1, S = L.
+template <int QSUB, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_enc_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ O, int B, int NH,
-                                                           int L, long rs) {
+                                                           int Lmax, long rs, const int* __restrict__ cu) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];       // [buffer][K | V]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
   constexpr int QROWS = 64 * QSUB;
-  const int nq = (L + QROWS - 1) / QROWS;
+  const int nq = (Lmax + QROWS - 1) / QROWS;
   int group, qt;
   if (!decode_group(blockIdx.x, nq, B * NH, group, qt)) return;
   const int b = group / NH, h = group % NH;
+  // VARLEN: the clip's own row range; the fixed-length instantiation keeps its expressions (and its code) as they were
+  [[maybe_unused]] long row0 = 0;                                     // first token row of the clip
+  if constexpr (VARLEN) row0 = cu[b];
+  const int L = VARLEN ? cu[b + 1] - (int)row0 : Lmax;
+  if constexpr (VARLEN) {
+    if (qt * QROWS >= L) return;                                      // before any barrier: the whole workgroup leaves
+  }
   const int q0 = qt * QROWS + wave * 16 * QSUB;                       // first query row of this wave
   const int Hd = NH * HD;
-  const bf16_t* Qb = qkv + (long)b * L * rs + h * HD;                 // q | k | v of this head: columns h*64 of each third
+  const bf16_t* Qb = qkv + (VARLEN ? row0 : (long)b * L) * rs + h * HD;   // q | k | v of this head: columns h*64 of each third
   const bf16_t* Kb = Qb + Hd;
   const int ntiles = (L + KT - 1) / KT;
 
@@ -240,7 +251,7 @@ __global__ __launch_bounds__(256) void attn_enc_fwd_kernel(const bf16_t* __restr
     const int row = i * 8 + (lane >> 3), p = lane & 7;
     const uint4 v = *(const uint4*)(stage + row * 128 + ((p ^ kswz(row)) << 4));
     const int qrow = q0 + row;
-    if (qrow < L) *(uint4*)(O + ((long)b * L + qrow) * Hd + h * HD + p * 8) = v;
+    if (qrow < L) *(uint4*)(O + ((VARLEN ? row0 : (long)b * L) + qrow) * Hd + h * HD + p * 8) = v;
   }
 }
 }  // namespace
@@ -253,7 +264,21 @@ extern "C" int ta_attention_enc_fwd(const void* qkv, void* out, int B, int heads
   constexpr int QSUB = 2;
   const int nq = (S + 64 * QSUB - 1) / (64 * QSUB);
   TA_LAUNCH((attn_enc_fwd_kernel<QSUB>), dim3(grouped_grid(nq, B * heads)), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)out, B,
-            heads, S, rs);
+            heads, S, rs, (const int*)nullptr);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// The same over clips of different lengths (the ragged encoder): clip b owns rows cu_rows[b] .. cu_rows[b + 1] of qkv [rows, 3*heads*64]
+// and of out [rows, heads*64]; cu_rows is a DEVICE int [B + 1] (non-decreasing, cu_rows[0] = 0), max_rows the longest clip's row count
+// (it sizes the grid; a clip longer than max_rows would lose its tail rows).  Attention stays inside a clip.
+extern "C" int ta_attention_enc_fwd_varlen(const void* qkv, void* out, const int* cu_rows, int B, int heads, int max_rows, hipStream_t st) {
+  if (B <= 0 || heads <= 0 || max_rows <= 0 || !cu_rows) return TA_ERR_ARG;
+  const long rs = 3L * heads * HD;
+  constexpr int QSUB = 2;
+  const int nq = (max_rows + 64 * QSUB - 1) / (64 * QSUB);
+  TA_LAUNCH((attn_enc_fwd_kernel<QSUB, true>), dim3(grouped_grid(nq, B * heads)), dim3(256), 0, st, (const bf16_t*)qkv, (bf16_t*)out,
+            B, heads, max_rows, rs, cu_rows);
   TA_CHECK_LAUNCH();
   return TA_OK;
 }

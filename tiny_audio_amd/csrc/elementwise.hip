@@ -1,5 +1,6 @@
 // ta355 element-wise / data-movement kernels (all HBM-bound; 8-16 B per lane, grid-stride).
 #include "common.h"
+#include "internal.h"
 
 static inline int ew_blocks(long n, int per_block = 256) {
   long b = (n + per_block - 1) / per_block;
@@ -145,6 +146,89 @@ __global__ void zero_pad_rows_kernel(bf16_t* __restrict__ buf, int T, int C) {
     buf[((long)b * (T + 2)) * C + c] = 0;
     buf[((long)b * (T + 2) + T + 1) * C + c] = 0;
   }
+}
+
+// ---------------------------------------------------------------------------- ragged encoder (clips of different lengths)
+// The stem's two kernels receive the clips' mel lengths BY VALUE, RAGGED_CHUNK clips per launch: the composite has them on the host
+// and may neither copy nor allocate.  The kernels behind the stem read the device table cu [B + 1] of first compact rows instead.
+// feats f32 [B, C, T] -> bf16 time-major [B, T+2, C] as feats_to_tm_kernel, frames t >= len[b] written as zero WITHOUT being read
+// (a select on the load: whatever lies in the padding, NaN included, never enters arithmetic).
+__global__ __launch_bounds__(256) void feats_to_tm_len_kernel(const float* __restrict__ f, bf16_t* __restrict__ out, int C, int T, int b0,
+                                                              RaggedLens lens) {
+  __shared__ float tile[64][65];
+  const int b = b0 + blockIdx.z, t0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+  const int Tb = lens.len[blockIdx.z];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int i = ty; i < 64; i += 4) {
+    const int c = c0 + i, t = t0 + tx;
+    float v = 0.f;
+    if (c < C && t < Tb) v = f[((long)b * C + c) * T + t];
+    tile[i][tx] = v;
+  }
+  __syncthreads();
+  for (int i = ty; i < 64; i += 4) {
+    const int t = t0 + i, c = c0 + tx;
+    if (t < T && c < C) out[((long)b * (T + 2) + t + 1) * C + c] = f2bf(tile[tx][i]);
+  }
+  if (blockIdx.x == 0 && ty == 0 && c0 + tx < C) {
+    out[((long)b * (T + 2)) * C + c0 + tx] = 0;
+    out[((long)b * (T + 2) + T + 1) * C + c0 + tx] = 0;
+  }
+}
+// conv1's output [B, T+2, C] bf16 (frame t at row t + 1): zero row 0 and the rows of frames t >= len[b] up to row T + 1 -- conv2 of
+// a clip encoded alone meets zero padding behind its last frame, not gelu(conv1(bias)).  blockIdx = (row chunk, clip of the launch).
+__global__ __launch_bounds__(256) void zero_tail_rows_kernel(bf16_t* __restrict__ buf, int T, int C, int b0, RaggedLens lens) {
+  const int b = b0 + blockIdx.y, Tb = lens.len[blockIdx.y];
+  const int cpr = C / 8;                                           // 16-byte chunks per row
+  const long ntail = (long)(T + 1 - Tb) * cpr;                     // rows Tb + 1 .. T + 1
+  uint4* base = (uint4*)(buf + (long)b * (T + 2) * C);
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < ntail; i += (long)gridDim.x * 256) base[(long)(Tb + 1) * cpr + i] = z;
+  if (blockIdx.x == 0) for (int i = threadIdx.x; i < cpr; i += 256) base[i] = z;
+}
+// clip of compact row m: the largest b with cu[b] <= m (cu non-decreasing, cu[0] = 0, cu[B] = rows > m)
+__device__ __forceinline__ int clip_of_row(const int* __restrict__ cu, int B, int m) {
+  int lo = 0, hi = B;
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cu[mid] <= m) lo = mid; else hi = mid; }
+  return lo;
+}
+// dst [rows, row_bytes] <- the real rows [b, 0:S_b) of src [B, S, row_bytes], back to back (conv2's output into the residual stream)
+__global__ __launch_bounds__(256) void compact_rows_kernel(const char* __restrict__ src, char* __restrict__ dst,
+                                                           const int* __restrict__ cu, int B, int S, int rows, int row_bytes) {
+  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (m >= rows) return;
+  const int b = clip_of_row(cu, B, m), s = m - cu[b];
+  if (s < 0 || s >= S) return;                                     // a table that disagrees with the launch geometry: write nothing
+  const uint4* in = (const uint4*)(src + ((long)b * S + s) * row_bytes);
+  uint4* out = (uint4*)(dst + (long)m * row_bytes);
+  for (int c = threadIdx.x & 63; c < row_bytes / 16; c += 64) out[c] = in[c];
+}
+// tab [rows][16][2] <- rope_il [max_pos][16][2], compact row m taking the entry of m's position inside its clip: the q|k|v GEMM's
+// epilogue reads table row m % rope_rows, and with rope_rows = rows that is m
+__global__ __launch_bounds__(256) void rope_rows_kernel(const float* __restrict__ rope_il, float* __restrict__ tab,
+                                                        const int* __restrict__ cu, int B, int rows, int max_pos) {
+  const int m = blockIdx.x * 32 + (threadIdx.x >> 3);
+  if (m >= rows) return;
+  int pos = m - cu[clip_of_row(cu, B, m)];
+  pos = pos < 0 ? 0 : (pos < max_pos ? pos : max_pos - 1);
+  ((float4*)(tab + (long)m * 32))[threadIdx.x & 7] = ((const float4*)(rope_il + (long)pos * 32))[threadIdx.x & 7];
+}
+// padded out [B, S, H] <- compact y [rows, H]: row (b, s) takes compact row cu[b] + s while s < S_b and the frame is kept
+// (keep == NULL or keep[b * S + s] != 0), and exact zeros otherwise -- a select, so a dropped or padding row never depends on data
+__global__ __launch_bounds__(256) void expand_rows_kernel(const bf16_t* __restrict__ yb, const float* __restrict__ yf,
+                                                          bf16_t* __restrict__ ob, float* __restrict__ of, const int* __restrict__ cu,
+                                                          const float* __restrict__ keep, int B, int S, int rows, int H) {
+  const long p = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (p >= (long)B * S) return;
+  const int b = (int)(p / S), s = (int)(p % S);
+  const int c0 = cu[b], Sb = cu[b + 1] - c0;
+  const long m = (long)c0 + s;
+  const bool real = s < Sb && c0 >= 0 && m < rows && (!keep || keep[p] != 0.f);
+  const int lane = threadIdx.x & 63;
+  if (ob) for (int c = lane; c < H / 8; c += 64)
+    ((uint4*)(ob + p * H))[c] = real ? ((const uint4*)(yb + m * H))[c] : make_uint4(0, 0, 0, 0);
+  if (of) for (int c = lane; c < H / 4; c += 64)
+    ((float4*)(of + p * H))[c] = real ? ((const float4*)(yf + m * H))[c] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // ---------------------------------------------------------------------------- Whisper position table
@@ -384,6 +468,44 @@ extern "C" int ta_feats_to_time_major(const float* feats, void* out, int B, int 
 extern "C" int ta_zero_pad_rows(void* buf, int B, int T, int C, hipStream_t st) {
   if (B <= 0) return TA_OK;
   TA_LAUNCH(zero_pad_rows_kernel, dim3(B), dim3(256), 0, st, (bf16_t*)buf, T, C);
+  TA_CHECK_LAUNCH(); return TA_OK;
+}
+// ---- ragged encoder helpers (internal.h)
+int ta_i_feats_to_time_major_len(const float* feats, void* out, int B, int C, int T, const int* len_host, hipStream_t st) {
+  for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
+    const int n = B - b0 < RAGGED_CHUNK ? B - b0 : RAGGED_CHUNK;
+    RaggedLens l;
+    for (int i = 0; i < RAGGED_CHUNK; ++i) l.len[i] = i < n ? len_host[b0 + i] : 0;
+    TA_LAUNCH(feats_to_tm_len_kernel, dim3(ta_cdiv(T, 64), ta_cdiv(C, 64), n), dim3(256), 0, st, feats, (bf16_t*)out, C, T, b0, l);
+    TA_CHECK_LAUNCH();
+  }
+  return TA_OK;
+}
+int ta_i_zero_tail_rows(void* buf, int B, int T, int C, const int* len_host, hipStream_t st) {
+  if (C % 8) return TA_ERR_ARG;
+  for (int b0 = 0; b0 < B; b0 += RAGGED_CHUNK) {
+    const int n = B - b0 < RAGGED_CHUNK ? B - b0 : RAGGED_CHUNK;
+    RaggedLens l;
+    for (int i = 0; i < RAGGED_CHUNK; ++i) l.len[i] = i < n ? len_host[b0 + i] : T;
+    TA_LAUNCH(zero_tail_rows_kernel, dim3(8, n), dim3(256), 0, st, (bf16_t*)buf, T, C, b0, l);
+    TA_CHECK_LAUNCH();
+  }
+  return TA_OK;
+}
+int ta_i_compact_rows(const void* src, void* dst, const int* cu, int B, int S, int rows, int row_bytes, hipStream_t st) {
+  if (row_bytes % 16) return TA_ERR_ARG;
+  TA_LAUNCH(compact_rows_kernel, dim3(ta_cdiv(rows, 4)), dim3(256), 0, st, (const char*)src, (char*)dst, cu, B, S, rows, row_bytes);
+  TA_CHECK_LAUNCH(); return TA_OK;
+}
+int ta_i_rope_rows(const float* rope_il, float* tab, const int* cu, int B, int rows, int max_pos, hipStream_t st) {
+  TA_LAUNCH(rope_rows_kernel, dim3(ta_cdiv(rows, 32)), dim3(256), 0, st, rope_il, tab, cu, B, rows, max_pos);
+  TA_CHECK_LAUNCH(); return TA_OK;
+}
+int ta_i_expand_rows(const void* y_bf16, const float* y_f32, void* out_bf16, float* out_f32, const int* cu, const float* keep, int B,
+                     int S, int rows, int H, hipStream_t st) {
+  if (H % 8) return TA_ERR_ARG;
+  TA_LAUNCH(expand_rows_kernel, dim3((unsigned)(((long)B * S + 3) / 4)), dim3(256), 0, st, (const bf16_t*)y_bf16, y_f32,
+            (bf16_t*)out_bf16, out_f32, cu, keep, B, S, rows, H);
   TA_CHECK_LAUNCH(); return TA_OK;
 }
 extern "C" int ta_audio_index(const long* ids, const long* counts, int* src_row, int B, int L, int N, long audio_id,

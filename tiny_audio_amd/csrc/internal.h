@@ -57,3 +57,14 @@ int ta_i_dec_attn(const void* qkv0, const float* qn_w, const float* kn_w, const 
 // ([K/32][32 rows][32]; buffers hold 32 rows whatever B is): x / res / out of the calls above are in that layout.
 int ta_i_dec_embed(const long* ids, const float* emb, float* xblk, int B, int D, long vocab, hipStream_t st);
 int ta_i_dec_final_norm(const float* xblk, const float* w, void* y, int B, int D, float eps, hipStream_t st);
+
+// ragged encoder (api.hip enc_forward_ragged; kernels in elementwise.hip).  The two stem kernels take the clips' mel lengths from
+// the HOST array, RAGGED_CHUNK of them per launch as a by-value kernel argument; the others read the device table cu [B + 1].
+constexpr int RAGGED_CHUNK = 128;
+struct RaggedLens { int len[RAGGED_CHUNK]; };
+int ta_i_feats_to_time_major_len(const float* feats, void* out, int B, int C, int T, const int* len_host, hipStream_t st);   // ta_feats_to_time_major, frames t >= len[b] zero and never read
+int ta_i_zero_tail_rows(void* buf, int B, int T, int C, const int* len_host, hipStream_t st);   // [B, T+2, C] bf16: zero row 0 and rows len[b] + 1 .. T + 1
+int ta_i_compact_rows(const void* src, void* dst, const int* cu, int B, int S, int rows, int row_bytes, hipStream_t st);   // dst [rows] <- src [B, S] rows [b, 0:S_b)
+int ta_i_rope_rows(const float* rope_il, float* tab, const int* cu, int B, int rows, int max_pos, hipStream_t st);   // tab [rows][16][2]: row m <- position of m inside its clip
+int ta_i_expand_rows(const void* y_bf16, const float* y_f32, void* out_bf16, float* out_f32, const int* cu, const float* keep, int B,
+                     int S, int rows, int H, hipStream_t st);   // padded [B, S, H] <- compact rows; zeros on padding rows and on frames with keep == 0

@@ -40,6 +40,10 @@ class GlmAsrEncoderMI355X(torch.nn.Module):
         self._w = None
         self._ws = None
         self._ws_key = None
+        self._rws = None         # workspace of the ragged path, cached per (B, T, rows)
+        self._rws_key = None
+        self._cu = None          # device table of first compact rows, cached per tuple of lengths
+        self._cu_key = None
         self.out_dtype = BF16
         self._res_f32 = False    # storage of the residual stream (ta_encoder_weights.res_f32): bf16 unless the owner asks for fp32
 
@@ -195,13 +199,35 @@ class GlmAsrEncoderMI355X(torch.nn.Module):
     def output_length(self, T):
         return (T - 1) // 2 + 1
 
+    @staticmethod
+    def check_mel_lengths(mel_lengths, B, T):
+        """-> the clips' mel lengths as a list of B host ints, each in [1, T]; ValueError otherwise.  A tensor is read back to the
+        host here (one device sync if it lives on the device)."""
+        if isinstance(mel_lengths, torch.Tensor):
+            mel_lengths = mel_lengths.detach().reshape(-1).to("cpu").tolist()
+        lens = [int(v) for v in mel_lengths]
+        if len(lens) != B:
+            raise ValueError(f"mel_lengths holds {len(lens)} lengths for a batch of {B} clips")
+        bad = [(i, v) for i, v in enumerate(lens) if v < 1 or v > T]
+        if bad:
+            raise ValueError(f"mel_lengths must lie in [1, {T}] (the feature width); got {bad[0][1]} for clip {bad[0][0]}")
+        return lens
+
     @torch.no_grad()
-    def forward(self, input_features, frame_keep=None, return_f32=False, **_):
-        """model.audio_tower(input_features=...).last_hidden_state through torch.ops.ta355.encoder_forward."""
+    def forward(self, input_features, frame_keep=None, return_f32=False, mel_lengths=None, **_):
+        """model.audio_tower(input_features=...).last_hidden_state through torch.ops.ta355.encoder_forward.
+
+        ``mel_lengths`` (B ints, or an integer tensor; ``audio_attention_mask.sum(-1)``) switches to the ragged encoder
+        (torch.ops.ta355.encoder_forward_ragged): every clip is encoded as if alone at its own length, rows behind a clip's end
+        are zeros.  ``None``: the reference's padded call, unchanged."""
         from . import torch_ops
         x = input_features.to(device=self.device_, dtype=F32)
         if frame_keep is not None:
             frame_keep = frame_keep.to(device=self.device_, dtype=F32).contiguous()
+        if mel_lengths is not None:
+            lens = self.check_mel_lengths(mel_lengths, x.shape[0], x.shape[2])
+            return BaseModelOutput(torch.ops.ta355.encoder_forward_ragged(x, lens, frame_keep, torch_ops.register_module(self),
+                                                                          bool(return_f32)))
         return BaseModelOutput(torch.ops.ta355.encoder_forward(x, frame_keep, torch_ops.register_module(self), bool(return_f32)))
 
     def _forward_impl(self, input_features, frame_keep=None, return_f32=False):
@@ -221,4 +247,33 @@ class GlmAsrEncoderMI355X(torch.nn.Module):
             frame_keep = frame_keep.to(device=self.device_, dtype=F32).contiguous()
         _lib.check(_lib.lib().ta_encoder_forward(C.byref(self._w), ptr(x), B, T, ptr(frame_keep), ptr(out_b), ptr(out_f),
                                                  ptr(self._ws), self._ws.numel(), stream()), "ta_encoder_forward")
+        return out_f if return_f32 else out_b
+
+    def _forward_ragged_impl(self, input_features, mel_lengths, frame_keep=None, return_f32=False):
+        if self._w is None:
+            raise _lib.Ta355Error("encoder weights not loaded (load_state_dict_hf / random_init)")
+        x = input_features.to(device=self.device_, dtype=F32).contiguous()
+        B, _, T = x.shape
+        lens = self.check_mel_lengths(mel_lengths, B, T)
+        S, H = self.output_length(T), self.config.hidden_size
+        cu = [0]
+        for t in lens:
+            cu.append(cu[-1] + self.output_length(t))
+        rows = cu[-1]
+        key = (B, T, rows)
+        if self._rws_key != key:
+            n = _lib.lib().ta_encoder_ragged_workspace_bytes(C.byref(self._w), B, T, rows)
+            self._rws = torch.empty(n, device=self.device_, dtype=torch.uint8)
+            self._rws_key = key
+        if self._cu_key != tuple(lens):          # the device table the kernels read (ta355.h: built by the binding)
+            self._cu = torch.tensor(cu, dtype=torch.int32).to(self.device_)
+            self._cu_key = tuple(lens)
+        out_b = torch.empty((B, S, H), device=self.device_, dtype=BF16)
+        out_f = torch.empty((B, S, H), device=self.device_, dtype=F32) if return_f32 else None
+        if frame_keep is not None:
+            frame_keep = frame_keep.to(device=self.device_, dtype=F32).contiguous()
+        host_lens = (C.c_int * B)(*lens)
+        _lib.check(_lib.lib().ta_encoder_forward_ragged(C.byref(self._w), ptr(x), B, T, host_lens, ptr(self._cu), ptr(frame_keep),
+                                                        ptr(out_b), ptr(out_f), ptr(self._rws), self._rws.numel(), stream()),
+                   "ta_encoder_forward_ragged")
         return out_f if return_f32 else out_b

@@ -226,6 +226,20 @@ def attention_enc_fwd(qkv, B, heads, S):
     return out
 
 
+def attention_enc_fwd_varlen(qkv, cu_rows, heads, max_rows, out=None):
+    """The same over clips of different lengths (ta_attention_enc_fwd_varlen): clip b owns rows ``cu_rows[b] .. cu_rows[b + 1]``
+    of qkv bf16 [rows, 3*heads*64]; ``cu_rows`` int32 [B + 1] on the device, ``max_rows`` the longest clip.  ``out``: a bf16
+    [rows, heads*64] tensor to write into."""
+    _req(qkv, BF16)
+    assert qkv.dim() == 2 and qkv.shape[1] == 3 * heads * 64
+    assert cu_rows.dtype == torch.int32 and cu_rows.is_contiguous() and cu_rows.device == qkv.device
+    if out is None:
+        out = torch.empty((qkv.shape[0], heads * 64), device=qkv.device, dtype=BF16)
+    check(lib().ta_attention_enc_fwd_varlen(ptr(qkv), ptr(out), ptr(cu_rows), cu_rows.numel() - 1, heads, int(max_rows), stream()),
+          "ta_attention_enc_fwd_varlen")
+    return out
+
+
 def attention_fwd_seg(Q, K, VT, L, scale, kmask=None, seg=None, want_lse=True, out=None):
     """ta_attention_fwd_seg: the causal head_dim-128 forward over packed rows (``seg``: the table of ``segment_table``; None = the
     plain causal ``attention_fwd``).  Shapes as ``attention_fwd``."""

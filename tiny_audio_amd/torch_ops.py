@@ -7,6 +7,8 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
+    ta355::encoder_forward_ragged   the same seam, every clip at its own length (opt-in; what the reference computes for a
+                               clip encoded alone, tiny_audio/asr_modeling.py:198-200)
     ta355::whisper_encoder_forward  the same seam with a Whisper tower    tiny_audio/asr_modeling.py:203-237
     ta355::mlp_projector       MLPAudioProjector.forward   (+ autograd)   tiny_audio/projectors.py:57-71
     ta355::moe_projector       MoEAudioProjector.forward   (+ autograd)   tiny_audio/projectors.py:257-347
@@ -133,6 +135,22 @@ def encoder_forward(input_features: Tensor, frame_keep: Optional[Tensor], handle
 
 @encoder_forward.register_fake
 def _(input_features, frame_keep, handle, return_f32):
+    enc = module_of(handle)
+    B, _, T = input_features.shape
+    return input_features.new_empty((B, enc.output_length(T), enc.config.hidden_size), dtype=F32 if return_f32 else BF16)
+
+
+@torch.library.custom_op("ta355::encoder_forward_ragged", mutates_args=())
+def encoder_forward_ragged(input_features: Tensor, mel_lengths: List[int], frame_keep: Optional[Tensor], handle: int,
+                           return_f32: bool) -> Tensor:
+    """The GLM-ASR tower with every clip encoded at its own length (not in the reference's training forward; opt-in): rows
+    [b, :S_b] = the encoder applied to ``input_features[b:b+1, :, :mel_lengths[b]]`` alone, rows [b, S_b:] and dropped frames exact
+    zeros, the padded [B, (T-1)//2+1, H] layout of ``encoder_forward``.  The lengths are host integers: they size the launches."""
+    return module_of(handle)._forward_ragged_impl(input_features, mel_lengths, frame_keep, return_f32)
+
+
+@encoder_forward_ragged.register_fake
+def _(input_features, mel_lengths, frame_keep, handle, return_f32):
     enc = module_of(handle)
     B, _, T = input_features.shape
     return input_features.new_empty((B, enc.output_length(T), enc.config.hidden_size), dtype=F32 if return_f32 else BF16)
@@ -594,4 +612,4 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
-             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain")
+             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged")
