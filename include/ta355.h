@@ -760,6 +760,37 @@ long ta_wave_sos_ws_bytes(int B, int Ls, int chunk);
 int ta_wave_sos_f32(float* wav, const long* lens, int B, int Ls, const int* n_sec, const double* sos, int chunk, void* ws,
                     long ws_bytes, hipStream_t st);
 
+/* ---- forced alignment of CTC emissions against a token sequence, for word timestamps (tiny_audio_amd/csrc/align.hip).  Replaces
+ * ForcedAligner._get_trellis and ._backtrack (tiny_audio/alignment.py:47-152), which the reference's pipeline calls per clip from
+ * ForcedAligner.align (tiny_audio/alignment.py:213-286; seam at tiny_audio/asr_pipeline.py:117-131).  Contract: DESIGN.md section 3,
+ * "Forced alignment", defined by tests/align_ref.py.  N clips in one launch, ragged:
+ *   emission: f32 log-probabilities, clip n owns rows cu_frames[n] .. cu_frames[n + 1] (T_n of them) of [sum T_n, C], row stride ld;
+ *   tokens:   int32 ids in [0, C), clip n owns tokens[cu_tokens[n] .. cu_tokens[n + 1]) (J_n of them); cu_* are int32[N + 1].
+ * trellis[0, 0] = 0, every other entry -inf, then
+ *   trellis[t + 1, j] = max(trellis[t, j] + emission[t, blank_id], trellis[t, j - 1] + emission[t, tokens[j - 1]])   (j = 0: first term)
+ * with one f32 add per candidate.  Outputs per clip:
+ *   score[n]  = trellis[T_n, J_n];
+ *   status[n] = 0 aligned, 1 failed (score == -inf; the caller falls back to uniform spans), 2 refused: T_n > max_T, J_n > max_J,
+ *               a negative length, or a token id outside [0, C) (nothing else of the clip is written);
+ *   frames[cu_tokens[n] + i] = the frame of token i on the best path (ties between staying and moving go to moving, as the
+ *               reference's `move >= stay`), strictly increasing in i; written ONLY for status 0, so token i spans (f, f + 1).
+ * J_n = 0 gives status 0 and no frames; T_n = 0 < J_n gives status 1.
+ * trellis_out (may be NULL): clip n's full [T_n + 1, J_n + 1] trellis is written at trellis_out + trellis_off[n] (device long[N]).
+ * ws: ta_ctc_align_workspace_bytes(N, max_T, max_J) bytes holding the decision bits, no initial contents required; max_T / max_J
+ * bound every clip's T_n / J_n.  Limits (TA_ERR_ARG beyond them): N <= TA_ALIGN_MAX_CLIPS, max_T <= TA_ALIGN_MAX_FRAMES,
+ * max_J <= TA_ALIGN_MAX_TOKENS, C <= TA_ALIGN_MAX_CLASSES; also 0 <= blank_id < C <= ld. */
+#define TA_ALIGN_MAX_TOKENS 2048
+#define TA_ALIGN_MAX_FRAMES 32768
+#define TA_ALIGN_MAX_CLASSES 65536
+#define TA_ALIGN_MAX_CLIPS 4096
+#define TA_ALIGN_THREADS 256      /* one workgroup per clip; a thread owns every 256th trellis column */
+#define TA_ALIGN_FRAME_BLOCK 64   /* frames whose emissions are staged in LDS at a time ... */
+#define TA_ALIGN_STAGE_FLOATS 8192 /* ... or fewer: min(TA_ALIGN_FRAME_BLOCK, TA_ALIGN_STAGE_FLOATS / (J_n + 1)), at least 3 */
+long ta_ctc_align_workspace_bytes(int N, int max_T, int max_J);
+int ta_ctc_align_f32(const float* emission, long ld, int C, const int* cu_frames, const int* tokens, const int* cu_tokens, int N,
+                     int max_T, int max_J, int blank_id, int* frames, float* score, int* status, void* ws, long ws_bytes,
+                     float* trellis_out, const long* trellis_off, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -559,3 +559,59 @@ def mix_bwd(dout, o, rw):
     dlg = torch.empty((M, E), device=o.device, dtype=F32)
     check(lib().ta_mix_bwd(ptr(dout), ptr(o), ptr(rw), ptr(dob), ptr(dlg), M, D, E, stream()), "ta_mix_bwd")
     return dob, dlg
+
+
+# ----------------------------------------------------------------------------- forced alignment (csrc/align.hip)
+ALIGN_LIMITS = {"clips": 4096, "frames": 32768, "tokens": 2048, "classes": 65536}      # TA_ALIGN_MAX_* of include/ta355.h
+
+
+def ctc_align(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, *, frames=None, trellis_off=None,
+              trellis_numel=0, trellis=None):
+    """ta_ctc_align_f32: N ragged clips in one launch.  ``emission`` f32 [sum T_n, C] log-probabilities (rows may be strided),
+    ``cu_frames`` / ``cu_tokens`` int32 [N + 1], ``tokens`` int32 [sum J_n], all on the device; ``max_frames`` / ``max_tokens`` bound
+    every clip (the caller built the lengths on the host).  -> (frames int32 [sum J_n], score f32 [N], status int32 [N], trellis):
+    ``frames`` (given, or a new tensor of -1) is written for aligned clips only; ``trellis`` is None unless ``trellis_off``
+    (int64 [N], element offsets) and ``trellis_numel`` ask for every clip's [T_n + 1, J_n + 1] trellis in one flat f32 tensor
+    (``trellis``: a tensor of that size to write into).
+    The cumulative lengths and the offsets live on the device and are NOT checked here (that would cost a synchronisation, as with
+    ``cu_rows`` of the ragged encoder): ``cu_frames[N] <= emission.shape[0]``, ``cu_tokens[N] == tokens.numel()`` and
+    ``trellis_off[n] + (T_n + 1) (J_n + 1) <= trellis_numel`` are the caller's responsibility.  The kernel itself refuses (status 2,
+    score -inf, nothing else written) a clip longer than ``max_frames`` / ``max_tokens`` and a token id outside [0, C)."""
+    if not (emission.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("ctc_align needs the emissions on a HIP device: there is no CPU path for the trellis")
+    assert emission.dim() == 2 and emission.dtype == F32 and (emission.stride(1) == 1 or emission.numel() == 0), \
+        "emission: f32 [frames, C], unit column stride"
+    C_ = emission.shape[1]
+    ld = emission.stride(0) if emission.shape[0] > 1 else C_
+    N = cu_frames.numel() - 1
+    for name, v, lim in (("clips", N, "clips"), ("frames per clip", max_frames, "frames"), ("tokens per clip", max_tokens, "tokens"),
+                         ("classes", C_, "classes")):
+        if v > ALIGN_LIMITS[lim]:
+            raise ValueError(f"ctc_align: {v} {name} is beyond the kernel's limit of {ALIGN_LIMITS[lim]}")
+    if not 0 <= blank_id < C_:
+        raise ValueError(f"ctc_align: blank_id {blank_id} is outside [0, {C_})")
+    if ld < C_:
+        raise ValueError("ctc_align: emission rows overlap")
+    dev = emission.device
+    for t in (cu_frames, tokens, cu_tokens):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == dev
+    assert cu_tokens.numel() == N + 1 and N >= 0
+    if frames is None:
+        frames = torch.full((tokens.numel(),), -1, device=dev, dtype=torch.int32)
+    assert frames.dtype == torch.int32 and frames.is_contiguous() and frames.numel() == tokens.numel() and frames.device == dev
+    score = torch.empty(N, device=dev, dtype=F32)
+    status = torch.empty(N, device=dev, dtype=torch.int32)
+    if trellis_off is None:
+        trellis = None
+    else:
+        assert trellis_off.dtype == torch.int64 and trellis_off.numel() == N and trellis_off.device == dev
+        if trellis is None:
+            trellis = torch.empty(int(trellis_numel), device=dev, dtype=F32)
+        assert trellis.dtype == F32 and trellis.is_contiguous() and trellis.numel() == int(trellis_numel) and trellis.device == dev
+    L = lib()
+    ws_bytes = L.ta_ctc_align_workspace_bytes(N, int(max_frames), int(max_tokens))
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    check(L.ta_ctc_align_f32(ptr(emission), ld, C_, ptr(cu_frames), ptr(tokens), ptr(cu_tokens), N, int(max_frames), int(max_tokens),
+                             int(blank_id), ptr(frames), ptr(score), ptr(status), ptr(ws), ws_bytes, ptr(trellis), ptr(trellis_off),
+                             stream()), "ta_ctc_align_f32")
+    return frames, score, status, trellis

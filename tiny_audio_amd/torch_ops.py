@@ -6,6 +6,7 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::logmel              WhisperFeatureExtractor.__call__           scripts/train.py:327-333
     ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
+    ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
     ta355::encoder_forward_ragged   the same seam, every clip at its own length (opt-in; what the reference computes for a
                                clip encoded alone, tiny_audio/asr_modeling.py:198-200)
@@ -123,6 +124,27 @@ def wave_augment_chain(wav: Tensor, lens: Tensor, desc: Tensor, stages: int, see
 @wave_augment_chain.register_fake
 def _(wav, lens, desc, stages, seed, offset, ev_stride, max_event_len, handle):
     return torch.empty_like(wav)
+
+
+# ============================================================================ forced alignment
+@torch.library.custom_op("ta355::ctc_align", mutates_args=())
+def ctc_align(emission: Tensor, cu_frames: Tensor, tokens: Tensor, cu_tokens: Tensor, blank_id: int, max_frames: int, max_tokens: int,
+              trellis_off: Optional[Tensor], trellis_numel: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """N ragged clips in one launch (``ops.ctc_align``): emission f32 [sum T_n, C] log-probabilities, cu_frames / cu_tokens i32 [N + 1],
+    tokens i32 [sum J_n] -> (frames i32 [sum J_n]: the frame of every token, -1 in clips that did not align; score f32 [N] =
+    trellis[T_n, J_n]; status i32 [N]: 0 aligned, 1 failed; the clips' trellises, flat f32 [trellis_numel] at the element offsets
+    ``trellis_off`` i64 [N], or empty without ``trellis_off``).  No autograd: the path is integers."""
+    from . import ops
+    frames, score, status, trellis = ops.ctc_align(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens,
+                                                   trellis_off=trellis_off, trellis_numel=trellis_numel)
+    return frames, score, status, trellis if trellis is not None else torch.empty(0, device=emission.device, dtype=F32)
+
+
+@ctc_align.register_fake
+def _(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, trellis_off, trellis_numel):
+    N = cu_frames.shape[0] - 1
+    return (tokens.new_empty(tokens.shape), emission.new_empty((N,)), tokens.new_empty((N,)),
+            emission.new_empty((trellis_numel if trellis_off is not None else 0,)))
 
 
 # ============================================================================ frozen encoder
@@ -612,4 +634,4 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
-             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged")
+             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align")
