@@ -388,6 +388,22 @@ int ta_logits_suppress_until(float* logits, long ld, int V, const long* ids, int
 int ta_greedy_advance(const long* amax, const long* eos_ids, int n_eos, long pad_id, int* finished, long* next_ids,
                       long* out_seq, int max_new, int* step_dev, int* slot_dev, int* pos, int* kmask, int Lmax, int B,
                       int* n_unfinished, hipStream_t st);
+/* Decoding scores of one step, from the PROCESSED logits [B, ld] f32 (V valid columns; columns >= V are never read; valid columns may
+ * be -inf) -- what HF's compute_transition_scores(..., normalize_logits=True) gives on its `scores` (TF:generation/utils.py), without
+ * ever keeping the [B, V] rows.  Writes column t = *step_dev (device memory, so the launch arguments are step-invariant; NULL = column 0;
+ * t >= max_new writes nothing) of the row-major buffers logprob / entropy f32 [B, max_new] and, with top_k > 0, top_ids i64 /
+ * top_logprobs f32 [B, max_new, top_k] (both may be NULL with top_k == 0; 0 <= top_k <= 8, else TA_ERR_ARG):
+ *   logprob[b, t]  = x[chosen[b]] - logsumexp(x[:V])      (a chosen -inf gives -inf)
+ *   entropy[b, t]  = -sum p log p over the entries with p > 0
+ *   top_ids[b, t]  = the top_k largest entries, descending, lowest index first on ties (slot 0 = ta_argmax_f32's choice),
+ *   top_logprobs   = their log-probabilities; slots beyond the number of finite entries are (-1, -inf).
+ * Rows with finished[b] != 0 (finished BEFORE this step: they emit pad; NULL = none) get 0 / 0 / -1 / -inf.  Call between the
+ * selection (ta_argmax_f32 / ta_sample_f32, whose output is `chosen`) and ta_greedy_advance, which advances *step_dev and finished.
+ * One workgroup per row; B <= 64 rows of V >= 16384 columns are split over 8 workgroups per row plus a combine launch, through a
+ * scratch the library owns (TA355_SCORES_SPLIT=0: never).  Calls are ordered by their stream; calls of the split form on two streams
+ * at the same time would share that scratch and must be serialised by the caller. */
+int ta_token_scores_f32(const float* logits, long ld, int V, int B, const long* chosen, const int* finished, const int* step_dev,
+                        int max_new, int top_k, float* logprob, float* entropy, long* top_ids, float* top_logprobs, hipStream_t st);
 
 /* loss.backward() through the LM (replaces autograd over Qwen3ForCausalLM, tiny_audio/asr_modeling.py:517-533).
  * d_audio f32 [n_audio_rows, D] (zeroed, then rows referenced by src_row written; NULL = not wanted, e.g. frozen

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Greedy-generation timing at full model size (secondary metric: the WER loop's inference side).
-B clips of 10 s, prompt = 3 + 125 <audio> + 24 tokens, N new tokens; reports prompt-pass and per-token latency."""
+B clips of 10 s, prompt = 3 + 125 <audio> + 24 tokens, N new tokens; reports prompt-pass and per-token latency.
+``gen_bench.py [B [N]] [--scores] [--top-logprobs K]``: the same loop with the decoding scores on (token log-probability and entropy,
+K alternatives per step)."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,14 +10,25 @@ import torch
 from tiny_audio_amd.asr_config import ASRConfig
 from tiny_audio_amd.asr_modeling import ASRModel
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+argv, scores, top_lp = [], False, 0
+it = iter(sys.argv[1:])
+for a in it:
+    if a == "--scores":
+        scores = True
+    elif a == "--top-logprobs":
+        top_lp = int(next(it))
+    else:
+        argv.append(a)
+B = int(argv[0]) if len(argv) > 0 else 32
+N = int(argv[1]) if len(argv) > 1 else 64
 cfg = ASRConfig()
 m = ASRModel(cfg, device="cuda", init="random", seed=0)
 feats = torch.randn(B, 128, 1000, device="cuda") * 0.5
 amask = torch.ones(B, 1000, dtype=torch.int64)
 ids = torch.tensor([[5, 6, 7] + [cfg.audio_token_id] * 125 + list(range(100, 124))] * B)
 kw = dict(input_ids=ids, input_features=feats, audio_attention_mask=amask, attention_mask=torch.ones_like(ids), eos_token_id=[])
+if scores or top_lp:
+    kw.update(return_token_scores=scores, top_logprobs=top_lp)
 res = {}
 for n in (1, N):
     m.generate(**kw, max_new_tokens=n); torch.cuda.synchronize()
@@ -41,4 +54,4 @@ print(json.dumps({"B": B, "new_tokens": N, "prompt_pass_ms": round(res[1] * 1e3,
                                "achieved": round((w_bytes + kv_bytes) / per_tok / 1e9, 1),
                                "frac": round(floor_ms / (per_tok * 1e3), 4), "floor_ms_per_token": round(floor_ms, 4),
                                "frac_weights_only": round(w_bytes / 8e12 / per_tok, 4)},
-                  "fused": os.environ.get("TA355_DECODE_FUSED", "1") != "0"}))
+                  "fused": os.environ.get("TA355_DECODE_FUSED", "1") != "0", "token_scores": bool(scores or top_lp), "top_logprobs": top_lp}))

@@ -69,6 +69,46 @@ class CausalLMOutput(dict):
         return (CausalLMOutput, (dict.get(self, "loss"), dict.get(self, "logits"), self.nll, self.n_label_tokens, self.aux_loss, self.loss_ce))
 
 
+class GenerationOutput(dict):
+    """What ``ASRModel.generate`` returns when decoding scores are asked for (``return_token_scores`` / ``top_logprobs``); like
+    ``CausalLMOutput`` the dict holds the fields that are not None, in order, with attribute, key, index and slice access:
+    ``sequences`` int64 [B, n_new], ``token_logprobs`` f32 [B, n_new] (log-probability of every emitted token under the processed
+    distribution it was chosen from: HF's ``compute_transition_scores(..., normalize_logits=True)``), ``token_entropy`` f32
+    [B, n_new] (nats), and with ``top_logprobs`` = k > 0 ``top_token_ids`` int64 [B, n_new, k] / ``top_logprobs`` f32 [B, n_new, k]
+    (descending; slots beyond the finite entries are -1 / -inf).  Positions after a clip's first eos hold 0 / 0 / -1 / -inf.
+    HF's ``scores`` (the full [B, V] row of every step) is deliberately not kept, so that name is not used."""
+
+    _items = ("sequences", "token_logprobs", "token_entropy", "top_token_ids", "top_logprobs")
+
+    def __init__(self, sequences=None, token_logprobs=None, token_entropy=None, top_token_ids=None, top_logprobs=None):
+        super().__init__()
+        if isinstance(sequences, Mapping):            # rebuilt from a mapping, as library code does with ModelOutput
+            src = sequences
+            unknown = [k for k in src if k not in self._items]
+            if unknown:
+                raise KeyError(f"GenerationOutput has no item {unknown[0]!r}")
+            sequences, token_logprobs, token_entropy, top_token_ids, top_logprobs = (src.get(k) for k in self._items)
+        for k, v in zip(self._items, (sequences, token_logprobs, token_entropy, top_token_ids, top_logprobs)):
+            if v is not None:
+                dict.__setitem__(self, k, v)
+
+    def __getattr__(self, k):                     # reached only when the normal lookup fails: an item, or an absent item
+        if k in GenerationOutput._items:
+            return dict.get(self, k)
+        raise AttributeError(k)
+
+    def __getitem__(self, k):
+        if isinstance(k, (int, slice)):
+            return tuple(self.values())[k]
+        return dict.__getitem__(self, k)
+
+    def to_tuple(self):
+        return tuple(self.values())
+
+    def __reduce__(self):
+        return (GenerationOutput, tuple(dict.get(self, k) for k in self._items))
+
+
 def _is_cjk(ch: str) -> bool:
     """CJK ideograph blocks (a streamer releases such characters one by one: they carry no spaces)."""
     cp = ord(ch)
@@ -596,26 +636,42 @@ class ASRModel(nn.Module):
                     max_new_tokens=max_new, eos_ids=eos_ids, pad_id=pad_id, repetition_penalty=rep, no_repeat_ngram_size=ngram,
                     min_new_tokens=min_new, sampling=sampling)
 
+    @staticmethod
+    def _check_top_logprobs(top_logprobs) -> int:
+        k = int(top_logprobs or 0)
+        if not 0 <= k <= ops.MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_logprobs must be within [0, {ops.MAX_TOP_LOGPROBS}]; got {top_logprobs}")
+        return k
+
     @torch.no_grad()
     def generate(self, input_ids: Optional[torch.Tensor] = None, input_features: Optional[torch.Tensor] = None,
                  audio_attention_mask: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
-                 system_prompt: Optional[str] = None, **generate_kwargs) -> torch.Tensor:
+                 system_prompt: Optional[str] = None, return_token_scores: bool = False, top_logprobs: int = 0, **generate_kwargs):
         """Transcription token ids [B, n_new] (prompt stripped), as ASRModel.generate of the reference
         (tiny_audio/asr_modeling.py:562-646): audio -> encoder -> projector -> <audio> rows of the prompt embeddings ->
         greedy search on the LM (num_beams 1, do_sample False: asr_config.py:103-111), with the
-        reference's ``repetition_penalty`` / ``no_repeat_ngram_size`` settings as device-side logits processors."""
+        reference's ``repetition_penalty`` / ``no_repeat_ngram_size`` settings as device-side logits processors.
+
+        ``return_token_scores=True`` and / or ``top_logprobs=k`` (1..8) return a ``GenerationOutput`` instead: the same tokens as
+        ``sequences`` plus every token's log-probability and the entropy of the distribution it was chosen from (after the
+        processors and warpers), and the k most probable alternatives of every step -- computed by one more row kernel inside the
+        decode step; the [B, V] rows themselves are never kept."""
+        top_k = self._check_top_logprobs(top_logprobs)
         was_training = self.training
         self.eval()
         try:
             args = self._prepare_generation(input_ids, input_features, audio_attention_mask, attention_mask, system_prompt,
                                             dict(generate_kwargs))
-            return self.language_model.greedy_decode(**args)
+            if not (return_token_scores or top_k):
+                return self.language_model.greedy_decode(**args)
+            seq, sc = self.language_model.greedy_decode(**args, token_scores=True, top_logprobs=top_k)
+            return GenerationOutput(sequences=seq, **sc)
         finally:
             self.train(was_training)
 
     def generate_streaming(self, input_features: torch.Tensor, audio_attention_mask: torch.Tensor,
                            system_prompt: Optional[str] = None, input_ids: Optional[torch.Tensor] = None,
-                           return_token_ids: bool = False, **generate_kwargs) -> Iterator:
+                           return_token_ids: bool = False, return_token_scores: bool = False, **generate_kwargs) -> Iterator:
         """Partial transcript text, piece by piece, while the clip is still being decoded (ASRModel.generate_streaming,
         tiny_audio/asr_modeling.py:648-760).  The reference runs ``language_model.generate`` on a thread feeding a
         ``TextIteratorStreamer``; here the decode loop itself is a generator (one device sync per token), so no thread
@@ -623,7 +679,11 @@ class ASRModel(nn.Module):
         up to the last space; CJK characters immediately), special tokens are skipped and ``<think>...</think>`` spans
         are dropped (:737-757).  One clip at a time, like the reference's streamer.
 
-        ``return_token_ids=True`` yields the raw int token id of every step instead (no tokenizer needed)."""
+        ``return_token_ids=True`` yields the raw int token id of every step instead (no tokenizer needed); with
+        ``return_token_scores=True`` as well, ``(token_id, logprob)`` pairs: the id and its log-probability under the processed
+        distribution of its step (a float).  The text mode carries no scores."""
+        if return_token_scores and not return_token_ids:
+            raise ValueError("return_token_scores needs return_token_ids=True: text pieces do not map to single tokens")
         if input_features.shape[0] != 1:
             raise ValueError("generate_streaming handles one clip at a time (TextIteratorStreamer: batch size 1 only)")
         if not return_token_ids and self.tokenizer is None:
@@ -639,12 +699,18 @@ class ASRModel(nn.Module):
             gate = _ThinkGate()
             # (the reference's streaming call passes inputs_embeds only, so HF's repetition / n-gram processors start from an empty
             # input_ids there and see the generated tokens alone -- generate() passes the prompt ids as well)
-            for col in self.language_model.greedy_decode_iter(per_token=True, processors_see_prompt=False, **args):
+            for col in self.language_model.greedy_decode_iter(per_token=True, processors_see_prompt=False,
+                                                              token_scores=bool(return_token_scores), **args):
+                lp = None
+                if return_token_scores:                  # (tokens [1], logprob [1]) per step; the closing item holds a dict
+                    col, lp = col
+                    if isinstance(lp, dict):
+                        break
                 if col.dim() != 1:                       # the closing full [B, n_new] tensor
                     break
                 tok = int(col[0])
                 if return_token_ids:
-                    yield tok
+                    yield (tok, float(lp[0])) if return_token_scores else tok
                     if tok in eos:
                         break
                     continue

@@ -17,7 +17,9 @@ static bool read_decode_fused() { const char* e = getenv("TA355_DECODE_FUSED"); 
 static bool g_decode_fused = read_decode_fused();                 // read at load; ta_gemm_reload_knobs() re-reads it (the tests compare both sequences)
 static const bool g_decode_prefetch = true;                       // next-kernel prefetch workgroups (1.54 -> 1.455 ms per token, r04)
 static const int g_decode_pf_wgs = 0;                             // 0 = decode_fused.hip's default (96: 1.94 ms at 32, 1.46 at 96-128, 1.59 at 256+)
-void ta_i_reload_decode_knobs() { g_decode_fused = read_decode_fused(); }
+static bool read_scores_split() { const char* e = getenv("TA355_SCORES_SPLIT"); return !(e && *e == '0'); }
+static bool g_scores_split = read_scores_split();                 // 0: ta_token_scores_f32 keeps one workgroup per row at every shape (the A/B of profiles/decode_scores.md)
+void ta_i_reload_decode_knobs() { g_decode_fused = read_decode_fused(); g_scores_split = read_scores_split(); }
 
 namespace {
 constexpr int HD = 128;
@@ -665,6 +667,224 @@ extern "C" int ta_sample_f32(const float* logits, long ld, int V, int B, unsigne
   if (B <= 0) return TA_OK;
   if (!logits || V <= 0 || !step_dev || !out) return TA_ERR_ARG;
   TA_LAUNCH(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, ld, V, seed, step_dev, out);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// ---- decoding scores: log-probability of the chosen token, entropy and the top-k alternatives of the step's PROCESSED logits (what HF's
+// compute_transition_scores(..., normalize_logits=True) gives on its `scores`; TF:generation/utils.py).  The [B, V] rows are never kept:
+// the kernel sits in the step between the selection and ta_greedy_advance and writes column *step_p of [B, max_new] buffers.
+// One 1024-lane workgroup per row, ONE pass: a lane carries (m, s, t) = (running maximum, sum e^(x-m), sum (x-m) e^(x-m)), rescaled on
+// every merge (element -> lane -> wave -> 16 waves through LDS); then log Z = m + log s, H = log s - t / s.  -inf entries are skipped,
+// so no (-inf) - (-inf) or (-inf) * 0 is ever formed.
+__device__ __forceinline__ void lse_merge(float& m, float& s, float& t, float m2, float s2, float t2) {
+  if (m2 == -INFINITY) return;                                    // the other side saw no finite entry
+  if (m == -INFINITY) { m = m2; s = s2; t = t2; return; }
+  if (m2 > m) { const float a = m, b = s, c = t; m = m2; s = s2; t = t2; m2 = a; s2 = b; t2 = c; }
+  const float d = m2 - m, e = __expf(d);                          // d <= 0, finite
+  s += s2 * e;
+  t += e * (t2 + d * s2);
+}
+__device__ __forceinline__ bool topk_before(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
+// Two layouts.  Direct: one workgroup per row does everything.  Split (few rows of a wide vocabulary: 32 workgroups would leave 7/8 of
+// the GPU idle, and a lane that meets 148 elements pays the list insertion on nearly every one of them because SOME lane of its wave
+// inserts): TS_SPLIT workgroups per row scan a slice each and leave (m, s, t) and their slice's top-k in the library's scratch below;
+// token_scores_combine_kernel (one wave per row) merges them.  Measured at B = 32, V = 151 670, top_k = 8: profiles/decode_scores.md.
+// The scratch is one per library: calls are ordered by their stream (the decode loop's, or torch's current one); calls of the split
+// layout on two streams at once would share it and must be serialised by the caller.
+#define TS_SPLIT 8
+#define TS_SPLIT_MAX_ROWS 64                                      // above this the direct layout fills the GPU by itself
+#define TS_SPLIT_MIN_V 16384                                      // below this a slice would not even give every lane two float4 loads
+__device__ float g_ts_mst[TS_SPLIT_MAX_ROWS * TS_SPLIT * 3];
+__device__ float g_ts_cv[TS_SPLIT_MAX_ROWS * TS_SPLIT * 8];
+__device__ int g_ts_ci[TS_SPLIT_MAX_ROWS * TS_SPLIT * 8];
+// K = capacity of the per-lane candidate list (0: no alternatives wanted), kk <= K = alternatives written
+template <int K, bool SPLIT>
+__global__ __launch_bounds__(1024) void token_scores_kernel(const float* __restrict__ x, long ld, int V, const long* __restrict__ chosen,
+                                                            const int* __restrict__ finished, const int* __restrict__ step_p, int max_new,
+                                                            int kk, float* __restrict__ logprob, float* __restrict__ entropy,
+                                                            long* __restrict__ top_ids, float* __restrict__ top_lp) {
+  __shared__ float rm[16], rs[16], rt[16];
+  __shared__ float bv[2][16];
+  __shared__ int bi[2][16];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  long o1 = 0;
+  if constexpr (SPLIT) {
+    if (finished && finished[b]) return;                          // (the combine kernel writes the row's fill)
+  } else {
+    const int col = step_p ? *step_p : 0;
+    if (col < 0 || col >= max_new) return;                        // (the loop never launches past max_new; nothing to write to)
+    o1 = (long)b * max_new + col;
+    if (finished && finished[b]) {                                // finished before this step: the step emits pad
+      if (tid == 0) { logprob[o1] = 0.f; entropy[o1] = 0.f; }
+      if (tid < kk) { top_ids[o1 * kk + tid] = -1; top_lp[o1 * kk + tid] = -INFINITY; }
+      return;
+    }
+  }
+  // this workgroup's columns [j0, j1): the whole row, or slice blockIdx.y (a multiple of 4 wide, so slices keep the row's alignment)
+  const int chunk = SPLIT ? ((V + TS_SPLIT - 1) / TS_SPLIT + 3) & ~3 : V;
+  const int j0 = SPLIT ? min(V, (int)blockIdx.y * chunk) : 0, j1 = SPLIT ? min(V, j0 + chunk) : V;
+  const float* row = x + (long)b * ld;
+  float m = -INFINITY, s = 0.f, t = 0.f;
+  constexpr int KL = K > 0 ? K : 1;
+  float tv[KL]; int ti[KL];
+#pragma unroll
+  for (int p = 0; p < KL; ++p) { tv[p] = -INFINITY; ti[p] = -1; }
+  // a lane meets its indices in increasing order, so on equal values the earlier (lower) index stays in front and a value
+  // equal to the lane's k-th never enters: one compare per element once the list is warm
+  auto take = [&](float v, int j) {
+    if (v > m) {
+      if (m == -INFINITY) { s = 1.f; t = 0.f; }
+      else { const float d = m - v, e = __expf(d); t = e * (t + d * s); s = s * e + 1.f; }
+      m = v;
+    } else if (v > -INFINITY) {
+      const float d = v - m, e = __expf(d);
+      s += e; t += d * e;
+    }
+    if constexpr (K > 0) {
+      if (v > tv[K - 1]) {
+        tv[K - 1] = v; ti[K - 1] = j;
+#pragma unroll
+        for (int p = K - 1; p > 0; --p)
+          if (tv[p] > tv[p - 1]) { const float a = tv[p]; tv[p] = tv[p - 1]; tv[p - 1] = a; const int c = ti[p]; ti[p] = ti[p - 1]; ti[p - 1] = c; }
+      }
+    }
+  };
+  const bool vec = (((size_t)row) & 15) == 0;
+  const int n4 = vec ? (j1 - j0) / 4 : 0;
+  const float4* row4 = (const float4*)(row + j0);
+  for (int q0 = tid; q0 < n4; q0 += 4 * 1024) {                   // four 16-byte loads in flight per lane
+    float4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = q0 + u * 1024;
+      v[u] = q < n4 ? row4[q] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int j = j0 + 4 * (q0 + u * 1024);
+      take(v[u].x, j); take(v[u].y, j + 1); take(v[u].z, j + 2); take(v[u].w, j + 3);
+    }
+  }
+  for (int j = j0 + n4 * 4 + tid; j < j1; j += 1024) take(row[j], j);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, t, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64), __shfl_xor(t, o, 64));
+  if (lane == 0) { rm[wave] = m; rs[wave] = s; rt[wave] = t; }
+  __syncthreads();
+  m = rm[0]; s = rs[0]; t = rt[0];
+  for (int w = 1; w < 16; ++w) lse_merge(m, s, t, rm[w], rs[w], rt[w]);      // the same order in every lane: one value for the row
+  const int part = SPLIT ? b * TS_SPLIT + (int)blockIdx.y : 0;
+  if constexpr (SPLIT) {
+    if (tid == 0) { g_ts_mst[part * 3] = m; g_ts_mst[part * 3 + 1] = s; g_ts_mst[part * 3 + 2] = t; }
+  }
+  const float ls = m == -INFINITY ? 0.f : logf(s);
+  if (!SPLIT && tid == 0) {
+    const long c = chosen[b];
+    const float xc = (c >= 0 && c < V) ? row[c] : -INFINITY;
+    logprob[o1] = (m == -INFINITY || xc == -INFINITY) ? -INFINITY : (xc - m) - ls;
+    entropy[o1] = m == -INFINITY ? 0.f : fmaxf(ls - t / s, 0.f);
+  }
+  if constexpr (K > 0) {
+    // kk rounds of "workgroup argmax over the list heads, the owner pops": lowest index first on ties, as ta_argmax_f32
+    for (int r = 0; r < kk; ++r) {
+      float hv = tv[0]; int hi = ti[0];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(hv, o, 64); const int oi = __shfl_xor(hi, o, 64);
+        if (oi >= 0 && (hi < 0 || topk_before(ov, oi, hv, hi))) { hv = ov; hi = oi; }
+      }
+      if (lane == 0) { bv[r & 1][wave] = hv; bi[r & 1][wave] = hi; }
+      __syncthreads();                                            // (two buffers: round r + 1 writes the other one, one barrier per round)
+      hv = bv[r & 1][0]; hi = bi[r & 1][0];
+      for (int w = 1; w < 16; ++w) {
+        const float ov = bv[r & 1][w]; const int oi = bi[r & 1][w];
+        if (oi >= 0 && (hi < 0 || topk_before(ov, oi, hv, hi))) { hv = ov; hi = oi; }
+      }
+      if (hi >= 0 && ti[0] == hi) {                               // the owner (indices are unique): drop the head
+#pragma unroll
+        for (int p = 0; p + 1 < K; ++p) { tv[p] = tv[p + 1]; ti[p] = ti[p + 1]; }
+        tv[K - 1] = -INFINITY; ti[K - 1] = -1;
+      }
+      if (tid == 0) {
+        if constexpr (SPLIT) { g_ts_cv[part * 8 + r] = hv; g_ts_ci[part * 8 + r] = hi; }
+        else {
+          top_ids[o1 * kk + r] = hi;
+          top_lp[o1 * kk + r] = hi < 0 ? -INFINITY : (hv - m) - ls;
+        }
+      }
+    }
+  }
+}
+
+// The split layout's second launch: one wave per row.  Lane p < TS_SPLIT merges slice p's (m, s, t); lane 8 p + r holds slice p's r-th
+// candidate, and kk rounds of "wave argmax, the owner drops its candidate" order them.  Lane 0 writes every output, so that under
+// greedy search top_logprobs[.., 0] and logprob are the same float.
+__global__ __launch_bounds__(64) void token_scores_combine_kernel(const float* __restrict__ x, long ld, int V, const long* __restrict__ chosen,
+                                                                  const int* __restrict__ finished, const int* __restrict__ step_p,
+                                                                  int max_new, int kk, float* __restrict__ logprob,
+                                                                  float* __restrict__ entropy, long* __restrict__ top_ids,
+                                                                  float* __restrict__ top_lp) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int col = step_p ? *step_p : 0;
+  if (col < 0 || col >= max_new) return;
+  const long o1 = (long)b * max_new + col;
+  if (finished && finished[b]) {
+    if (lane == 0) { logprob[o1] = 0.f; entropy[o1] = 0.f; }
+    if (lane < kk) { top_ids[o1 * kk + lane] = -1; top_lp[o1 * kk + lane] = -INFINITY; }
+    return;
+  }
+  float m = -INFINITY, s = 0.f, t = 0.f;
+  if (lane < TS_SPLIT) { const float* p = g_ts_mst + (b * TS_SPLIT + lane) * 3; m = p[0]; s = p[1]; t = p[2]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, t, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64), __shfl_xor(t, o, 64));
+  m = __shfl(m, 0, 64); s = __shfl(s, 0, 64); t = __shfl(t, 0, 64);        // lane 0's association order for everybody
+  const float ls = m == -INFINITY ? 0.f : logf(s);
+  if (lane == 0) {
+    const long c = chosen[b];
+    const float xc = (c >= 0 && c < V) ? x[(long)b * ld + c] : -INFINITY;
+    logprob[o1] = (m == -INFINITY || xc == -INFINITY) ? -INFINITY : (xc - m) - ls;
+    entropy[o1] = m == -INFINITY ? 0.f : fmaxf(ls - t / s, 0.f);
+  }
+  float cv = -INFINITY; int ci = -1;
+  if ((lane & 7) < kk) { cv = g_ts_cv[b * TS_SPLIT * 8 + lane]; ci = g_ts_ci[b * TS_SPLIT * 8 + lane]; }
+  for (int r = 0; r < kk; ++r) {
+    float hv = cv; int hi = ci;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(hv, o, 64); const int oi = __shfl_xor(hi, o, 64);
+      if (oi >= 0 && (hi < 0 || topk_before(ov, oi, hv, hi))) { hv = ov; hi = oi; }
+    }
+    if (hi >= 0 && ci == hi) { cv = -INFINITY; ci = -1; }
+    if (lane == 0) {
+      top_ids[o1 * kk + r] = hi;
+      top_lp[o1 * kk + r] = hi < 0 ? -INFINITY : (hv - m) - ls;
+    }
+  }
+}
+
+extern "C" int ta_token_scores_f32(const float* logits, long ld, int V, int B, const long* chosen, const int* finished,
+                                   const int* step_dev, int max_new, int top_k, float* logprob, float* entropy, long* top_ids,
+                                   float* top_logprobs, hipStream_t st) {
+  if (top_k < 0 || top_k > 8) return TA_ERR_ARG;
+  if (B <= 0) return TA_OK;
+  if (!logits || V <= 0 || ld < V || !chosen || max_new <= 0 || !logprob || !entropy || (top_k > 0 && (!top_ids || !top_logprobs)))
+    return TA_ERR_ARG;
+  const bool split = g_scores_split && B <= TS_SPLIT_MAX_ROWS && V >= TS_SPLIT_MIN_V && V <= (1 << 30);
+#define TS(K_, S_) TA_LAUNCH((token_scores_kernel<K_, S_>), dim3(B, S_ ? TS_SPLIT : 1), dim3(1024), 0, st, logits, ld, V, chosen, finished, \
+                             step_dev, max_new, top_k, logprob, entropy, top_ids, top_logprobs)
+  if (split) {
+    if (top_k == 0) TS(0, true);
+    else if (top_k <= 4) TS(4, true);
+    else TS(8, true);
+    TA_CHECK_LAUNCH();
+    TA_LAUNCH(token_scores_combine_kernel, dim3(B), dim3(64), 0, st, logits, ld, V, chosen, finished, step_dev, max_new, top_k, logprob,
+              entropy, top_ids, top_logprobs);
+  } else {
+    if (top_k == 0) TS(0, false);
+    else if (top_k <= 4) TS(4, false);
+    else TS(8, false);
+  }
+#undef TS
   TA_CHECK_LAUNCH();
   return TA_OK;
 }

@@ -636,19 +636,20 @@ class Qwen3MI355X(torch.nn.Module):
     # ------------------------------------------------------------------ greedy decoding
     @torch.no_grad()
     def greedy_decode(self, input_ids, src_row, audio, attention_mask=None, max_new_tokens=128, eos_ids=(), pad_id=0,
-                      sync_every=8, use_graph=True, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sampling=None):
-        """-> int64 [B, n_new]; see ``greedy_decode_iter`` (this drains it, polling the device every ``sync_every``
-        steps only)."""
+                      sync_every=8, use_graph=True, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sampling=None,
+                      token_scores=False, top_logprobs=0):
+        """-> int64 [B, n_new], or with ``token_scores`` / ``top_logprobs`` the pair (that tensor, the scores dict); see
+        ``greedy_decode_iter`` (this drains it, polling the device every ``sync_every`` steps only)."""
         out = None
         for out in self.greedy_decode_iter(input_ids, src_row, audio, attention_mask, max_new_tokens, eos_ids, pad_id,
                                            sync_every, use_graph, per_token=False, repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, sampling=sampling,
-                                           no_repeat_ngram_size=no_repeat_ngram_size):
+                                           no_repeat_ngram_size=no_repeat_ngram_size, token_scores=token_scores, top_logprobs=top_logprobs):
             pass
         return out
 
     def greedy_decode_iter(self, input_ids, src_row, audio, attention_mask=None, max_new_tokens=128, eos_ids=(), pad_id=0,
                            sync_every=8, use_graph=True, per_token=True, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
-                           processors_see_prompt=True, sampling=None):
+                           processors_see_prompt=True, sampling=None, token_scores=False, top_logprobs=0):
         """HF greedy search with a KV cache (what ``language_model.generate`` does for the reference's generation
         config, tiny_audio/asr_config.py:103-111): prompt pass, then one token per clip per step until every clip has
         emitted an eos id or ``max_new_tokens`` is reached.  -> int64 [B, n_new] (prompt stripped; finished clips are
@@ -657,7 +658,18 @@ class Qwen3MI355X(torch.nn.Module):
 
         A generator: with ``per_token`` it yields the int64 [B] host tensor of every step's tokens as soon as that step
         has run (one device sync per token: the streaming mode of tiny_audio/asr_modeling.py:648-760) and stops when
-        every clip is finished; the last item yielded is always the full [B, n_new] device tensor."""
+        every clip is finished; the last item yielded is always the full [B, n_new] device tensor.
+
+        Decoding scores (``token_scores`` and / or ``top_logprobs`` = k in [1, 8]; off by default, and then nothing below is launched or
+        allocated): every step also runs ``ta_token_scores_f32`` on its PROCESSED logits (after the processors and warpers), between the
+        selection and the bookkeeping, also inside the captured step.  The last item is then ``(sequences, scores)`` with scores =
+        {``token_logprobs`` f32 [B, n_new], ``token_entropy`` f32 [B, n_new], ``top_token_ids`` int64 [B, n_new, k] or None,
+        ``top_logprobs`` f32 [B, n_new, k] or None} (positions after a clip's eos: 0 / 0 / -1 / -inf), and with ``per_token`` every
+        step yields ``(tokens [B], logprob [B])`` host tensors."""
+        n_top = int(top_logprobs or 0)
+        if not 0 <= n_top <= 8:
+            raise ValueError(f"top_logprobs must be within [0, 8]; got {top_logprobs}")
+        want_scores = bool(token_scores) or n_top > 0
         if self._w is None:
             raise _lib.Ta355Error("LM weights not loaded")
         L_ = _lib.lib()
@@ -665,7 +677,11 @@ class Qwen3MI355X(torch.nn.Module):
         B, L = input_ids.shape
         max_new = int(max_new_tokens)
         if max_new <= 0:
-            yield torch.empty((B, 0), dtype=torch.int64, device=dev)
+            seq = torch.empty((B, 0), dtype=torch.int64, device=dev)
+            e = torch.empty((B, 0), dtype=F32, device=dev)
+            yield (seq, dict(token_logprobs=e, token_entropy=e.clone(),
+                             top_token_ids=torch.empty((B, 0, n_top), dtype=torch.int64, device=dev) if n_top else None,
+                             top_logprobs=torch.empty((B, 0, n_top), dtype=F32, device=dev) if n_top else None)) if want_scores else seq
             return
         Lmax = L + max_new
         if Lmax > c.max_position_embeddings:
@@ -703,6 +719,12 @@ class Qwen3MI355X(torch.nn.Module):
         a = None if audio is None else audio.detach().to(F32).contiguous()
 
         rep, ngram, min_new = float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens or 0)
+        sc_lp = sc_ent = sc_ids = sc_top = None
+        if want_scores:                             # one column per step, written on the device at *step_dev; never the [B, V] rows
+            sc_lp, sc_ent = torch.zeros((B, max_new), dtype=F32, device=dev), torch.zeros((B, max_new), dtype=F32, device=dev)
+            if n_top:
+                sc_ids = torch.full((B, max_new, n_top), -1, dtype=i64, device=dev)
+                sc_top = torch.full((B, max_new, n_top), float("-inf"), dtype=F32, device=dev)
 
         def advance():
             if rep != 1.0 or ngram > 0:            # HF logits processors over prompt ids + generated tokens (device-side, graph-safe)
@@ -721,6 +743,10 @@ class Qwen3MI355X(torch.nn.Module):
                                             ptr(amax), stream()), "ta_sample_f32")
             else:
                 _lib.check(L_.ta_argmax_f32(ptr(logits), self.vocab_pad, c.vocab_size, B, ptr(amax), stream()), "ta_argmax_f32")
+            if want_scores:                         # before the bookkeeping: it reads *step_dev and `finished` as they stand for THIS step
+                _lib.check(L_.ta_token_scores_f32(ptr(logits), self.vocab_pad, c.vocab_size, B, ptr(amax), ptr(finished), ptr(step_dev),
+                                                  max_new, n_top, ptr(sc_lp), ptr(sc_ent), ptr(sc_ids), ptr(sc_top), stream()),
+                           "ta_token_scores_f32")
             _lib.check(L_.ta_greedy_advance(ptr(amax), ptr(eos), n_eos, int(pad_id), ptr(finished), ptr(next_ids), ptr(out_seq),
                                             max_new, ptr(step_dev), ptr(slot_dev), ptr(pos), ptr(kmask), Lmax, B, ptr(alive),
                                             stream()), "ta_greedy_advance")
@@ -741,7 +767,7 @@ class Qwen3MI355X(torch.nn.Module):
         graph = None
         want_graph = use_graph and dev.type == "cuda" and not _lib.DRY_RUN and max_new > 3      # (``use_graph=False``: eager steps)
         if per_token:
-            yield out_seq[:, 0].cpu()
+            yield (out_seq[:, 0].cpu(), sc_lp[:, 0].cpu()) if want_scores else out_seq[:, 0].cpu()
         for t in range(1, max_new):
             if (per_token or t % sync_every == 0) and int(alive.item()) == 0:
                 break
@@ -756,7 +782,7 @@ class Qwen3MI355X(torch.nn.Module):
             else:
                 step()
             if per_token:
-                yield out_seq[:, t].cpu()
+                yield (out_seq[:, t].cpu(), sc_lp[:, t].cpu()) if want_scores else out_seq[:, t].cpu()
         seq = out_seq.cpu()
         # HF stops right after the step in which the last clip finished: trim the surplus (all-pad) columns
         n_new = max_new
@@ -764,6 +790,11 @@ class Qwen3MI355X(torch.nn.Module):
             is_eos = torch.isin(seq, torch.tensor(list(eos_ids), dtype=i64))
             first = torch.where(is_eos.any(-1), is_eos.to(torch.int8).argmax(-1) + 1, torch.full((B,), max_new + 1))
             n_new = min(max_new, int(first.max()))
+        if want_scores:
+            yield out_seq[:, :n_new], dict(token_logprobs=sc_lp[:, :n_new], token_entropy=sc_ent[:, :n_new],
+                                           top_token_ids=sc_ids[:, :n_new] if n_top else None,
+                                           top_logprobs=sc_top[:, :n_new] if n_top else None)
+            return
         yield out_seq[:, :n_new]
 
 

@@ -35,8 +35,8 @@ def _req(t, dtype=None):
 
 # The library reads its environment knobs once (csrc/gemm.hip GemmKnobs::load, the decode switch of generate.hip); tests and A/B
 # scripts switch them between launches, so the wrapper calls ta_gemm_reload_knobs() whenever one has changed since the previous call.
-# These three are all the library has (plus TA355_ENC_QKV_FUSED, read per call).
-_KNOB_KEYS = ("TA355_GEMM_VARIANT", "TA355_GELU_LUT", "TA355_DECODE_FUSED")
+# These four are all the library has (plus TA355_ENC_QKV_FUSED, read per call).
+_KNOB_KEYS = ("TA355_GEMM_VARIANT", "TA355_GELU_LUT", "TA355_DECODE_FUSED", "TA355_SCORES_SPLIT")
 _knob_state = None
 
 
@@ -615,3 +615,38 @@ def ctc_align(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_
                              int(blank_id), ptr(frames), ptr(score), ptr(status), ptr(ws), ws_bytes, ptr(trellis), ptr(trellis_off),
                              stream()), "ta_ctc_align_f32")
     return frames, score, status, trellis
+
+
+# ----------------------------------------------------------------------------- decoding scores (csrc/generate.hip)
+MAX_TOP_LOGPROBS = 8      # the per-lane candidate list of token_scores_kernel
+
+
+def token_scores(logits, chosen, V, top_k=0):
+    """ta_token_scores_f32 on one step of logits a caller holds: ``logits`` f32 [B, ld] (unit column stride, the first ``V`` columns are
+    valid and may hold -inf; the rest is never read), ``chosen`` int64 [B] within [0, V) -> (logprob f32 [B] = log softmax(logits[:, :V])
+    at ``chosen``, entropy f32 [B], top_ids int64 [B, top_k], top_logprobs f32 [B, top_k]): the ``top_k`` <= 8 most probable tokens in
+    descending order, lowest index first on ties, slots beyond the finite entries (-1, -inf).  ``chosen`` is compared with V on the
+    host (one synchronisation: this is the convenience form; the decode loop calls the C entry point with device-resident state)."""
+    if not (logits.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("token_scores needs the logits on a HIP device: there is no CPU path")
+    if logits.dim() != 2 or logits.dtype != F32 or not (logits.stride(1) == 1 or logits.numel() == 0):
+        raise ValueError("token_scores: logits must be f32 [B, ld] with unit column stride")
+    B, V, top_k = logits.shape[0], int(V), int(top_k)
+    ld = logits.stride(0) if B > 1 else logits.shape[1]
+    if not 0 < V <= logits.shape[1]:
+        raise ValueError(f"token_scores: V = {V} is outside (0, {logits.shape[1]}]")
+    if ld < V:
+        raise ValueError("token_scores: logits rows overlap")
+    if not 0 <= top_k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"token_scores: top_k = {top_k} is outside [0, {MAX_TOP_LOGPROBS}]")
+    if chosen.dtype != torch.int64 or chosen.shape != (B,) or not chosen.is_contiguous() or chosen.device != logits.device:
+        raise ValueError(f"token_scores: chosen must be a contiguous int64 [{B}] on the logits' device")
+    if B and not bool(((chosen >= 0) & (chosen < V)).all()):
+        raise ValueError(f"token_scores: chosen holds an id outside [0, {V})")
+    dev = logits.device
+    logprob, entropy = torch.empty(B, device=dev, dtype=F32), torch.empty(B, device=dev, dtype=F32)
+    top_ids = torch.empty((B, top_k), device=dev, dtype=torch.int64)
+    top_lp = torch.empty((B, top_k), device=dev, dtype=F32)
+    check(lib().ta_token_scores_f32(ptr(logits), ld, V, B, ptr(chosen), None, None, 1, top_k, ptr(logprob), ptr(entropy),
+                                    ptr(top_ids) if top_k else None, ptr(top_lp) if top_k else None, stream()), "ta_token_scores_f32")
+    return logprob, entropy, top_ids, top_lp

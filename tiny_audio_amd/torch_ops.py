@@ -7,6 +7,8 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
+    ta355::token_scores        compute_transition_scores on one step's processed logits (TF:generation/utils.py); the reference
+                               asks HF for no scores (tiny_audio/asr_modeling.py:631-637)
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
     ta355::encoder_forward_ragged   the same seam, every clip at its own length (opt-in; what the reference computes for a
                                clip encoded alone, tiny_audio/asr_modeling.py:198-200)
@@ -145,6 +147,23 @@ def _(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, 
     N = cu_frames.shape[0] - 1
     return (tokens.new_empty(tokens.shape), emission.new_empty((N,)), tokens.new_empty((N,)),
             emission.new_empty((trellis_numel if trellis_off is not None else 0,)))
+
+
+# ============================================================================ decoding scores
+@torch.library.custom_op("ta355::token_scores", mutates_args=())
+def token_scores(logits: Tensor, chosen: Tensor, V: int, top_k: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """One step of f32 logits [B, ld] (V valid columns, -inf allowed) and the chosen ids i64 [B] -> (logprob f32 [B] = log softmax at the
+    chosen id, entropy f32 [B], top_ids i64 [B, top_k], top_logprobs f32 [B, top_k]; ``ops.token_scores``).  The decode loop runs the
+    same kernel inside its captured step (``ASRModel.generate(return_token_scores=True)``); this is for callers who hold their own
+    logits.  No autograd."""
+    from . import ops
+    return ops.token_scores(logits, chosen, V, top_k)
+
+
+@token_scores.register_fake
+def _(logits, chosen, V, top_k):
+    B = logits.shape[0]
+    return (logits.new_empty((B,)), logits.new_empty((B,)), chosen.new_empty((B, top_k)), logits.new_empty((B, top_k)))
 
 
 # ============================================================================ frozen encoder
@@ -634,4 +653,5 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
-             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align")
+             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
+             "token_scores")
