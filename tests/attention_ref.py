@@ -16,18 +16,18 @@ Two forms of the same function:
                   (tests/test_attention_ref.py), which is what ties the two forms together.
 
 Rounding points of the kernels (file:line of the instruction that rounds), all modelled below:
-  R1  Q after norm / RoPE -> bf16         attention.hip:799-800 (fused forward, query fragments = the stored Q), qkv_post.hip:164
-  R2  K after norm / RoPE -> bf16         attention.hip:718 (fused forward, in place in LDS and to Ko), qkv_post.hip:164
-  R3  P~ = exp(s - rowmax) -> bf16        attention.hip:355 (tiled), :536 (resident K/V), :892 (fused): ``pack_p`` before P V.  The softmax
-      denominator is accumulated by the SAME MFMA from a row of ones (:245, :734), so  l = sum_k bf16(P~)  -- the rounded values.
-  R4  O = (sum_k bf16(P~) V) / l -> bf16  attention.hip:386-387, :558-559, :914-915
-      LSE = rowmax * scale + log(l), f32   attention.hip:390, :564, :920 (1e30 on rows with no visible key)
+  R1  Q after norm / RoPE -> bf16         attention.hip:657-658 (fused forward, query fragments = the stored Q), qkv_post.hip:164
+  R2  K after norm / RoPE -> bf16         attention.hip:574 (fused forward, in place in LDS and to Ko), qkv_post.hip:164
+  R3  P~ = exp(s - rowmax) -> bf16        attention.hip:269 (pv_accumulate, every forward kernel): ``pack_p`` before P V.  The softmax
+      denominator is accumulated by the SAME MFMA from a row of ones (:313, :590), so  l = sum_k bf16(P~)  -- the rounded values.
+  R4  O = (sum_k bf16(P~) V) / l -> bf16  attention.hip:413-414 (tiled), :730-731 (fused)
+      LSE = rowmax * scale + log(l), f32   attention.hip:417, :736 (1e30 on rows with no visible key)
   R5  backward: P = exp(s * scale - LSE) with the stored f32 LSE; dS = P (dP - Delta) scale; P and dS -> bf16 before the products
-      dV += P^T dO, dK += dS^T Q, dQ += dS K      attention.hip:1134 (dQ body), :1277-1278 (dK / dV body)
+      dV += P^T dO, dK += dS^T Q, dQ += dS K      attention.hip:949 (dQ body), :1090-1091 (dK / dV body)
       Delta = rowsum(dO o O) over the bf16 O, f32  qkv_post.hip attn_bwd_prep_kernel
-  R6  un-fused backward: dQ / dK / dV -> bf16    attention.hip:1162 (dQ), :1313-1315 (dK, dV); ta_lm_qkv_post_bwd then works from
+  R6  un-fused backward: dQ / dK / dV -> bf16    attention.hip:977 (dQ), :1126-1128 (dK, dV); ta_lm_qkv_post_bwd then works from
       those bf16 values and rounds d(qkv0) once more (qkv_post.hip, lm_qkv_post_bwd_kernel)
-  R7  fused backward: RoPE^T and the RMSNorm backward run on the f32 accumulators, d(qkv0) -> bf16   attention.hip:1029-1030
+  R7  fused backward: RoPE^T and the RMSNorm backward run on the f32 accumulators, d(qkv0) -> bf16   attention.hip:845-846
 rq / rk are f32.  Everything between two rounding points is f32 in the kernels and float64 here: fp32 accumulation contributes
 ~2^-24 * L, far below bf16's 2^-9.
 """

@@ -1,4 +1,4 @@
-"""-m gpu: every attention entry point of the LM (fused short-sequence forward, resident / tiled forward, segment-aware forms, the
+"""-m gpu: every attention entry point of the LM (fused short-sequence forward, tiled forward, segment-aware forms, the
 backward with and without the fused q|k|v epilogue, ta_lm_qkv_post_fwd / _bwd) against the float64 reference of
 tests/attention_ref.py, row by row.
 
@@ -15,6 +15,8 @@ Every check prints  ``GRID <entry point> <case> <tensor> e/m=<ratio> worst=(b, h
 Worst e/m per entry point on the MI355X with the inputs as they are drawn now (gate: 2; every case passes, no kernel change was needed):
   ta_attention_fwd_qkv      O 1.021 (g2-L150-left37-nr)  LSE 1.000  Q 1.000  K 1.000      ta_attention_fwd_qkv_seg  O, LSE, Q, K 1.000
   ta_attention_fwd          O 1.064 (g2-L200-left37-nr)  LSE 1.001 (g2-L150-noncausal)     ta_attention_fwd_seg      O, LSE 1.000
+    (the tiled kernel at every L since the resident two-kernel form was deleted; worst over the unpacked L <= 192 cases that moved to
+    it: O 1.021 (g2-L150-left37-nr), LSE 1.000 -- the deleted kernel's figures: O and LSE are bit-identical, profiles/attention_refactor.md)
   ta_lm_qkv_post_fwd        Q, K 1.000                                                     ta_lm_qkv_post_bwd        d(qkv0) 1.000
   ta_attention_bwd          dQ 1.000  dK 1.000  dV 1.012 (g2-L150-left37-0)                ta_attention_bwd_seg      dQ, dK, dV 1.000
   ta_attention_bwd_qkv      d(qkv0) 1.000 (V given and V = NULL, bit-identical)            ta_attention_bwd_qkv_seg  d(qkv0) 1.001
@@ -34,8 +36,8 @@ Instantiation -> case id (forward: attn_fwd_gqa_qkv_kernel<128,3,2,6, PAIR, NORM
    0    1    1    1    g1-L192-seg63_2_63_64-nr, g4-L96-seg40_56-nr
    0    1    0    1    g1-L192-seg63_2_63_64-n   0 0 1 1  g1-L192-seg63_2_63_64-r   0 0 0 1  g1-L192-seg63_2_63_64-0
 Forward, other kernels (test_forward_two_kernel):
-  attn_fwd_gqa_kernel (resident K/V, ta_attention_fwd at L <= 192)     every unpacked case with L <= 192
-  attn_fwd_kernel<128, true, 1, false> (tiled)                         g2-L200-*, g2-L320-*, g1-L200-none-nr, g4-L200-left37-nr
+  attn_fwd_kernel<128, true, 1, false> (tiled, ta_attention_fwd)       every unpacked causal case: L 33 ... 192 (g1, g2, g4), g2-L200-*,
+                                                                       g2-L320-*, g1-L200-none-nr, g4-L200-left37-nr
   attn_fwd_kernel<128, true, 1, true>  (tiled, SEG)                    every packed case (L 96, 192, 320)
   attn_fwd_kernel<128, false, 1>                                       g2-L150-noncausal
 Backward: attn_bwd_kernel<128, CAUSAL, NORM, ROPE, SEG> (NORM / ROPE matter in the fused epilogue only: test_backward_fused)
@@ -289,7 +291,7 @@ def test_forward_fused(cid):
 
 @pytest.mark.parametrize("cid", ALL)
 def test_forward_two_kernel(cid):
-    """ta_lm_qkv_post_fwd, then ta_attention_fwd (resident K/V at L <= 192 inside the envelope, tiled beyond) or ta_attention_fwd_seg."""
+    """ta_lm_qkv_post_fwd, then ta_attention_fwd (the tiled kernel at every L) or ta_attention_fwd_seg."""
     r = ref(cid); c = r.c; a = device_args(r)
     Q, K, V, QT, KT, VT, rq, rk = ops.lm_qkv_post_fwd(a.qkv0, a.qn, a.kn, a.cos, a.sin, B, c.Hq, c.Hkv, c.L, pos=a.pos)
     torch.cuda.synchronize()

@@ -3,9 +3,12 @@
 //   attn_fwd_kernel<64,false>   GLM-ASR encoder self-attention: non-causal, NO mask (padded frames are
 //                               attended to, exactly as the reference does), 20 heads x 64
 //                               (TF:models/glmasr/modeling_glmasr.py:187-217)
-//   attn_fwd_kernel<128,true>   Qwen3 attention: causal + key-padding mask, GQA 16q/8kv x 128
+//   attn_fwd_kernel<128,true>   Qwen3 attention: causal + key-padding mask, GQA 16q/8kv x 128, tiled over the keys; SEG = packed rows
 //                               (TF:models/qwen3/modeling_qwen3.py:185-208,264-275)
-//   attn_bwd_dq_kernel / attn_bwd_dkv_kernel   activation gradients of the latter (frozen LM, dX only)
+//   attn_fwd_gqa_qkv_kernel     the same for short sequences (L <= 192): K / V of a (clip, kv head) resident in LDS, q/k-norm and RoPE
+//                               applied while staging, straight from the q|k|v GEMM output
+//   attn_bwd_kernel             activation gradients of the LM's attention (frozen LM, dX only): one launch, dK / dV and dQ bodies
+// The forward kernels share one online-softmax tile: qk_scores, softmax_tile, pv_accumulate.
 //
 // Formulation: everything is computed TRANSPOSED so that the softmax row (one query) lives in one
 // lane column:  S^T[key,q] = K Q^T  -> lane holds q = lane&15 and 4 consecutive keys per 16-key
@@ -210,6 +213,71 @@ __device__ __forceinline__ int wave_max_i(int v) {
   return __builtin_amdgcn_readfirstlane(v);
 }
 
+// ---- the online-softmax tile of one wave over 64 keys, in the three pieces every forward kernel is built from.  s[sub][kt] is S^T of
+// key block kt (16 keys) for query sub-tile sub, o[sub][0 .. ND - 1] is O^T and o[sub][ND] the row-sum block.  What the kernels differ
+// in stays with the caller: masking (between qk_scores and softmax_tile), where the V fragments come from, the epilogue -- and FENCE,
+// the scheduling fences of the resident kernel, which keep the fragments of one block live at a time (VGPR budget).
+// S^T = K Q^T for every query sub-tile: each K fragment read from the row tile feeds QSUB MFMAs
+template <int HD, int QSUB, bool FENCE>
+__device__ __forceinline__ void qk_scores(const char* Kt, const bf16x8 (&qf)[QSUB][HD / 32], f32x4 (&s)[QSUB][4], int l15, int g) {
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) {
+#pragma unroll
+    for (int sub = 0; sub < QSUB; ++sub) s[sub][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < HD / 32; ++ks) {
+      const bf16x8 a = *(const bf16x8*)(Kt + RowTile<HD>::off(kt * 16 + l15, ks * 4 + g));
+#pragma unroll
+      for (int sub = 0; sub < QSUB; ++sub)
+        s[sub][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, qf[sub][ks], s[sub][kt], 0, 0, 0);
+    }
+    if (FENCE) __builtin_amdgcn_sched_barrier(0);
+  }
+}
+// online softmax numerators of one sub-tile, masked scores already -inf (the denominator rides in the MFMA of pv_accumulate)
+template <int ND>
+__device__ __forceinline__ void softmax_tile(f32x4 (&s)[4], f32x4 (&o)[ND + 1], float& m_run, float sl2) {
+  float mloc = max3(s[0][0], s[0][1], s[0][2]);
+  mloc = max3(mloc, s[0][3], s[1][0]);
+  mloc = max3(mloc, s[1][1], s[1][2]);
+  mloc = max3(mloc, s[1][3], s[2][0]);
+  mloc = max3(mloc, s[2][1], s[2][2]);
+  mloc = max3(mloc, s[2][3], s[3][0]);
+  mloc = max3(mloc, s[3][1], s[3][2]);
+  mloc = fmaxf(mloc, s[3][3]);
+  const float m_new = fmaxf(m_run, group_max(mloc));
+  if (__any(m_new != m_run)) {                       // rescale only when some row's running max moved
+    const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sl2);
+#pragma unroll
+    for (int i = 0; i <= ND; ++i) { o[i][0] *= alpha; o[i][1] *= alpha; o[i][2] *= alpha; o[i][3] *= alpha; }
+    m_run = m_new;
+  }
+  const float mb = m_new * sl2;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[kt][r] = __builtin_amdgcn_exp2f(fmaf(s[kt][r], sl2, -mb));
+}
+// [O^T ; l] += [V^T ; 1] P^T.  vfrag(dt, kp) = the A fragment of row block dt (ND: the block whose first row is all ones) over the
+// keys of block pair kp, i.e. columns [c, c + 4) for c = (2 kp) * 16 + g * 4 and (2 kp + 1) * 16 + g * 4
+template <int ND, int QSUB, bool FENCE, typename VF>
+__device__ __forceinline__ void pv_accumulate(const f32x4 (&s)[QSUB][4], f32x4 (&o)[QSUB][ND + 1], VF&& vfrag) {
+#pragma unroll
+  for (int kp = 0; kp < 2; ++kp) {
+    bf16x8 pb[QSUB];
+#pragma unroll
+    for (int sub = 0; sub < QSUB; ++sub) pb[sub] = pack_p(s[sub][2 * kp], s[sub][2 * kp + 1]);
+#pragma unroll
+    for (int dt = 0; dt <= ND; ++dt) {
+      const bf16x8 va = vfrag(dt, kp);
+#pragma unroll
+      for (int sub = 0; sub < QSUB; ++sub)
+        o[sub][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[sub], o[sub][dt], 0, 0, 0);
+      if (FENCE && (dt & 1)) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
 // One workgroup = 128 query rows of one head (4 waves x 2 sub-tiles of 16 rows): every K / V^T fragment read from LDS
 // feeds two MFMAs.  The softmax denominator is NOT summed on the VALU: the V^T image carries 16 extra rows whose
 // first is all ones, so one extra MFMA block per k-step accumulates l = sum_k P[q,k] next to O (and is rescaled
@@ -294,19 +362,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
     }
     // ---- S^T = K Q^T for both query sub-tiles
     f32x4 s[QSUB][4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int sub = 0; sub < QSUB; ++sub) s[sub][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        const bf16x8 a = *(const bf16x8*)(Ks + RowTile<HD>::off(kt * 16 + l15, ks * 4 + g));
-#pragma unroll
-        for (int sub = 0; sub < QSUB; ++sub)
-          s[sub][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, qf[sub][ks], s[sub][kt], 0, 0, 0);
-      }
-    }
-    // ---- online softmax numerators (the denominator rides in the MFMA below)
+    qk_scores<HD, QSUB, false>(Ks, qf, s, l15, g);
 #pragma unroll
     for (int sub = 0; sub < QSUB; ++sub) {
       const int qrow = q0 + sub * 16 + l15;
@@ -326,47 +382,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
           }
         }
       }
-      float mloc = max3(s[sub][0][0], s[sub][0][1], s[sub][0][2]);
-      mloc = max3(mloc, s[sub][0][3], s[sub][1][0]);
-      mloc = max3(mloc, s[sub][1][1], s[sub][1][2]);
-      mloc = max3(mloc, s[sub][1][3], s[sub][2][0]);
-      mloc = max3(mloc, s[sub][2][1], s[sub][2][2]);
-      mloc = max3(mloc, s[sub][2][3], s[sub][3][0]);
-      mloc = max3(mloc, s[sub][3][1], s[sub][3][2]);
-      mloc = fmaxf(mloc, s[sub][3][3]);
-      const float m_new = fmaxf(m_run[sub], group_max(mloc));
-      if (__any(m_new != m_run[sub])) {              // rescale only when some row's running max moved
-        const float alpha = __builtin_amdgcn_exp2f((m_run[sub] - m_new) * sl2);
-#pragma unroll
-        for (int i = 0; i <= ND; ++i) { o[sub][i][0] *= alpha; o[sub][i][1] *= alpha; o[sub][i][2] *= alpha; o[sub][i][3] *= alpha; }
-        m_run[sub] = m_new;
-      }
-      const float mb = m_new * sl2;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[sub][kt][r] = __builtin_amdgcn_exp2f(fmaf(s[sub][kt][r], sl2, -mb));
+      softmax_tile<ND>(s[sub], o[sub], m_run[sub], sl2);
     }
-    // ---- [O^T ; l] += [V^T ; 1] P^T
-#pragma unroll
-    for (int kp = 0; kp < 2; ++kp) {
-      bf16x8 pb[QSUB];
-#pragma unroll
-      for (int sub = 0; sub < QSUB; ++sub) pb[sub] = pack_p(s[sub][2 * kp], s[sub][2 * kp + 1]);
-#pragma unroll
-      for (int dt = 0; dt <= ND; ++dt) {
-        const bf16x8 va = read_colfrag(Vs, dt * 16 + l15, (2 * kp) * 16 + g * 4, (2 * kp + 1) * 16 + g * 4);
-#pragma unroll
-        for (int sub = 0; sub < QSUB; ++sub)
-          o[sub][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[sub], o[sub][dt], 0, 0, 0);
-      }
-    }
+    // the V^T column tile carries its ones-row block as rows HD .. HD + 15
+    pv_accumulate<ND, QSUB, false>(s, o, [&](int dt, int kp) {
+      return read_colfrag(Vs, dt * 16 + l15, (2 * kp) * 16 + g * 4, (2 * kp + 1) * 16 + g * 4);
+    });
     __syncthreads();
   };
-  int nfull = (kmask == nullptr) ? L / KV_TILE : 0;
+  int nfull = L / KV_TILE;
   if (CAUSAL) nfull = min(nfull, (qt * QROWS) / KV_TILE);      // keys of tiles below the first query row of the workgroup
   nfull = min(nfull, ntiles);
-  if (valign & 4) nfull = 0;                                   // experiment (TA355_ATTN_NOPEEL=1): every tile takes the general body
+  if (kmask) nfull = 0;                                         // a key mask: every tile takes the general body
   if constexpr (SEG) {                                          // every tile from the first one needed takes the general body
     for (int t = t0; t < ntiles; ++t) tile(t, std::true_type{});
   } else {
@@ -390,181 +417,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
       if (LSE && g == 0) LSE[(long)(b * Hq + h) * L + qrow] = l_run > 0.f ? m_run[sub] * scale + __logf(l_run) : 1.0e30f;
     }
   }
-}
-
-// ============================================================================ forward, short sequences (LM, L <= 192)
-// One workgroup = one (clip, kv head): ALL keys / values of the sequence are staged once (3 K row tiles + 3 V^T column
-// tiles, 102 KB of LDS) and shared by every query of the GQA group -- 2 q heads x 192 queries = 12 waves x 2 sub-tiles
-// of 16 rows.  After the single staging barrier each wave walks its causal key range alone: no barriers, no
-// re-staging, and B * Hkv = 256 workgroups are one round of the 256 CUs.  (The tiled kernel above spent its time in
-// 1536 small workgroups that each re-staged K / V for 64 queries: 42 us per layer for 4.8 GFLOP.)
-template <int HD, int MAXT, int QSUB, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                           const bf16_t* __restrict__ VT, bf16_t* __restrict__ O,
-                                                           float* __restrict__ LSE, const int* __restrict__ kmask,
-                                                           int B, int Hq, int Hkv, int L, int Lp, float scale) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ND = HD / 16, VBYTES = (HD + 16) * CT_STRIDE, NT_ = NW * 64;
-  char* Ks = smem;                                   // MAXT row tiles
-  char* Vs = smem + MAXT * RowTile<HD>::BYTES;       // MAXT column tiles, each with its ones-row block
-  int* Ms = (int*)(Vs + MAXT * VBYTES);              // key mask, MAXT * 64
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, l15 = lane & 15;
-  const int b = blockIdx.x / Hkv, hk = blockIdx.x % Hkv;
-  // query chunks of 16 * QSUB rows: chunk c belongs to q head c / cph; a wave takes chunk `wave` and then its mirror
-  // image (nchunk - 1 - wave), which pairs a short causal key range with a long one
-  const int grp = Hq / Hkv, cph = (L + 16 * QSUB - 1) / (16 * QSUB), nchunk = grp * cph;
-  const bf16_t* Kb = K + ((long)(b * Hkv + hk) * L) * HD;
-  const bf16_t* Vb = VT + ((long)(b * Hkv + hk) * HD) * Lp;
-  const float sl2 = scale * LOG2E;
-  const int ntiles = (L + KV_TILE - 1) / KV_TILE;
-  // ---- stage everything once.  All global loads are issued before the first LDS store (MAXT * 1024 16-B chunks of K
-  // and of V^T = 4 + 4 per thread): a load -> store loop per tile serialises 12 round trips to memory (measured: the
-  // kernel took 38 us that way, no faster than the tiled one).
-  constexpr int PER = (MAXT * 64 * (HD / 8) + NT_ - 1) / NT_;
-  uint4 kreg[PER], vreg[PER];
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int ch = tid + i * NT_, t = ch / (64 * (HD / 8)), w = ch % (64 * (HD / 8));
-    if (t < ntiles) {
-      const int r = w / (HD / 8), c = w % (HD / 8);
-      int gr = t * KV_TILE + r; if (gr > L - 1) gr = L - 1;
-      kreg[i] = *(const uint4*)(Kb + (long)gr * HD + c * 8);
-      const int vr = w >> 3, vc = w & 7;
-      vreg[i] = *(const uint4*)(Vb + (long)vr * Lp + t * KV_TILE + vc * 8);
-    }
-  }
-  for (int i = tid; i < ntiles * 16 * (CT_STRIDE / 4); i += NT_) {
-    const int t = i / (16 * (CT_STRIDE / 4)), w = i % (16 * (CT_STRIDE / 4)), r = w / (CT_STRIDE / 4);
-    ((uint32_t*)(Vs + t * VBYTES + HD * CT_STRIDE))[w] = r == 0 ? 0x3f803f80u : 0u;
-  }
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int ch = tid + i * NT_, t = ch / (64 * (HD / 8)), w = ch % (64 * (HD / 8));
-    if (t < ntiles) {
-      const int r = w / (HD / 8), c = w % (HD / 8);
-      *(uint4*)(Ks + t * RowTile<HD>::BYTES + RowTile<HD>::off(r, c)) = kreg[i];
-      const int vr = w >> 3, vc = w & 7;
-      const uint4 x = vreg[i];
-      const uint4 y = (vr & 1) ? make_uint4(x.z, x.w, x.x, x.y) : x;
-      *(uint4*)(Vs + t * VBYTES + vr * CT_STRIDE + ((vc ^ ((vr & 15) >> 1)) << 4)) = y;
-    }
-  }
-  for (int i = tid; i < ntiles * 64; i += NT_) Ms[i] = (i < L) ? (kmask ? kmask[(long)b * L + i] : 1) : 0;
-  __syncthreads();
-  for (int pass = 0; pass < 2; ++pass) {
-  const int chunk = pass == 0 ? wave : nchunk - 1 - wave;
-  if (chunk >= nchunk || (pass == 1 && chunk < NW)) continue;          // wave-uniform
-  const int h = hk * grp + chunk / cph;
-  const int q0 = (chunk % cph) * 16 * QSUB;
-  const bf16_t* Qb = Q + ((long)(b * Hq + h) * L) * HD;
-  bf16x8 qf[QSUB][HD / 32];
-#pragma unroll
-  for (int sub = 0; sub < QSUB; ++sub) {
-    int qr = q0 + sub * 16 + l15; if (qr > L - 1) qr = L - 1;
-#pragma unroll
-    for (int ks = 0; ks < HD / 32; ++ks) qf[sub][ks] = *(const bf16x8*)(Qb + (long)qr * HD + ks * 32 + g * 8);
-  }
-  f32x4 o[QSUB][ND + 1];
-#pragma unroll
-  for (int sub = 0; sub < QSUB; ++sub)
-#pragma unroll
-    for (int i = 0; i <= ND; ++i) o[sub][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  float m_run[QSUB];
-#pragma unroll
-  for (int sub = 0; sub < QSUB; ++sub) m_run[sub] = NEG_BIG;
-  const int my_tiles = min(ntiles, (q0 + 16 * QSUB - 1) / KV_TILE + 1);      // causal: keys beyond the wave's last query never count
-  for (int t = 0; t < my_tiles; ++t) {
-    const int key0 = t * KV_TILE;
-    const char* Kt = Ks + t * RowTile<HD>::BYTES;
-    const char* Vt = Vs + t * VBYTES;
-    f32x4 s[QSUB][4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int sub = 0; sub < QSUB; ++sub) s[sub][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        const bf16x8 a = *(const bf16x8*)(Kt + RowTile<HD>::off(kt * 16 + l15, ks * 4 + g));
-#pragma unroll
-        for (int sub = 0; sub < QSUB; ++sub)
-          s[sub][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, qf[sub][ks], s[sub][kt], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);             // keep the K fragments of one key block live at a time (VGPR budget)
-    }
-#pragma unroll
-    for (int sub = 0; sub < QSUB; ++sub) {
-      const int qrow = q0 + sub * 16 + l15;
-      const bool full = (key0 + KV_TILE <= L) && (kmask == nullptr) && (key0 + KV_TILE - 1 <= q0 + sub * 16);
-      if (!full) {
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-          const int4 mk = *(const int4*)(Ms + key0 + kt * 16 + g * 4);
-          const int mkv[4] = {mk.x, mk.y, mk.z, mk.w};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = key0 + kt * 16 + g * 4 + r;
-            const bool v = (key <= qrow) & (mkv[r] != 0);
-            s[sub][kt][r] = v ? s[sub][kt][r] : -INFINITY;
-          }
-        }
-      }
-      float mloc = max3(s[sub][0][0], s[sub][0][1], s[sub][0][2]);
-      mloc = max3(mloc, s[sub][0][3], s[sub][1][0]);
-      mloc = max3(mloc, s[sub][1][1], s[sub][1][2]);
-      mloc = max3(mloc, s[sub][1][3], s[sub][2][0]);
-      mloc = max3(mloc, s[sub][2][1], s[sub][2][2]);
-      mloc = max3(mloc, s[sub][2][3], s[sub][3][0]);
-      mloc = max3(mloc, s[sub][3][1], s[sub][3][2]);
-      mloc = fmaxf(mloc, s[sub][3][3]);
-      const float m_new = fmaxf(m_run[sub], group_max(mloc));
-      if (__any(m_new != m_run[sub])) {
-        const float alpha = __builtin_amdgcn_exp2f((m_run[sub] - m_new) * sl2);
-#pragma unroll
-        for (int i = 0; i <= ND; ++i) { o[sub][i][0] *= alpha; o[sub][i][1] *= alpha; o[sub][i][2] *= alpha; o[sub][i][3] *= alpha; }
-        m_run[sub] = m_new;
-      }
-      const float mb = m_new * sl2;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[sub][kt][r] = __builtin_amdgcn_exp2f(fmaf(s[sub][kt][r], sl2, -mb));
-    }
-#pragma unroll
-    for (int kp = 0; kp < 2; ++kp) {
-      bf16x8 pb[QSUB];
-#pragma unroll
-      for (int sub = 0; sub < QSUB; ++sub) pb[sub] = pack_p(s[sub][2 * kp], s[sub][2 * kp + 1]);
-#pragma unroll
-      for (int dt = 0; dt <= ND; ++dt) {
-        const bf16x8 va = read_colfrag(Vt, dt * 16 + l15, (2 * kp) * 16 + g * 4, (2 * kp + 1) * 16 + g * 4);
-#pragma unroll
-        for (int sub = 0; sub < QSUB; ++sub)
-          o[sub][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[sub], o[sub][dt], 0, 0, 0);
-        if (dt & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-#pragma unroll
-  for (int sub = 0; sub < QSUB; ++sub) {
-    const int qrow = q0 + sub * 16 + l15;
-    const float l_run = __shfl(o[sub][ND][0], l15, 64);
-    if (qrow < L) {
-      const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-      bf16_t* orow = O + ((long)b * L + qrow) * ((long)Hq * HD) + (long)h * HD;
-      // adjacent 16-column blocks are exchanged between lane rows (v_permlane16_swap) so that a lane stores 8
-      // consecutive columns: 64 contiguous bytes per row per store instead of 32 (see gemm.hip epilogue_strip)
-#pragma unroll
-      for (int dt = 0; dt < ND; dt += 2) {
-        const uint32_t x0 = pack2bf(o[sub][dt][0] * inv, o[sub][dt][1] * inv), x1 = pack2bf(o[sub][dt][2] * inv, o[sub][dt][3] * inv);
-        const uint32_t y0 = pack2bf(o[sub][dt + 1][0] * inv, o[sub][dt + 1][1] * inv), y1 = pack2bf(o[sub][dt + 1][2] * inv, o[sub][dt + 1][3] * inv);
-        const auto a = __builtin_amdgcn_permlane16_swap(x0, y0, false, false);
-        const auto c = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
-        *(uint4*)(orow + 16 * (dt + (g & 1)) + 8 * (g >> 1)) = make_uint4(a[0], c[0], a[1], c[1]);
-      }
-      if (LSE && g == 0) LSE[(long)(b * Hq + h) * L + qrow] = l_run > 0.f ? m_run[sub] * scale + __logf(l_run) : 1.0e30f;
-    }
-  }
-  }   // pass
 }
 
 // ---- round 3: global -> LDS DMA staging of [64][128] row tiles for the backward (double-buffered LDS, no staging registers).
@@ -593,7 +445,11 @@ __device__ __forceinline__ unsigned lds_addr_of(const char* p) {
 constexpr int BWD_BUF = 2 * 64 * 128 * 2 + 512;      // one staging buffer of the backward: two row tiles + 128 floats / ints
 
 // ============================================================================ forward, short sequences, straight from the q|k|v GEMM output
-// attn_fwd_gqa_kernel with ta_lm_qkv_post_fwd folded in: one workgroup = one (clip, kv head) reads the PRE-norm q | k | v rows of its
+// One workgroup = one (clip, kv head): ALL keys / values of the sequence are staged once (3 K + 3 V row tiles, 97 KB of LDS) and shared
+// by every query of the GQA group -- 2 q heads x 192 queries = 12 wave passes x 2 sub-tiles of 16 rows.  After the staging barriers
+// each wave walks its causal key range alone: no barriers, no re-staging, and B * Hkv = 256 workgroups are one round of the 256 CUs.
+// (The tiled kernel above spent its time in 1536 small workgroups that each re-staged K / V for 64 queries: 42 us per layer for
+// 4.8 GFLOP.)  ta_lm_qkv_post_fwd is folded in: the workgroup reads the PRE-norm q | k | v rows of its
 // GQA group from the token-major GEMM output, applies the per-head RMSNorm (q_norm / k_norm) and RoPE while staging
 // (TF:models/qwen3/modeling_qwen3.py:50-64,211-240), keeps K and V as ROW tiles in LDS (the V^T operand of the second product is read
 // transposed with ds_read_b64_tr_b16, the row of ones that accumulates the softmax denominator is a constant fragment) and writes
@@ -792,8 +648,10 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float n1 = NORM ? x[ks][e] * rr * w1[e] : x[ks][e], n2 = NORM ? x[ks + 2][e] * rr * w2[e] : x[ks + 2][e];
-        y1[e] = ROPE ? n1 * cs[e] - n2 * sn[e] : n1;
-        y2[e] = ROPE ? n2 * cs[e] + n1 * sn[e] : n2;
+        // which product of a * b + c * d is fused is written out: left to the compiler's contraction it followed the instruction
+        // order of unrelated code further down (the tile loop), see profiles/attention_refactor.md
+        y1[e] = ROPE ? fmaf(n1, cs[e], -(n2 * sn[e])) : n1;
+        y2[e] = ROPE ? fmaf(n1, sn[e], n2 * cs[e]) : n2;
       }
       union { bf16x8 v; uint4 u; } a, c;
       a.u = make_uint4(pack2bf(y1[0], y1[1]), pack2bf(y1[2], y1[3]), pack2bf(y1[4], y1[5]), pack2bf(y1[6], y1[7]));
@@ -833,19 +691,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
     const char* Kt = Ks + t * RowTile<HD>::BYTES;
     const char* Vt = Vs + t * RowTile<HD>::BYTES;
     f32x4 s[QSUB][4];
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int sub = 0; sub < QSUB; ++sub) s[sub][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < HD / 32; ++ks) {
-        const bf16x8 a = *(const bf16x8*)(Kt + RowTile<HD>::off(kt * 16 + l15, ks * 4 + g));
-#pragma unroll
-        for (int sub = 0; sub < QSUB; ++sub)
-          s[sub][kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, qf[sub][ks], s[sub][kt], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    qk_scores<HD, QSUB, true>(Kt, qf, s, l15, g);
 #pragma unroll
     for (int sub = 0; sub < QSUB; ++sub) {
       const int qrow = q0 + sub * RSTEP + l15;
@@ -864,41 +710,11 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_gqa_qkv_kernel(const bf16_t*
           }
         }
       }
-      float mloc = max3(s[sub][0][0], s[sub][0][1], s[sub][0][2]);
-      mloc = max3(mloc, s[sub][0][3], s[sub][1][0]);
-      mloc = max3(mloc, s[sub][1][1], s[sub][1][2]);
-      mloc = max3(mloc, s[sub][1][3], s[sub][2][0]);
-      mloc = max3(mloc, s[sub][2][1], s[sub][2][2]);
-      mloc = max3(mloc, s[sub][2][3], s[sub][3][0]);
-      mloc = max3(mloc, s[sub][3][1], s[sub][3][2]);
-      mloc = fmaxf(mloc, s[sub][3][3]);
-      const float m_new = fmaxf(m_run[sub], group_max(mloc));
-      if (__any(m_new != m_run[sub])) {
-        const float alpha = __builtin_amdgcn_exp2f((m_run[sub] - m_new) * sl2);
-#pragma unroll
-        for (int i = 0; i <= ND; ++i) { o[sub][i][0] *= alpha; o[sub][i][1] *= alpha; o[sub][i][2] *= alpha; o[sub][i][3] *= alpha; }
-        m_run[sub] = m_new;
-      }
-      const float mb = m_new * sl2;
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s[sub][kt][r] = __builtin_amdgcn_exp2f(fmaf(s[sub][kt][r], sl2, -mb));
+      softmax_tile<ND>(s[sub], o[sub], m_run[sub], sl2);
     }
-#pragma unroll
-    for (int kp = 0; kp < 2; ++kp) {
-      bf16x8 pb[QSUB];
-#pragma unroll
-      for (int sub = 0; sub < QSUB; ++sub) pb[sub] = pack_p(s[sub][2 * kp], s[sub][2 * kp + 1]);
-#pragma unroll
-      for (int dt = 0; dt <= ND; ++dt) {
-        const bf16x8 va = dt < ND ? read_colfrag_tr<HD>(Vt, dt, l15, (2 * kp) * 16 + g * 4, (2 * kp + 1) * 16 + g * 4) : one_row;
-#pragma unroll
-        for (int sub = 0; sub < QSUB; ++sub)
-          o[sub][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va, pb[sub], o[sub][dt], 0, 0, 0);
-        if (dt & 1) __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    pv_accumulate<ND, QSUB, true>(s, o, [&](int dt, int kp) {
+      return dt < ND ? read_colfrag_tr<HD>(Vt, dt, l15, (2 * kp) * 16 + g * 4, (2 * kp + 1) * 16 + g * 4) : one_row;
+    });
   }
   ATTN_STAMP(blockIdx.x + 6144, 6 + 3 * pass, 0);                                   // tile loop done
 #pragma unroll
@@ -1037,8 +853,7 @@ __device__ __forceinline__ void qkv_post_bwd_tile(const char* st, const QkvPostB
 // grid (q tiles, Hq, B).  dQ^T[d,q] = sum_key K^T[d,key] dS^T[key,q],  dS = P o (dP - Delta) * scale
 template <int HD, bool CAUSAL, bool NORM, bool ROPE, bool SEG>
 __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
-                                                 const bf16_t* __restrict__ V, const bf16_t* __restrict__ KT,
-                                                 const bf16_t* __restrict__ dO, long dO_stride,
+                                                 const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO, long dO_stride,
                                                  const float* __restrict__ LSE, const float* __restrict__ Delta,
                                                  const int* __restrict__ kmask, bf16_t* __restrict__ dQ,
                                                  int B, int Hq, int Hkv, int L, int Lp, float scale, const QkvPostBwd& F,
@@ -1058,7 +873,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
   const long ldq = (long)(Hq + 2 * Hkv) * HD;
   const bf16_t* Vb = V ? V + ((long)(b * Hkv + hk) * L) * HD : F.qkv0 + (long)b * L * ldq + (long)(Hq + Hkv + hk) * HD;
   const long v_rs = V ? HD : ldq;
-  (void)KT; (void)Lp;
+  (void)Lp;
   const bf16_t* dOb = dO + (long)b * L * dO_stride + (long)h * HD;   // token-major rows
   const float sl2 = scale * LOG2E;
   bf16x8 qf[HD / 32], dof[HD / 32];
@@ -1169,10 +984,8 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* smem, int block_id, const
 // grid (key tiles, Hkv, B); loops over the Hq/Hkv query heads of the group and over query tiles.
 //   dV^T[d,key] += dO^T[d,q] P[q,key]      dK^T[d,key] += Q^T[d,q] dS[q,key]
 template <int HD, bool CAUSAL, bool NORM, bool ROPE, bool SEG>
-__device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ QT,
-                                                  const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
-                                                  const bf16_t* __restrict__ dO, long dO_stride,
-                                                  const bf16_t* __restrict__ dOT,
+__device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
+                                                  const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO, long dO_stride,
                                                   const float* __restrict__ LSE, const float* __restrict__ Delta,
                                                   const int* __restrict__ kmask, bf16_t* __restrict__ dK,
                                                   bf16_t* __restrict__ dV, int B, int Hq, int Hkv, int L, int Lp,
@@ -1322,24 +1135,31 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* smem, int block_id, cons
 // are independent (both only read Q, K, V, dO), so a single grid lets the dQ workgroups fill the CUs while the longer
 // dK / dV ones drain, without a second stream or a kernel boundary in between.  The heavier dK / dV blocks go first.
 template <int HD, bool CAUSAL, bool NORM = true, bool ROPE = true, bool SEG = false>      // NORM / ROPE: the fused epilogue's variant (qkv_post_bwd_tile)
-__global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ QT,
-                                                       const bf16_t* __restrict__ K, const bf16_t* __restrict__ KT,
+__global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                        const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO, long dO_stride,
-                                                       const bf16_t* __restrict__ dOT, const float* __restrict__ LSE,
+                                                       const float* __restrict__ LSE,
                                                        const float* __restrict__ Delta, const int* __restrict__ kmask,
                                                        bf16_t* __restrict__ dQ, bf16_t* __restrict__ dK, bf16_t* __restrict__ dV,
                                                        int B, int Hq, int Hkv, int L, int Lp, float scale, int n_dkv,
                                                        const QkvPostBwd F, const int* __restrict__ seg) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if ((int)blockIdx.x < n_dkv)
-    attn_bwd_dkv_body<HD, CAUSAL, NORM, ROPE, SEG>(smem, blockIdx.x, Q, QT, K, V, dO, dO_stride, dOT, LSE, Delta, kmask, dK, dV, B, Hq, Hkv, L, Lp, scale, F, seg);
+    attn_bwd_dkv_body<HD, CAUSAL, NORM, ROPE, SEG>(smem, blockIdx.x, Q, K, V, dO, dO_stride, LSE, Delta, kmask, dK, dV, B, Hq, Hkv, L, Lp, scale, F, seg);
   else
-    attn_bwd_dq_body<HD, CAUSAL, NORM, ROPE, SEG>(smem, blockIdx.x - n_dkv, Q, K, V, KT, dO, dO_stride, LSE, Delta, kmask, dQ, B, Hq, Hkv, L, Lp, scale, F, seg);
+    attn_bwd_dq_body<HD, CAUSAL, NORM, ROPE, SEG>(smem, blockIdx.x - n_dkv, Q, K, V, dO, dO_stride, LSE, Delta, kmask, dQ, B, Hq, Hkv, L, Lp, scale, F, seg);
 }
 
 
 // ----------------------------------------------------------------------------- C-ABI
 template <int HD> static size_t fwd_lds() { return RowTile<HD>::BYTES + (HD + 16) * CT_STRIDE + 64 * 4; }
+// Launch of a kernel that needs more than the default 64 KB of dynamic LDS: the limit is raised on the first launch of each
+// instantiation (one `attr` per KERNEL), so the kernels that have the attribute are by construction the kernels that are launched.
+template <auto KERNEL, typename... Args>
+static void launch_big_lds(dim3 grid, dim3 blk, size_t lds, hipStream_t st, Args... args) {
+  static bool attr = false;
+  if (!attr) { (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+  TA_LAUNCH(KERNEL, grid, blk, lds, st, args...);
+}
 
 extern "C" int ta_attention_fwd(const void* Q, const void* K, const void* VT, void* O, float* LSE, const int* kmask,
                                 int B, int Hq, int Hkv, int L, int Lp, int head_dim, int causal, float scale,
@@ -1351,21 +1171,7 @@ extern "C" int ta_attention_fwd_ex(const void* Q, const void* K, const void* VT,
                                    int B, int Hq, int Hkv, int L, int Lp, int head_dim, int causal, float scale,
                                    const ta_attn_layout* lay_in, hipStream_t st) {
   if (B <= 0 || L <= 0) return TA_OK;
-  if (Hq % Hkv || Lp % 64 || Lp < L) return TA_ERR_ARG;
-  // LM with a short prompt: the whole sequence of a (clip, kv head) lives in LDS, one workgroup serves the GQA group
-  if (!lay_in) {
-    const int grp = Hq / Hkv;
-    if (head_dim == 128 && causal && L <= 192 && grp * ((L + 31) / 32) <= 12) {
-      constexpr int MAXT = 3, QS = 2, NW = 6;          // 6 waves x 2 passes x 32 queries = 384 query rows per workgroup
-      const size_t lds = MAXT * (RowTile<128>::BYTES + (128 + 16) * CT_STRIDE) + MAXT * 64 * 4;
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void*)attn_fwd_gqa_kernel<128, MAXT, QS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-      TA_LAUNCH((attn_fwd_gqa_kernel<128, MAXT, QS, NW>), dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)Q, (const bf16_t*)K,
-                (const bf16_t*)VT, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, Lp, scale);
-      TA_CHECK_LAUNCH();
-      return TA_OK;
-    }
-  }
+  if (Hq % Hkv || Lp % 64 || Lp < L || (head_dim != 64 && head_dim != 128)) return TA_ERR_ARG;
   const long hd = head_dim;
   ta_attn_layout lay = {Hq * L * hd, L * hd, hd, Hkv * L * hd, L * hd, hd, Hkv * hd * Lp, hd * Lp, Lp};   // head-major images
   if (lay_in) lay = *lay_in;
@@ -1377,15 +1183,13 @@ extern "C" int ta_attention_fwd_ex(const void* Q, const void* K, const void* VT,
   // encoder (hd 64, S = 500, non-causal): 128 query rows per workgroup; LM (hd 128, short causal L): 64
   const int qsub = (head_dim == 64) ? 2 : 1;
   dim3 grid(grouped_grid((Hq / Hkv) * ta_cdiv(L, 64 * qsub), B * Hkv)), blk(256);
-#define FWD(HD_, C_)                                                                                              \
-  TA_LAUNCH((attn_fwd_kernel<HD_, C_, (HD_ == 64 ? 2 : 1)>), grid, blk, fwd_lds<HD_>(), st, (const bf16_t*)Q, (const bf16_t*)K, \
-                     (const bf16_t*)VT, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, Lp, scale, lay, valign, (const int*)nullptr)
-  if (head_dim == 64 && !causal) FWD(64, false);
-  else if (head_dim == 64 && causal) FWD(64, true);
-  else if (head_dim == 128 && causal) FWD(128, true);
-  else if (head_dim == 128 && !causal) FWD(128, false);
-  else return TA_ERR_ARG;
-#undef FWD
+  with_const<64, 128>(head_dim, [&](auto hd_c) {
+    with_bool(causal != 0, [&](auto causal_c) {
+      constexpr int HD = decltype(hd_c)::value;
+      TA_LAUNCH((attn_fwd_kernel<HD, decltype(causal_c)::value, (HD == 64 ? 2 : 1)>), grid, blk, fwd_lds<HD>(), st, (const bf16_t*)Q,
+                (const bf16_t*)K, (const bf16_t*)VT, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, Lp, scale, lay, valign, (const int*)nullptr);
+    });
+  });
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
@@ -1419,40 +1223,19 @@ static int attention_bwd_launch(const void* Q, const void* K, const void* V, con
   // the fused epilogue's variant: with q/k-norm and RoPE (Qwen3) unless the caller passed NULL norm weights / NULL tables
   const bool norm = !F.qkv0 || F.qn_w, rope = !F.qkv0 || F.cosT;
   if (!causal && !(norm && rope)) return TA_ERR_ARG;               // the other variants exist for the causal (LM) form only
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<HD, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv);
-    attr_done = true;
-  }
   const int n_dq = grouped_grid((Hq / Hkv) * ta_cdiv(L, 64), B * Hkv), n_dkv = grouped_grid(ta_cdiv(L, 64), B * Hkv);
   dim3 grid(n_dq + n_dkv), blk(256);
   // One launch for both halves: the heavier dK / dV blocks first, the dQ blocks fill the CUs while they drain.  (Measured alternatives,
   // removed in round 5: two launches -- +0.47 ms per step, r02; the dK/dV and dQ workgroups of one (clip, kv head) interleaved on
   // one XCD -- 45.42 vs 45.29 ms per step: the heavier blocks first balance the tail better than the shared L2 lines help.)
-  const bf16_t* nul = nullptr;
-#define BWD(...)                                                                                                                    \
-  TA_LAUNCH((attn_bwd_kernel<HD, __VA_ARGS__>), grid, blk, lds_kv, st, (const bf16_t*)Q, nul, (const bf16_t*)K, nul, (const bf16_t*)V, \
-            (const bf16_t*)dO, dO_stride, nul, LSE, Delta, kmask, (bf16_t*)dQ, (bf16_t*)dK, (bf16_t*)dV, B, Hq, Hkv, L, Lp, scale, n_dkv, F, seg)
-  if (seg) {                                         // packed rows: the same four epilogue variants, segment-aware
-    if (norm && rope) BWD(true, true, true, true);
-    else if (norm) BWD(true, true, false, true);
-    else if (rope) BWD(true, false, true, true);
-    else BWD(true, false, false, true);
-  }
-  else if (!causal) BWD(false);
-  else if (norm && rope) BWD(true);
-  else if (norm) BWD(true, true, false);
-  else if (rope) BWD(true, false, true);
-  else BWD(true, false, false);
-#undef BWD
+  auto launch = [&](auto causal_c, auto norm_c, auto rope_c, auto seg_c) {
+    launch_big_lds<attn_bwd_kernel<HD, decltype(causal_c)::value, decltype(norm_c)::value, decltype(rope_c)::value, decltype(seg_c)::value>>(
+        grid, blk, lds_kv, st, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)dO, dO_stride, LSE, Delta,
+        kmask, (bf16_t*)dQ, (bf16_t*)dK, (bf16_t*)dV, B, Hq, Hkv, L, Lp, scale, n_dkv, F, seg);
+  };
+  // non-causal: the one variant admitted above; causal: the four epilogue variants, plain or segment-aware (packed rows)
+  if (!causal) launch(std::false_type{}, std::true_type{}, std::true_type{}, std::false_type{});
+  else with_bool(norm, [&](auto n) { with_bool(rope, [&](auto r) { with_bool(seg != nullptr, [&](auto s) { launch(std::true_type{}, n, r, s); }); }); });
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
@@ -1470,36 +1253,15 @@ static int attention_fwd_qkv_launch(const void* qkv0, const float* qn_w, const f
   if (norm && (!rq || !rk)) return TA_ERR_ARG;
   const int grp = Hq / Hkv;
   if (L > 192 || grp * ((L + 31) / 32) > 12) return TA_ERR_ARG;
-  constexpr int MAXT = 3, QS = 2, NW = 6;
+  constexpr int MAXT = 3, QS = 2, NW = 6;              // 6 waves x 2 passes x 32 queries = 384 query rows per workgroup
   const size_t lds = 2 * MAXT * RowTile<128>::BYTES + MAXT * 64 * 4;
-  static bool attr = false;
-#define FQ_ATTR(...) (void)hipFuncSetAttribute((const void*)attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-  if (!attr) {
-    FQ_ATTR(false); FQ_ATTR(true);
-    FQ_ATTR(false, true, false); FQ_ATTR(true, true, false); FQ_ATTR(false, false, true); FQ_ATTR(true, false, true);
-    FQ_ATTR(false, false, false); FQ_ATTR(true, false, false);
-    FQ_ATTR(false, true, true, true); FQ_ATTR(true, true, true, true);
-    FQ_ATTR(false, true, false, true); FQ_ATTR(true, true, false, true); FQ_ATTR(false, false, true, true); FQ_ATTR(true, false, true, true);
-    FQ_ATTR(false, false, false, true); FQ_ATTR(true, false, false, true);
-    attr = true;
-  }
-#undef FQ_ATTR
-#define FQ(...)                                                                                                                       \
-  TA_LAUNCH((attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, __VA_ARGS__>), dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)qkv0, qn_w, kn_w, \
-            cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk, (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps, seg)
-  // groups of two (Qwen3 16 / 8): both heads of the group on the same 16 rows per wave (one fetch of the rows' cos / sin entries)
-  const bool pair = grp == 2;
-  if (seg) {                                         // packed rows: the same eight variants, segment-aware
-    if (norm && rope) { if (pair) FQ(true, true, true, true); else FQ(false, true, true, true); }
-    else if (norm) { if (pair) FQ(true, true, false, true); else FQ(false, true, false, true); }
-    else if (rope) { if (pair) FQ(true, false, true, true); else FQ(false, false, true, true); }
-    else { if (pair) FQ(true, false, false, true); else FQ(false, false, false, true); }
-  }
-  else if (norm && rope) { if (pair) FQ(true); else FQ(false); }
-  else if (norm) { if (pair) FQ(true, true, false); else FQ(false, true, false); }
-  else if (rope) { if (pair) FQ(true, false, true); else FQ(false, false, true); }
-  else { if (pair) FQ(true, false, false); else FQ(false, false, false); }
-#undef FQ
+  // PAIR for groups of two (Qwen3 16 / 8): both heads of the group on the same 16 rows per wave (one fetch of the rows' cos / sin
+  // entries); NORM x ROPE per layer; SEG for packed rows.  All 16 combinations exist.
+  with_bool(grp == 2, [&](auto pair_c) { with_bool(norm, [&](auto norm_c) { with_bool(rope, [&](auto rope_c) { with_bool(seg != nullptr, [&](auto seg_c) {
+    launch_big_lds<attn_fwd_gqa_qkv_kernel<128, MAXT, QS, NW, decltype(pair_c)::value, decltype(norm_c)::value, decltype(rope_c)::value, decltype(seg_c)::value>>(
+        dim3(B * Hkv), dim3(NW * 64), lds, st, (const bf16_t*)qkv0, qn_w, kn_w, cosT, sinT, pos, (bf16_t*)Q, (bf16_t*)K, (bf16_t*)V, rq, rk,
+        (bf16_t*)O, LSE, kmask, B, Hq, Hkv, L, scale, eps, seg);
+  }); }); }); });
   TA_CHECK_LAUNCH();
   return TA_OK;
 }

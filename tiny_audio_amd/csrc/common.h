@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef uint16_t bf16_t;                                   // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;  // MFMA A/B fragment (4 VGPRs)
@@ -72,3 +73,14 @@ __device__ __forceinline__ float gelu_erf_fast(float x) {
 }
 
 static inline int ta_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// A run-time value -> a compile-time one: f(std::integral_constant<int, V>) for the V among Vs that equals v (no call if none does);
+// with_bool: f(std::true_type) or f(std::false_type).  Host dispatch over template arguments is nested lambdas over these.
+template <int... Vs, typename F>
+static void with_const(int v, F&& f) {
+  ((v == Vs ? (void)f(std::integral_constant<int, Vs>{}) : (void)0), ...);
+}
+template <typename F>
+static void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{}); else f(std::false_type{});
+}

@@ -487,11 +487,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_bf16x8_kernel(const bf16_t* _
 }
 
 // ----------------------------------------------------------------------------- C-ABI
-// A run-time value -> a compile-time one: f(std::integral_constant<int, V>) for the V among Vs that equals v (no call if none does)
-template <int... Vs, typename F>
-static void with_const(int v, F&& f) {
-  ((v == Vs ? (void)f(std::integral_constant<int, Vs>{}) : (void)0), ...);
-}
+// (with_const: common.h)
 // H -> NCH = H / 256, the 8-column chunks per lane of a half-wave kernel
 template <typename F> static void with_nch(int H, F&& f) { with_const<1, 2, 3, 4, 5, 6, 7, 8>(H / 256, f); }
 // H -> MAXV, the float4 per lane a wave-per-row kernel holds
