@@ -69,7 +69,7 @@ if only in ("all", "gemm"):
         shapes = [s_ for s_ in shapes if sys.argv[sys.argv.index("--match") + 1] in s_[0]]
     for name, M, N, K, obf, act, hasres in shapes:
       for var in variants:
-        os.environ["TA355_GEMM_VARIANT"] = var                    # the one tile knob the library has (0-5, 10, 12; "" = automatic)
+        os.environ["TA355_GEMM_VARIANT"] = var                    # the one tile knob the library has (0, 3, 4, 5, 10, 12; "" or any other number = automatic)
         name_v = name + (":v" + var if var else "")
         A = (torch.randn(M, K, device=DEV) * 1.0).to(BF16)
         W = (torch.randn(N, K, device=DEV) / K ** 0.5).to(BF16)

@@ -18,8 +18,8 @@ BF16, F32 = torch.bfloat16, torch.float32
 
 
 def _force_variant(monkeypatch, variant):
-    """TA355_GEMM_VARIANT for the launches that follow (0-5, 10, 12: every tile variant the library carries; the experiment-only
-    variants 6-9 / 11 of rounds 2-5 left it in round 6)."""
+    """TA355_GEMM_VARIANT for the launches that follow (0, 3, 4, 5, 10, 12: every tile variant the library carries; any other
+    number -- the plain 256-row tiles 1 / 2 and the experiment-only variants 6-9 / 11 of earlier rounds -- is the model's choice)."""
     monkeypatch.setenv("TA355_GEMM_VARIANT", variant)
 
 
@@ -88,7 +88,7 @@ def test_gemm_gelu_chord_table(variant, monkeypatch):
 
 
 @pytest.mark.parametrize("M,N,K", [(200, 64, 256), (1000, 1024, 1024), (6144, 4096, 1024), (4100, 1024, 3072)])
-@pytest.mark.parametrize("variant", [None, "0", "1", "3", "4", "10", "12"])
+@pytest.mark.parametrize("variant", [None, "0", "3", "4", "10", "12"])
 def test_gemm_k_extension(M, N, K, variant, monkeypatch):
     """C = A W^T + A2 W2^T in one launch (one extra 64-wide K tile: the fused LoRA update), every tile variant."""
     if variant is not None:
@@ -102,6 +102,43 @@ def test_gemm_k_extension(M, N, K, variant, monkeypatch):
     assert relerr(ops.gemm_nt(A, W, out_dtype=F32, residual=res, k_ext=(A2, W2)), ref + res) < 2e-3
     # one-shot: the next call is a plain GEMM again
     assert relerr(ops.gemm_nt(A, W, out_dtype=F32), A.float() @ W.float().T) < 2e-3
+
+
+def _gemm_with_logged_variant(A, W):
+    """(C, tile variant the launch log records) of one plain bf16 GEMM under the current TA355_GEMM_VARIANT."""
+    import ctypes as C
+    from tiny_audio_amd import _lib
+    L = _lib.lib()
+    ops.sync_gemm_knobs()
+    L.ta_profile_gemm(2)
+    try:
+        out = ops.gemm_nt(A, W, out_dtype=BF16)
+        torch.cuda.synchronize()
+        n = L.ta_profile_gemm_log(None, 0)
+        buf = (C.c_long * (n * 24))()
+        L.ta_profile_gemm_log(C.cast(buf, C.c_void_p), n)
+    finally:
+        L.ta_profile_gemm(0)
+    assert n == 1, n
+    return out, buf[20]                                   # field 20 of a log row: the tile variant as launched
+
+
+_UNFORCED = {}
+
+
+@pytest.mark.parametrize("forced", ["1", "2", "7", "11", "13"])
+def test_gemm_forced_variant_the_library_does_not_carry_is_the_models_choice(forced, monkeypatch):
+    """TA355_GEMM_VARIANT with a number that has no row in the variant table (the removed plain 256-row tiles 1 / 2, the
+    experiment-only 7 / 11, anything above 12) launches what the model chooses: the same logged variant, the same bits."""
+    M, N, K = 300, 256, 128
+    A, W = rnd(M, K, seed=1, dtype=BF16), rnd(N, K, seed=2, scale=1 / math.sqrt(K), dtype=BF16)
+    if not _UNFORCED:
+        monkeypatch.delenv("TA355_GEMM_VARIANT", raising=False)
+        _UNFORCED["out"], _UNFORCED["variant"] = _gemm_with_logged_variant(A, W)
+    _force_variant(monkeypatch, forced)
+    out, variant = _gemm_with_logged_variant(A, W)
+    assert variant == _UNFORCED["variant"], (variant, _UNFORCED["variant"])
+    assert torch.equal(out, _UNFORCED["out"])
 
 
 @pytest.mark.parametrize("splits", [2, 5, 16])

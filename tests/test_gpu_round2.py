@@ -33,8 +33,8 @@ DEV = "cuda"
 
 
 def _force_variant(monkeypatch, variant):
-    """TA355_GEMM_VARIANT for the launches that follow (0-5, 10, 12: every tile variant the library carries; the experiment-only
-    variants 6-9 / 11 of rounds 2-5 left it in round 6)."""
+    """TA355_GEMM_VARIANT for the launches that follow (0, 3, 4, 5, 10, 12: every tile variant the library carries; any other
+    number -- the plain 256-row tiles 1 / 2 and the experiment-only variants 6-9 / 11 of earlier rounds -- is the model's choice)."""
     monkeypatch.setenv("TA355_GEMM_VARIANT", variant)
 
 

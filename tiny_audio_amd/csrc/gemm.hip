@@ -32,6 +32,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int g = lane >> 4, l15 = lane & 15;
 
+  // This kernel keeps its own copy of the tile walk (tile_ctx, gemm_common.h, is what the other three call; the group height here
+  // defaults to 8).  With tile_ctx it had 1-2 VGPRs fewer and the same bits, and every launch of the step on it measured
+  // 0.5 - 1.4 % slower (17.63 against 17.36 us for M = 4000, N = K = 1024 on 96-row tiles; profiles/gemm_refactor.md).
   // ---- XCD-aware, grouped tile order (block b runs on XCD b % 8: give each XCD a contiguous chunk)
   const int nwg = gridDim.x;
   int bid = blockIdx.x;
@@ -69,25 +72,16 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = i * 32 + lr;
-    if (i < MI) {
-      int gm = rbase + min(m0 + r, Mact - 1);
-      if (p.a_idx) gm = p.a_idx[gm];
-      const long aoff = p.a_plain ? (long)gm * p.lda : (long)(gm / p.a_rpb) * p.a_bs + (long)(gm % p.a_rpb) * p.lda;
-      a_src[i] = (const char*)(p.A + aoff + (long)kt_begin * BK + clog * 8);
-    }
-    const int gn = min(n0 + r, p.N - 1);
-    w_src[i] = p.w_blocked ? (const char*)(Wp + (((long)(gn >> 6) * nkt + kt_begin) << 12) + ((gn & 63) << 6) + clog * 8)
-                           : (const char*)(Wp + (long)gn * p.K + (long)kt_begin * BK + clog * 8);
+    if (i < MI) a_src[i] = a_chunk_src(p, rbase + min(m0 + r, Mact - 1), kt_begin, clog);
+    w_src[i] = w_chunk_src(p, Wp, min(n0 + r, p.N - 1), nkt, kt_begin, clog);
   }
   const int w_step = p.w_blocked ? 8192 : BK * 2;      // bytes to the next K tile of the same rows
   char* lds_w = smem + wave * 1024;   // + buf*2*TILE + (A:0 | W:TILE) + i*4096, lane*16 added by the DMA
 
   // ---- per-lane fragment read offsets (bytes) inside a tile
-  const int swz = l15 >> 1;
   const int a_rd = (wm * WR + l15) * 128;
   const int b_rd = (wn * 64 + l15) * 128;
-  const int koff0 = ((0 + g) ^ swz) << 4;
-  const int koff1 = ((4 + g) ^ swz) << 4;
+  const FragOff ko2 = frag_koff(l15, g);
 
   f32x4 acc[MI][4];
   const bool res_init = residual_is_start<ACT, OUT_BF16, HAS_RES>(p);
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
     const char* Bs = As + TILE_BYTES;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const int ko = kk ? koff1 : koff0;
+      const int ko = kk ? ko2.k1 : ko2.k0;
       bf16x8 af[MI], bfr[4];
 #pragma unroll
       for (int i = 0; i < MI; ++i) af[i] = *(const bf16x8*)(As + a_rd + i * 2048 + ko);
@@ -145,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
   // ---- epilogue: lane owns row m = .. + l15, columns n .. n+3 (n = .. + g*4)
   char* Cb = (char*)p.C;
   if (p.splits > 1) Cb += (long)z * p.slab_stride * 4;
-  const bool wide = epilogue_wide_ok(p);
+  const bool wide = p.wide != 0;
   const float2* lut = stage_gelu_lut<ACT, 256>(smem, p, tid, false);       // the K loop ended with a barrier
   if (res_init) epilogue_tile<MI, 4, ACT, OUT_BF16, false>(acc, p, Cb, m0 + wm * WR + l15, Mact, rbase, n0 + wn * 64, g, wide, biasp, lut);
   else epilogue_tile<MI, 4, ACT, OUT_BF16, HAS_RES>(acc, p, Cb, m0 + wm * WR + l15, Mact, rbase, n0 + wn * 64, g, wide, biasp, lut);
@@ -154,12 +148,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
 // ============================================================================ v2: 256-row tiles, 8 waves, 1 WG / CU
 // The 128x128 kernel above is bound by the per-CU L2 -> LDS DMA rate: it must stage 32 KB per 2.1 MFLOP tile-step
 // (profiles/r01_a_pmc_summary.md: L2 request volume ~48x the algorithmic bytes).  A 256 x BN2 tile halves
-// (BN2 = 256) or cuts by a quarter (BN2 = 128) the bytes staged per flop.  8 waves as 2 (M) x 4 (N): each wave owns
-// 128 x BN2/4 outputs = 8 x NT accumulator fragments.  Same DMA + source-side swizzle + double buffer as v1; the DMA
-// issue for the next K-tile is interleaved in four places between MFMA groups instead of one burst, because with a
-// single workgroup per CU nothing else hides a burst.
+// (BN2 = 256) the bytes staged per flop.  8 waves as 2 (M) x 4 (N): each wave owns
+// 128 x BN2/4 outputs = 8 x NT accumulator fragments.  Same DMA + source-side swizzle + double buffer as v1.
+// (Rounds 1-5 also had a plain double-buffered main loop on this tile -- variants 1, 256x256, and 2, 256x128, with the next
+// K tile's DMA interleaved in four places between MFMA groups: 0.9 and 0.5 of the 128x128 kernel's rate per unit area against
+// 1.40 for the schedule below, so the launch-time model could choose neither; DESIGN.md "dead ends".)
 //
-// PP ("ping-pong"): the two wave groups (wm = 0 / 1; wave w and w+4 share a SIMD) run ONE barrier interval apart,
+// Ping-pong: the two wave groups (wm = 0 / 1; wave w and w+4 share a SIMD) run ONE barrier interval apart,
 // alternating a load interval L(t,s) = {ds_read the 12 fragments of k-step s (+ issue the next tile's DMA when
 // s = 0); wait for them} with a compute interval C(t,s) = {32 MFMAs}.  In every interval one group feeds the
 // matrix pipe while its SIMD partner loads, so the pipe never waits on LDS latency, DMA issue or the barrier:
@@ -169,7 +164,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(GemmArgs p) {
 // Hazards: every wave drains its own DMA (vmcnt 0) at the end of L(t,1), i.e. before barrier 4t+3 (group 0) /
 // 4t+4 (group 1), and the first read of tile t+1 is after barrier 4t+4; the last reads of tile t-1 (group 1's
 // L(t-1,1)) retire (lgkmcnt 0) before barrier 4t, and the first DMA into that buffer is issued after it.
-template <int BN2, int ACT, bool OUT_BF16, bool HAS_RES, bool PP, bool KEXT = false>
+// The K step itself is pingpong_ktile (gemm_common.h), shared with the persistent form below.
+template <int BN2, int ACT, bool OUT_BF16, bool HAS_RES, bool KEXT = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
   constexpr int BM2 = 256;
   constexpr int NT = BN2 / 64;                 // n-fragments per wave
@@ -180,69 +176,36 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
   const int wm = wave >> 2, wn = wave & 3;
   const int g = lane >> 4, l15 = lane & 15;
 
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
-  const int tiles = p.tiles_m * p.tiles_n;
-  const int z = bid / tiles;
-  int t = bid - z * tiles;
-  const int GROUP_M = p.group_m > 0 ? p.group_m : 4;
-  const int width = GROUP_M * p.tiles_n;
-  const int group = t / width;
-  const int first_m = group * GROUP_M;
-  const int gsize = min(p.tiles_m - first_m, GROUP_M);
-  int pm = first_m + (t % width) % gsize;
-  const int pn = (t % width) / gsize;
-  const int* segp; const bf16_t* Wp; const float* biasp; const int* krp;
-  if (!resolve_group<BM2>(p, pm, z, segp, Wp, biasp, krp)) return;
-  const int m0 = pm * BM2, n0 = pn * BN2;
-
+  const TileCtx c = block_tile<BM2, BN2>(p);
+  if (!c.ok) return;
+  const int m0 = c.m0, n0 = c.n0, z = c.z, Mact = c.Mact, rbase = c.rbase;
+  const bf16_t* Wp = c.Wp; const float* biasp = c.biasp;
   const int nkt = p.K / BK;
-  int kt_begin = 0, kt_end = nkt;                  // 32-bit, and only when split: two 64-bit quotients cost ~2 k cycles per workgroup
-  if (p.splits > 1) { kt_begin = (nkt * z) / p.splits; kt_end = (nkt * (z + 1)) / p.splits; }
-  if (krp) { kt_begin = krp[0]; kt_end = krp[1]; }
-  if (KEXT) kt_end = nkt + p.K2 / BK;
-  int Mact = p.M, rbase = 0;
-  if (segp) { rbase = segp[0]; Mact = segp[1]; if (m0 >= Mact) return; }
+  const int kt_begin = c.kb;
+  const int kt_end = KEXT ? nkt + p.K2 / BK : c.ke;
 
   const int lr = tid >> 3;                                    // 0..63
   const int clog = (tid & 7) ^ ((lr >> 1) & 7);
   const char* a_src[NA];
   const char* w_src[NB];
 #pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    int gm = rbase + min(m0 + i * 64 + lr, Mact - 1);
-    if (p.a_idx) gm = p.a_idx[gm];
-    const long aoff = p.a_plain ? (long)gm * p.lda : (long)(gm / p.a_rpb) * p.a_bs + (long)(gm % p.a_rpb) * p.lda;
-    a_src[i] = (const char*)(p.A + aoff + (long)kt_begin * BK + clog * 8);
-  }
+  for (int i = 0; i < NA; ++i) a_src[i] = a_chunk_src(p, rbase + min(m0 + i * 64 + lr, Mact - 1), kt_begin, clog);
 #pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int gn = min(n0 + i * 64 + lr, p.N - 1);
-    w_src[i] = p.w_blocked ? (const char*)(Wp + (((long)(gn >> 6) * nkt + kt_begin) << 12) + ((gn & 63) << 6) + clog * 8)
-                           : (const char*)(Wp + (long)gn * p.K + (long)kt_begin * BK + clog * 8);
-  }
+  for (int i = 0; i < NB; ++i) w_src[i] = w_chunk_src(p, Wp, min(n0 + i * 64 + lr, p.N - 1), nkt, kt_begin, clog);
   const int w_step = p.w_blocked ? 8192 : BK * 2;
   char* lds_w = smem + wave * 1024;
 
-  const int swz = l15 >> 1;
   const int a_rd = (wm * 128 + l15) * 128;
   const int b_rd = A_BYTES + (wn * (BN2 / 4) + l15) * 128;
-  const int koff0 = ((0 + g) ^ swz) << 4;
-  const int koff1 = ((4 + g) ^ swz) << 4;
+  const FragOff ko2 = frag_koff(l15, g);
 
   f32x4 acc[8][NT];
   const bool res_init = residual_is_start<ACT, OUT_BF16, HAS_RES>(p);
   if (res_init) residual_start<8, NT>(acc, p, m0 + wm * 128 + l15, Mact, rbase, n0 + wn * (BN2 / 4), g);
   else zero_acc<8, NT>(acc);
 
-  auto dma_a = [&](char* base, int i) { glds16(a_src[i], base + i * 8192); a_src[i] += BK * 2; };
-  auto dma_w = [&](char* base, int i) { glds16(w_src[i], base + A_BYTES + i * 8192); w_src[i] += w_step; };
-  auto ext_switch = [&](int tile) {                 // call before staging K-tile `tile`
-    if (KEXT && tile == nkt) {
+  auto dma_tile = [&](char* base, int tile) {       // K tile `tile` of both operands into the stage at `base`
+    if (KEXT && tile == nkt) {                      // switch both operands to the extension
 #pragma unroll
       for (int i = 0; i < NA; ++i)
         a_src[i] = (const char*)(p.A2 + (long)(rbase + min(m0 + i * 64 + lr, Mact - 1)) * p.lda2 + clog * 8);
@@ -250,98 +213,27 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v2(GemmArgs p) {
       for (int i = 0; i < NB; ++i)
         w_src[i] = (const char*)(p.W2 + (long)min(n0 + i * 64 + lr, p.N - 1) * p.K2 + clog * 8);
     }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) { glds16(a_src[i], base + i * 8192); a_src[i] += BK * 2; }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) { glds16(w_src[i], base + A_BYTES + i * 8192); w_src[i] += w_step; }
   };
 
-  if (kt_begin < kt_end) {
-    ext_switch(kt_begin);
-#pragma unroll
-    for (int i = 0; i < NA; ++i) dma_a(lds_w, i);
-#pragma unroll
-    for (int i = 0; i < NB; ++i) dma_w(lds_w, i);
-  }
+  if (kt_begin < kt_end) dma_tile(lds_w, kt_begin);
   __syncthreads();
-  if constexpr (PP) {
-    const int lag = __builtin_amdgcn_readfirstlane(wm);     // SGPR: scalar branches around the extra barriers
-    if (lag) __builtin_amdgcn_s_barrier();
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-      const int cur = (kt - kt_begin) & 1;
-      const bool more = kt + 1 < kt_end;
-      const char* S = smem + cur * STAGE;
-      char* nxt = lds_w + (cur ^ 1) * STAGE;
-      bf16x8 af[8], bfr[NT];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ko = kk ? koff1 : koff0;
-        // ---- L(t, kk)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) bfr[j] = *(const bf16x8*)(S + b_rd + j * 2048 + ko);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) af[i] = *(const bf16x8*)(S + a_rd + i * 2048 + ko);
-        if (kk == 0) {
-          if (more) {
-            ext_switch(kt + 1);
-#pragma unroll
-            for (int i = 0; i < NA; ++i) dma_a(nxt, i);
-#pragma unroll
-            for (int i = 0; i < NB; ++i) dma_w(nxt, i);
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- C(t, kk)
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (!lag) __builtin_amdgcn_s_barrier();
-  } else {
+  const int lag = __builtin_amdgcn_readfirstlane(wm);     // SGPR: scalar branches around the extra barriers
+  if (lag) __builtin_amdgcn_s_barrier();
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int cur = (kt - kt_begin) & 1;
     const bool more = kt + 1 < kt_end;
-    const char* S = smem + cur * STAGE;
     char* nxt = lds_w + (cur ^ 1) * STAGE;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int ko = kk ? koff1 : koff0;
-      bf16x8 af[8], bfr[NT];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) bfr[j] = *(const bf16x8*)(S + b_rd + j * 2048 + ko);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) af[i] = *(const bf16x8*)(S + a_rd + i * 2048 + ko);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (more) {   // quarter of the next tile's DMA ahead of each 4-row MFMA group
-          if (kk == 0 && h == 0) ext_switch(kt + 1);
-          if (kk == 0) { dma_a(nxt, 2 * h); dma_a(nxt, 2 * h + 1); }
-          else if (NB == 4) { dma_w(nxt, 2 * h); dma_w(nxt, 2 * h + 1); }
-          else { dma_w(nxt, h); }
-        }
-#pragma unroll
-        for (int i = 4 * h; i < 4 * h + 4; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
+    pingpong_ktile<8, NT>(smem + cur * STAGE, a_rd, b_rd, ko2, acc, [&] { if (more) dma_tile(nxt, kt + 1); });
   }
-  }
+  if (!lag) __builtin_amdgcn_s_barrier();
 
   char* Cb = (char*)p.C;
   if (p.splits > 1) Cb += (long)z * p.slab_stride * 4;
-  const bool wide = epilogue_wide_ok(p);
+  const bool wide = p.wide != 0;
   const float2* lut = stage_gelu_lut<ACT, 512>(smem, p, tid, false);       // both wave groups are past their last LDS read
   if (res_init) epilogue_tile<8, NT, ACT, OUT_BF16, false>(acc, p, Cb, m0 + wm * 128 + l15, Mact, rbase, n0 + wn * (BN2 / 4), g, wide, biasp, lut);
   else epilogue_tile<8, NT, ACT, OUT_BF16, HAS_RES>(acc, p, Cb, m0 + wm * 128 + l15, Mact, rbase, n0 + wn * (BN2 / 4), g, wide, biasp, lut);
@@ -395,11 +287,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
   const int a_step = a_blk ? 8192 : BK * 2;
   // wave-uniform LDS byte address of this wave's 1-KB DMA window in stage 0
   const unsigned lds_w = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem + wave * 1024);
-  const int swz = l15 >> 1;
   const int a_rd = (wm * (BM2 / 2) + l15) * 128;
   const int b_rd = A_BYTES + (wn * (BN2 / 4) + l15) * 128;
-  const int koff0 = ((0 + g) ^ swz) << 4;
-  const int koff1 = ((4 + g) ^ swz) << 4;
+  const FragOff ko2 = frag_koff(l15, g);
   const int lag = __builtin_amdgcn_readfirstlane(wm);
   // The thread index, re-derived where the code around the main loop needs it (wave number from an SGPR + v_mbcnt): index
   // arithmetic that started from threadIdx.x was hoisted out of the tile loop and carried, spilled, across the main loop.
@@ -430,13 +320,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
     } else if (p.a_plain) {
 #pragma unroll
       for (int i = 0; i < NA; ++i)
-        a_off[i] = (unsigned)(((long)(min(c.m0 + i * 64 + lr, c.Mact - 1) - c.m0) * p.lda + clog * 8) * 2);
+        a_off[i] = rel_off(min(c.m0 + i * 64 + lr, c.Mact - 1), c.m0, p.lda, clog);
       a_base = (const char*)(p.A + (long)(c.rbase + c.m0) * p.lda) + (long)c.kb * (BK * 2);
     } else {
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
-        const int gm = c.rbase + min(c.m0 + i * 64 + lr, c.Mact - 1);
-        a_off[i] = (unsigned)(((long)(gm / p.a_rpb) * p.a_bs + (long)(gm % p.a_rpb) * p.lda + clog * 8) * 2);
+        a_off[i] = (unsigned)((a_row_off(p, c.rbase + min(c.m0 + i * 64 + lr, c.Mact - 1)) + clog * 8) * 2);
       }
       a_base = (const char*)p.A + (long)c.kb * (BK * 2);
     }
@@ -444,7 +333,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
     for (int i = 0; i < NB; ++i) {
       const int gn = min(c.n0 + i * 64 + lr, p.N - 1);
       w_off[i] = p.w_blocked ? (unsigned)(((((long)((gn >> 6) - (c.n0 >> 6)) * nkt) << 12) + ((gn & 63) << 6) + clog * 8) * 2)
-                             : (unsigned)(((long)(gn - c.n0) * p.K + clog * 8) * 2);
+                             : rel_off(gn, c.n0, p.K, clog);
     }
     w_base = (const char*)c.Wp + (p.w_blocked ? (((long)(c.n0 >> 6) * nkt) << 13) + (long)c.kb * 8192 : ((long)c.n0 * p.K + (long)c.kb * BK) * 2);
     if (c.kb < c.ke) dma_tile(lds_w + st * STAGE);
@@ -515,40 +404,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
     for (int kt = cur.kb; kt < cur.ke; ++kt) {
       const int cs = ((kt - cur.kb) & 1) ^ ph;
       const bool more = kt + 1 < cur.ke;
-      const char* S = smem + cs * STAGE;
       const unsigned nxt = lds_w + (cs ^ 1) * STAGE;
-      bf16x8 af[MI], bfr[NT];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ko = kk ? koff1 : koff0;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) bfr[j] = *(const bf16x8*)(S + b_rd + j * 2048 + ko);
-#pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = *(const bf16x8*)(S + a_rd + i * 2048 + ko);
-        if (kk == 0) {
-          if (more) {
-            dma_tile(nxt);
-          } else {
-            dma_epi(cur, nxt);
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      // the issue step: the next K tile, or -- behind the last one -- the epilogue's constants
+      pingpong_ktile<MI, NT>(smem + cs * STAGE, a_rd, b_rd, ko2, acc, [&] { if (more) dma_tile(nxt); else dma_epi(cur, nxt); });
     }
     if (!lag) __builtin_amdgcn_s_barrier();                      // both groups are past their last LDS read: both stages are free
 
@@ -572,7 +430,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel_v4(GemmArgs p) {
     const int e_l15 = te & 15, e_g = (te >> 4) & 3, e_wn = (te >> 6) & 3, e_wm = te >> 8;
     char* Cb = (char*)p.C;
     if (p.splits > 1) Cb += (long)cur.z * p.slab_stride * 4;
-    const bool wide = epilogue_wide_ok(p);
+    const bool wide = p.wide != 0;
     const int erow0 = e_wm * (BM2 / 2) + e_l15;
     // full tiles: row-merged stores
     const bool full = OUT_BF16 && wide && p.c_plain && (!HAS_RES || res_init) && cur.m0 + BM2 <= cur.Mact && cur.n0 + BN2 <= p.N;
@@ -638,32 +496,13 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
   const int wm = wave >> 1, wn = wave & 1;
   const int g = lane >> 4, l15 = lane & 15;
 
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, within = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + within;
-  }
-  const int tiles = p.tiles_m * p.tiles_n;
-  const int z = bid / tiles;
-  const int t = bid - z * tiles;
-  const int GROUP_M = p.group_m > 0 ? p.group_m : 4;
-  const int width = GROUP_M * p.tiles_n;
-  const int group = t / width;
-  const int first_m = group * GROUP_M;
-  const int gsize = min(p.tiles_m - first_m, GROUP_M);
-  int pm = first_m + (t % width) % gsize;
-  const int pn = (t % width) / gsize;
-  const int* segp; const bf16_t* Wp; const float* biasp; const int* krp;
-  if (!resolve_group<BM5>(p, pm, z, segp, Wp, biasp, krp)) return;
-  const int m0 = pm * BM5, n0 = pn * BN5;
+  const TileCtx c = block_tile<BM5, BN5>(p);
+  if (!c.ok) return;
+  const int m0 = c.m0, n0 = c.n0, z = c.z, Mact = c.Mact, rbase = c.rbase;
+  const bf16_t* Wp = c.Wp; const float* biasp = c.biasp;
   const int nkt = p.K / BK;
-  int kt_begin = 0, kt_end = nkt;
-  if (p.splits > 1) { kt_begin = (nkt * z) / p.splits; kt_end = (nkt * (z + 1)) / p.splits; }
-  if (krp) { kt_begin = krp[0]; kt_end = krp[1]; }
-  if (KEXT) kt_end = nkt + p.K2 / BK;              // host guarantees splits == 1, no krange
-  int Mact = p.M, rbase = 0;
-  if (segp) { rbase = segp[0]; Mact = segp[1]; if (m0 >= Mact) return; }
+  const int kt_begin = c.kb;
+  const int kt_end = KEXT ? nkt + p.K2 / BK : c.ke;   // host guarantees splits == 1, no krange
 
   // ---- DMA sources: pass q stages rows [32 q, 32 q + 32) of A (q < 6) / of W (q - 6 < 4); a thread owns one 16-B chunk per pass
   const int lr = tid >> 3;
@@ -673,27 +512,22 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
   if (p.a_plain) {
 #pragma unroll
     for (int q = 0; q < 6; ++q)
-      a_off[q] = (unsigned)(((long)(min(m0 + q * 32 + lr, Mact - 1) - m0) * p.lda + clog * 8) * 2);
+      a_off[q] = rel_off(min(m0 + q * 32 + lr, Mact - 1), m0, p.lda, clog);
     a_base = (const char*)(p.A + (long)(rbase + m0) * p.lda) + (long)kt_begin * (BK * 2);
   } else {
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      const int gm = rbase + min(m0 + q * 32 + lr, Mact - 1);
-      a_off[q] = (unsigned)(((long)(gm / p.a_rpb) * p.a_bs + (long)(gm % p.a_rpb) * p.lda + clog * 8) * 2);
-    }
+    for (int q = 0; q < 6; ++q) a_off[q] = (unsigned)((a_row_off(p, rbase + min(m0 + q * 32 + lr, Mact - 1)) + clog * 8) * 2);
     a_base = (const char*)p.A + (long)kt_begin * (BK * 2);
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q)
-    w_off[q] = (unsigned)(((long)(min(n0 + q * 32 + lr, p.N - 1) - n0) * p.K + clog * 8) * 2);
+    w_off[q] = rel_off(min(n0 + q * 32 + lr, p.N - 1), n0, p.K, clog);
   w_base = (const char*)(Wp + (long)n0 * p.K) + (long)kt_begin * (BK * 2);
   const unsigned lds_w = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(__attribute__((address_space(3))) char*)smem + wave * 1024);
 
-  const int swz = l15 >> 1;
   const int a_rd = (wm * 96 + l15) * 128;
   const int b_rd = A_BYTES + (wn * 64 + l15) * 128;
-  const int koff0 = ((0 + g) ^ swz) << 4;
-  const int koff1 = ((4 + g) ^ swz) << 4;
+  const FragOff ko2 = frag_koff(l15, g);
 
   f32x4 acc[6][4];
   const bool res_init = residual_is_start<ACT, OUT_BF16, HAS_RES>(p);
@@ -712,9 +546,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
           a_base = (const char*)(p.A2 + (long)(rbase + m0) * p.lda2);
           w_base = (const char*)(p.W2 + (long)n0 * p.K2);
 #pragma unroll
-          for (int q = 0; q < 6; ++q) a_off[q] = (unsigned)(((long)(min(m0 + q * 32 + lr, Mact - 1) - m0) * p.lda2 + clog * 8) * 2);
+          for (int q = 0; q < 6; ++q) a_off[q] = rel_off(min(m0 + q * 32 + lr, Mact - 1), m0, p.lda2, clog);
 #pragma unroll
-          for (int q = 0; q < 4; ++q) w_off[q] = (unsigned)(((long)(min(n0 + q * 32 + lr, p.N - 1) - n0) * p.K2 + clog * 8) * 2);
+          for (int q = 0; q < 4; ++q) w_off[q] = rel_off(min(n0 + q * 32 + lr, p.N - 1), n0, p.K2, clog);
         } else {
           a_base += BK * 2; w_base += BK * 2;
         }
@@ -735,9 +569,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
     wait_vm_lgkm0_n<10>();                                     // group 0 landed
     __builtin_amdgcn_s_barrier();
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bf0[j] = *(const bf16x8*)(smem + b_rd + j * 2048 + koff0);
+    for (int j = 0; j < 4; ++j) bf0[j] = *(const bf16x8*)(smem + b_rd + j * 2048 + ko2.k0);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) af0[i] = *(const bf16x8*)(smem + a_rd + i * 2048 + koff0);
+    for (int i = 0; i < 6; ++i) af0[i] = *(const bf16x8*)(smem + a_rd + i * 2048 + ko2.k0);
     int rslot = 0;                                             // slot of the K tile being computed
     // One half-step.  FIRST (k columns 0..31 of tile t): MFMAs on (ca, cb), reads of the second half of the same slot into
     // (na, nb), DMA of group t + 2 into the slot tile t - 1 left.  SECOND: waits for group t + 1 (group t + 2 may stay in flight),
@@ -747,9 +581,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
       const int nslot = rslot == NS - 1 ? 0 : rslot + 1;
       if (FIRST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       else wait_vm_lgkm0_n<10>();
-      // pass the fragments through an empty asm: the compiler's own wait for them lands HERE, not behind the reads issued below
+      // pass the fragments through an empty asm: the compiler's own wait for them lands HERE, not behind the reads issued below.
+      // The A fragment read LAST goes first, so that this is one lgkmcnt(0) whatever the compiler knows about its counters: in
+      // issue order it can become a ladder lgkmcnt(5) ... lgkmcnt(0) behind the wait above -- ten more s_waitcnt per K tile with
+      // nothing to hide them at one wave per SIMD, 55.1 against 54.2 us for K = 5120 (profiles/gemm_refactor.md)
 #pragma unroll
-      for (int i = 0; i < 6; ++i) asm volatile("" : "+v"(ca[i]));
+      for (int i = 5; i >= 0; --i) asm volatile("" : "+v"(ca[i]));
 #pragma unroll
       for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(cb[j]));
       __builtin_amdgcn_sched_barrier(0);
@@ -757,7 +594,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
         __builtin_amdgcn_s_barrier();                          // slot t + 1 is complete; slot t may be overwritten (by group t + 3, next tile)
         __builtin_amdgcn_sched_barrier(0);
       }
-      const char* S = smem + (FIRST ? rslot : nslot) * SLOT + (FIRST ? koff1 : koff0);
+      const char* S = smem + (FIRST ? rslot : nslot) * SLOT + (FIRST ? ko2.k1 : ko2.k0);
       const char* ab = uniform_ptr(a_base);
       const char* wb = uniform_ptr(w_base);
       const unsigned base = lds_w + islot * SLOT;
@@ -786,7 +623,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel_v5(GemmArgs p) {
 
   char* Cb = (char*)p.C;
   if (p.splits > 1) Cb += (long)z * p.slab_stride * 4;
-  const bool wide = epilogue_wide_ok(p);
+  const bool wide = p.wide != 0;
   const float2* lut = stage_gelu_lut<ACT, 256>(smem, p, tid, true);
   if (res_init) epilogue_tile<6, 4, ACT, OUT_BF16, false>(acc, p, Cb, m0 + wm * 96 + l15, Mact, rbase, n0 + wn * 64, g, wide, biasp, lut);
   else epilogue_tile<6, 4, ACT, OUT_BF16, HAS_RES, ((HAS_RES && !OUT_BF16) ? 3 : 2)>(acc, p, Cb, m0 + wm * 96 + l15, Mact, rbase, n0 + wn * 64, g, wide, biasp, lut);   // one wave per SIMD: registers to spare
@@ -805,13 +642,6 @@ bool g_log_on = false;
 std::vector<long> g_log;
 }  // namespace
 
-// The library carries the variants the launch-time model can choose (0-5, 10, 12).  Rounds 2-5 also had, in experiment builds,
-// the ring form (6 / 7), stamped timing builds (8 / 9), the 32x32x16 form of v5 (11) and v5's timing experiments: all removed
-// (scripts/attic/gemm_r05_with_experiments.hip.txt keeps the source, profiles/ the measurements).
-// Tile variant: 0 = 128x128 (4 waves, 2 WG/CU), 5 = 96x128 (same kernel), 1 = 256x256, 2 = 256x128 (8 waves, 1 WG/CU), 3 = 256x256 ping-pong,
-// 4 = 256x320 ping-pong (N = 1280 / 3840 / 5120 divide exactly: M = 16000 x N = 1280 is 252 tiles = ONE round of 256 CUs).
-// Model: time ~ rounds(tiles / resident slots) * tile area / relative rate; pick the cheapest.  The relative rates
-// come from scripts/gemm_bench.py on MI355X (see profiles/).  TA355_GEMM_VARIANT forces one (tests, microbenchmarks).
 #include <cstdlib>
 // The two environment knobs of the GEMM launcher, read ONCE (round 4: they were 17 getenv calls PER LAUNCH).
 // ta_gemm_reload_knobs() re-reads the environment: tests and the A/B scripts that switch a knob between launches call it
@@ -832,81 +662,114 @@ static GemmKnobs& knobs() {
 void ta_i_reload_decode_knobs();   // generate.hip: TA355_DECODE_FUSED
 extern "C" int ta_gemm_reload_knobs(void) { knobs().load(); ta_i_reload_decode_knobs(); return TA_OK; }
 
-static int pick_variant(int M, int N, int K, int splits) {
-  const int forced = knobs().variant;
-  if (forced >= 0 && forced <= 12 && !(forced >= 6 && forced <= 9) && forced != 11) return forced;
-  const double rate[6] = {1.0, TA355_RATE_256x256, TA355_RATE_256x128, TA355_RATE_256x256_PP, TA355_RATE_256x320_PP, TA355_RATE_96x128};
-  const int bm[6] = {128, 256, 256, 256, 256, 96}, bn[6] = {128, 256, 128, 256, 320, 128}, slots[6] = {512, 256, 256, 256, 256, 512};
-  int best = 0; double best_t = 1e300;
-  for (int v = 0; v < 6; ++v) {
-    const long tiles = (long)ta_cdiv(M, bm[v]) * ta_cdiv(N, bn[v]) * splits;
-    const double rounds = (double)((tiles + slots[v] - 1) / slots[v]);
-    // a round of variant v costs (tile area / rate) per slot; variants 0 and 5 run two tiles per CU concurrently
-    const double t = rounds * (double)bm[v] * bn[v] / rate[v] * ((v == 0 || v == 5) ? 2.0 : 1.0);
-    if (t < best_t) { best_t = t; best = v; }
+// ---- the tile variants.  The library carries the variants the launch-time model can choose; everything a variant number means is
+// its row here.  Rounds 1-5 also had the plain double-buffered 256x256 / 256x128 tiles (1 / 2: rates 0.9 / 0.5, never the model's
+// choice -- variant 3 has 1's tile and slots at a higher rate, and 128x128 has no more rounds than 2 at half the cost per round) and, in
+// experiment builds, the ring form (6 / 7), stamped timing builds (8 / 9), the 32x32x16 form of v5 (11) and v5's timing experiments: all
+// removed (git, scripts/attic/gemm_r05_with_experiments.hip.txt and profiles/ keep sources and measurements; DESIGN.md "dead ends").
+// Model: time ~ rounds(tiles / resident slots) * tile area / relative rate * tiles per CU; pick the cheapest (the first of equals, in
+// table order).  The relative rates come from scripts/gemm_bench.py on MI355X (see profiles/).  TA355_GEMM_VARIANT forces one
+// (tests, microbenchmarks); a number the library does not carry means the model's choice.
+enum : unsigned { V_GATHER = 1, V_FAR_A = 2, V_KEXT = 4, V_WBLOCKED = 8 };   // what a launch may need: gathered A rows, row-mapped A beyond 32-bit offsets, the K extension, blocked W
+// What the persistent kernel (v4) does not take.  Gathered A rows (their offsets are not bounded by the tile) and far row-mapped A.
+// And the K extension (LoRA): its first persistent form hoisted the extension's nine DMA offsets out of
+// the tile loop and spilled the regular ones (91.8 against 61.6 us per launch, profiles/r03_p_ab_lora.txt); with the offsets derived
+// from a fresh thread index at the switch there was no scratch and the LoRA step was the same on both kernels (45.45 ms each,
+// profiles/r03_r_ab_lora_persist_kext.txt), so v4 carries no extension.
+constexpr unsigned V_NOT_PERSISTENT = V_GATHER | V_FAR_A | V_KEXT;
+struct Variant {
+  int id, bm, bn;      // TA355_GEMM_VARIANT / launch-log number; tile rows, columns
+  int slots, per_cu;   // resident tiles on the chip; tiles a CU runs concurrently (a round costs per_cu tile areas per CU)
+  double rate;         // per-CU throughput per unit tile area relative to the 128x128 kernel (gemm_common.h); <= 0: never chosen
+  int min_k;           // the model chooses it only for K / splits >= min_k
+  bool v2;             // persistent workgroups (v4), and one workgroup per tile (v2) for a launch with one of V_NOT_PERSISTENT
+  unsigned cannot;     // what no form of the variant takes: such a launch goes to `fallback`
+  int fallback;
+};
+constexpr Variant kVariants[] = {
+    {0, 128, 128, 512, 2, 1.0, 0, false, 0, 0},                                          // 4 waves, 2 WG / CU (gemm_nt_kernel)
+    {3, 256, 256, 256, 1, TA355_RATE_256x256_PP, 0, true, 0, 3},
+    // N = 1280 / 3840 / 5120 divide exactly: M = 16000 x N = 1280 is 252 tiles = ONE round of 256 CUs
+    {4, 256, 320, 256, 1, TA355_RATE_256x320_PP, 0, true, 0, 4},
+    {5, 96, 128, 512, 2, TA355_RATE_96x128, 0, false, 0, 5},                             // the same kernel as 0
+    // one 4-wave workgroup per CU (v5): no gather, plain W only.  Only long contractions: with one workgroup per CU nothing overlaps
+    // its prologue and epilogue (K = 1280: 33 vs 28 us for 96x128)
+    {10, 192, 128, 256, 1, TA355_RATE_192x128, 2048, false, V_GATHER | V_FAR_A | V_WBLOCKED, 5},
+    // the 192-row ping-pong tile exists in the persistent form only: what that form does not take goes to the 256x256 tile.
+    // (a minimum contraction length -- two K tiles -- so that tiny-K launches stay on the small tiles)
+    {12, 192, 256, 256, 1, TA355_RATE_192x256_PP, 128, false, V_NOT_PERSISTENT, 3},
+};
+constexpr const Variant* find_variant(int id) {
+  for (const Variant& v : kVariants)
+    if (v.id == id) return &v;
+  return nullptr;
+}
+constexpr bool fallbacks_take_everything() {
+  for (const Variant& v : kVariants) {
+    const Variant* f = find_variant(v.fallback);
+    if (!f || (v.cannot && f->cannot)) return false;
   }
-  {                                                  // 10 = 192x128, one 4-wave workgroup per CU (v5)
-    const long tiles = (long)ta_cdiv(M, 192) * ta_cdiv(N, 128) * splits;
-    const double t = (double)((tiles + 255) / 256) * 192.0 * 128.0 / TA355_RATE_192x128;
-    // only long contractions: with one workgroup per CU nothing overlaps its prologue and epilogue (K = 1280: 33 vs 28 us for 96x128)
-    if (TA355_RATE_192x128 > 0.0 && K / splits >= 2048 && t < best_t) { best_t = t; best = 10; }
-  }
-  {                                                  // 12 = 192x256 ping-pong, persistent (v4 with BM2 = 192)
-    const long tiles = (long)ta_cdiv(M, 192) * ta_cdiv(N, 256) * splits;
-    const double t = (double)((tiles + 255) / 256) * 192.0 * 256.0 / TA355_RATE_192x256_PP;
-    // (the same minimum contraction length as for v5's own choice -- two K tiles -- so that tiny-K launches stay on the small tiles)
-    if (TA355_RATE_192x256_PP > 0.0 && K / splits >= 128 && t < best_t) { best_t = t; best = 12; }
+  return true;
+}
+static_assert(fallbacks_take_everything(), "a launch a variant cannot take must end at a row that takes it");
+
+static const Variant& pick_variant(int M, int N, int K, int splits) {
+  if (const Variant* forced = find_variant(knobs().variant)) return *forced;
+  const Variant* best = &kVariants[0]; double best_t = 1e300;
+  for (const Variant& v : kVariants) {
+    if (v.rate <= 0.0 || K / splits < v.min_k) continue;
+    const long tiles = (long)ta_cdiv(M, v.bm) * ta_cdiv(N, v.bn) * splits;
+    const double rounds = (double)((tiles + v.slots - 1) / v.slots);
+    const double t = rounds * (double)v.bm * v.bn / v.rate * (double)v.per_cu;
+    if (t < best_t) { best_t = t; best = &v; }
   }
   // (Rounds 4-5 built two more kernel families on these tiles and removed them from the library after measuring them slower in the step:
   // gemm_v7 -- one 4-wave workgroup per CU, one wave per SIMD, 256 AGPR accumulators, 4-stage BK = 32 ring -- and its round-5
   // two-workgroups-per-CU form on 128x256 / 256x128 tiles; a 32x32x16 form (gemm_v8).  Sources: scripts/attic/; measurements:
   // profiles/r04_a/e_*, profiles/r05_b_gemm_2wg_*)
-  return best;
+  return *best;
 }
 
-// The variant -> kernel map.  persist: variants 3 / 4 as persistent workgroups (v4, grid = one workgroup per CU at most) instead of one
-// workgroup per tile (v2); variant 12 exists in the persistent form only.  v4 has no K extension: the caller sends neither there with A2.
+// The variant -> kernel map.  persist: the ping-pong variants 3 / 4 as persistent workgroups (v4, grid = one workgroup per CU at most)
+// instead of one workgroup per tile (v2); variant 12 exists in the persistent form only.  Only rows of kVariants arrive here.
 template <int ACT, bool OUT_BF16, bool HAS_RES, bool KEXT>
-static void launch_variant(int variant, bool persist, int grid, int pgrid, const GemmArgs& a, hipStream_t st) {
-  if (variant == 0) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 128, KEXT>), dim3(grid), dim3(256), 0, st, a);
-  else if (variant == 5) TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 96, KEXT>), dim3(grid), dim3(256), 0, st, a);
-  else if (variant == 1) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, false, KEXT>), dim3(grid), dim3(512), 0, st, a);
-  else if (variant == 12) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES, 192>), dim3(pgrid), dim3(512), 0, st, a);
-  else if (variant == 3 && persist) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
-  else if (variant == 4 && persist) TA_LAUNCH((gemm_nt_kernel_v4<320, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
-  else if (variant == 3) TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, true, KEXT>), dim3(grid), dim3(512), 0, st, a);
-  else if (variant == 4) TA_LAUNCH((gemm_nt_kernel_v2<320, ACT, OUT_BF16, HAS_RES, true, KEXT>), dim3(grid), dim3(512), 0, st, a);
-  else if (variant == 10) TA_LAUNCH((gemm_nt_kernel_v5<ACT, OUT_BF16, HAS_RES, KEXT>), dim3(grid), dim3(256), 0, st, a);
-  else TA_LAUNCH((gemm_nt_kernel_v2<128, ACT, OUT_BF16, HAS_RES, false, KEXT>), dim3(grid), dim3(512), 0, st, a);
+static void launch_variant(const Variant& v, bool persist, int grid, int pgrid, const GemmArgs& a, hipStream_t st) {
+  switch (v.id) {
+    case 0: TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 128, KEXT>), dim3(grid), dim3(256), 0, st, a); break;
+    case 5: TA_LAUNCH((gemm_nt_kernel<ACT, OUT_BF16, HAS_RES, 96, KEXT>), dim3(grid), dim3(256), 0, st, a); break;
+    case 3:
+      if (persist) TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
+      else TA_LAUNCH((gemm_nt_kernel_v2<256, ACT, OUT_BF16, HAS_RES, KEXT>), dim3(grid), dim3(512), 0, st, a);
+      break;
+    case 4:
+      if (persist) TA_LAUNCH((gemm_nt_kernel_v4<320, ACT, OUT_BF16, HAS_RES>), dim3(pgrid), dim3(512), 0, st, a);
+      else TA_LAUNCH((gemm_nt_kernel_v2<320, ACT, OUT_BF16, HAS_RES, KEXT>), dim3(grid), dim3(512), 0, st, a);
+      break;
+    case 10: TA_LAUNCH((gemm_nt_kernel_v5<ACT, OUT_BF16, HAS_RES, KEXT>), dim3(grid), dim3(256), 0, st, a); break;
+    case 12: TA_LAUNCH((gemm_nt_kernel_v4<256, ACT, OUT_BF16, HAS_RES, 192>), dim3(pgrid), dim3(512), 0, st, a); break;
+  }
 }
 
 template <int ACT, bool OUT_BF16, bool HAS_RES>
 static int launch_gemm(GemmArgs a, hipStream_t st) {
   if (a.A2 && ACT != 0) return TA_ERR_ARG;          // the K extension exists for plain linears only (LoRA)
-  int variant = pick_variant(a.M, a.N, a.K, a.splits);
   const bool a_far = !a.a_plain && ((long)(a.M / a.a_rpb + 1) * a.a_bs + a.lda * a.a_rpb) * 2 >= (1L << 32);   // row-mapped A is addressed from its start with 32-bit offsets
-  if (variant == 10 && (a.w_blocked || a.a_idx || a_far)) variant = 5;     // v5: no gather, plain W only
-  // the 192-row tile exists in the persistent form only: what that form does not take goes to the 256x256 tile
-  if (variant == 12 && (a.a_idx || a_far || a.A2)) variant = 3;
-  const int bm = variant == 0 ? 128 : (variant == 5 ? 96 : ((variant == 10 || variant == 12) ? 192 : 256));
-  const int bn = variant == 4 ? 320 : ((variant == 1 || variant == 3 || variant == 12) ? 256 : 128);
+  const unsigned needs = (a.a_idx ? V_GATHER : 0u) | (a_far ? V_FAR_A : 0u) | (a.A2 ? V_KEXT : 0u) | (a.w_blocked ? V_WBLOCKED : 0u);
+  const Variant* vp = &pick_variant(a.M, a.N, a.K, a.splits);
+  while (vp->cannot & needs) vp = find_variant(vp->fallback);      // (10 -> 5, 12 -> 3: rows that take everything)
+  const Variant& v = *vp;
   // rows-grouped launch: every group may end in a partial M tile, so the tile grid is an upper bound (surplus tiles exit)
-  a.tiles_m = ta_cdiv(a.M, bm) + ((a.grp_n > 0 && a.seg) ? a.grp_n : 0); a.tiles_n = ta_cdiv(a.N, bn);
+  a.tiles_m = ta_cdiv(a.M, v.bm) + ((a.grp_n > 0 && a.seg) ? a.grp_n : 0); a.tiles_n = ta_cdiv(a.N, v.bn);
   const int grid = a.tiles_m * a.tiles_n * a.splits;
   // few M-tiles (LM head): one group, W panels read once per XCD; otherwise the kernel's own group height.
   // (Round 3, measured and not kept: groups of 16 row tiles instead of 4 for the 12 column tiles of 320 of the encoder's q | k | v GEMM
   // -- an XCD's round is then 16 row tiles x 2 column tiles.  Cold operands (profiles/r03_c_gemm_enc_groupm_cold.txt): 146.3 us against
   // 153.9 (g = 8: 148.1); N = 5120 / 1280 shapes are flat in g; in the STEP 42.85 vs 42.79 ms (profiles/r03_d_ab_groupm.txt).)
-  a.group_m = (variant != 0 && a.tiles_m <= 8) ? a.tiles_m : 0;
+  a.group_m = (v.id != 0 && a.tiles_m <= 8) ? a.tiles_m : 0;
   a.wide = (((long)a.N | a.ldc | a.c_off | a.c_bs) & 7) == 0;
   a.gelu_erf = knobs().gelu_erf;
-  // Ping-pong tiles run as persistent workgroups (v4).  Gathered A rows stay on v2 (their offsets are not bounded by the tile) and so
-  // does far row-mapped A.  So does the K extension (LoRA): its first persistent form hoisted the extension's nine DMA offsets out of
-  // the tile loop and spilled the regular ones (91.8 against 61.6 us per launch, profiles/r03_p_ab_lora.txt); with the offsets derived
-  // from a fresh thread index at the switch there was no scratch and the LoRA step was the same on both kernels (45.45 ms each,
-  // profiles/r03_r_ab_lora_persist_kext.txt), so v4 carries no extension.
   // (variant 12 is always persistent; `persist`, which the launch log records, says which form variants 3 / 4 take)
-  const bool persist = (variant == 3 || variant == 4) && !a.a_idx && !a.A2 && !a_far;
+  const bool persist = v.v2 && !(needs & V_NOT_PERSISTENT);
   static const int ncu = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
   const int pgrid = grid < ncu ? grid : ncu;
   ProfRec r;
@@ -916,20 +779,35 @@ static int launch_gemm(GemmArgs a, hipStream_t st) {
     (void)hipEventRecord(r.a, st);
   }
   if constexpr (ACT == 0) {
-    if (a.A2) launch_variant<ACT, OUT_BF16, HAS_RES, true>(variant, persist, grid, pgrid, a, st);
+    if (a.A2) launch_variant<ACT, OUT_BF16, HAS_RES, true>(v, persist, grid, pgrid, a, st);
   }
-  if (!a.A2) launch_variant<ACT, OUT_BF16, HAS_RES, false>(variant, persist, grid, pgrid, a, st);
+  if (!a.A2) launch_variant<ACT, OUT_BF16, HAS_RES, false>(v, persist, grid, pgrid, a, st);
   if (g_prof_on) { (void)hipEventRecord(r.b, st); g_prof.push_back(r); }
   if (g_log_on) {
     const long flags = (a.a_idx ? 1 : 0) | (a.seg ? 2 : 0) | (a.krange ? 4 : 0) | (a.A2 ? 8 : 0) | (a.w_blocked ? 16 : 0) | (a.grp_n > 0 ? 32 : 0) |
                        (a.a_plain ? 256 : 0) | (a.c_plain ? 512 : 0);
     const long rec[TA_GEMM_LOG_FIELDS] = {a.M, a.N, a.K, a.lda, a.a_rpb, a.a_bs, a.ldc, a.c_rpb, a.c_bs, a.c_off, ACT, OUT_BF16 ? 1 : 0,
-                                          HAS_RES ? 1 : 0, a.res_bf16, a.bias ? 1 : 0, a.splits, a.rope_cols, a.rope_rows, flags, a.K2, variant,
+                                          HAS_RES ? 1 : 0, a.res_bf16, a.bias ? 1 : 0, a.splits, a.rope_cols, a.rope_rows, flags, a.K2, v.id,
                                           a.grp_n, 0, persist ? 1 : 0};
     g_log.insert(g_log.end(), rec, rec + TA_GEMM_LOG_FIELDS);
   }
   TA_CHECK_LAUNCH();
   return TA_OK;
+}
+
+// (act, out_bf16, residual) -> the instantiation.  ACT 2 (rope) exists only as <2, true, false> (the entry point has refused the rest),
+// an unknown act is an argument error
+static int dispatch_gemm(int act, bool out_bf16, bool has_res, const GemmArgs& a, hipStream_t st) {
+  int rc = TA_ERR_ARG;
+  with_const<0, 1, 2>(act, [&](auto act_c) {
+    with_bool(out_bf16, [&](auto ob) {
+      with_bool(has_res, [&](auto hr) {
+        constexpr int ACT = decltype(act_c)::value;
+        if constexpr (ACT != 2 || (decltype(ob)::value && !decltype(hr)::value)) rc = launch_gemm<ACT, decltype(ob)::value, decltype(hr)::value>(a, st);
+      });
+    });
+  });
+  return rc;
 }
 
 extern "C" int ta_profile_gemm(int enable) {
@@ -967,13 +845,6 @@ extern "C" int ta_profile_gemm_collect(double* total_ms, double* total_flops, lo
 }
 
 // ----------------------------------------------------------------------------- C-ABI (see include/ta355.h)
-extern "C" int ta_gemm_bf16_nt_ex(const void* A, const void* W, void* C, int M, int N, int K,
-                                  long lda, int a_rpb, long a_bs,
-                                  long ldc, int c_rpb, long c_bs, long c_off,
-                                  const float* bias, const float* residual,
-                                  int act, int out_bf16, int splits, float* splitk_ws,
-                                  const int* a_idx, const int* seg, const int* krange, hipStream_t st);
-
 extern "C" int ta_gemm_bf16_nt(const void* A, const void* W, void* C, int M, int N, int K,
                                long lda, int a_rpb, long a_bs,
                                long ldc, int c_rpb, long c_bs, long c_off,
@@ -1010,7 +881,7 @@ extern "C" int ta_gemm_bf16_nt_opt(const void* A, const void* W, void* C, int M,
   if ((K % BK) != 0 || (N % 4) != 0 || (lda % 8) != 0 || (a_bs % 8) != 0 || (ldc % 4) != 0 ||
       (c_off % 4) != 0 || (c_bs % 4) != 0)
     return TA_ERR_ARG;
-  GemmArgs a;
+  GemmArgs a;                                        // (what is not set here keeps its default: gemm_common.h)
   a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = C; a.bias = bias; a.res = residual;
   a.M = M; a.N = N; a.K = K;
   a.lda = lda; a.a_rpb = a_rpb > 0 ? a_rpb : M; a.a_bs = a_bs;
@@ -1022,8 +893,7 @@ extern "C" int ta_gemm_bf16_nt_opt(const void* A, const void* W, void* C, int M,
   a.A2 = (const bf16_t*)xA2; a.W2 = (const bf16_t*)xW2; a.K2 = xK2; a.lda2 = o.lda2;
   a.res_bf16 = resb != nullptr;
   a.rope_tab = o.rope_tab; a.rope_rows = o.rope_rows; a.rope_cols = o.rope_cols > 0 ? o.rope_cols : N;
-  a.w_blocked = o.w_blocked ? 1 : 0; a.a_blocked = 0;
-  a.grp_n = 0; a.grp_w_stride = 0;
+  a.w_blocked = o.w_blocked ? 1 : 0;
   if (a.w_blocked && ((N & 63) || xA2 || krange || a_idx)) return TA_ERR_ARG;
   if (act == 2 && (!o.rope_tab || o.rope_rows <= 0 || !out_bf16 || residual || splits > 1 || (N % 64) || o.rope_cols < 0 || (o.rope_cols % 64))) return TA_ERR_ARG;
   if (resb && splits > 1) return TA_ERR_ARG;
@@ -1046,17 +916,7 @@ extern "C" int ta_gemm_bf16_nt_opt(const void* A, const void* W, void* C, int M,
     TA_CHECK_LAUNCH();
     return TA_OK;
   }
-  const bool hr = residual != nullptr;
-  if (act == 0) {
-    if (out_bf16) return hr ? launch_gemm<0, true, true>(a, st) : launch_gemm<0, true, false>(a, st);
-    return hr ? launch_gemm<0, false, true>(a, st) : launch_gemm<0, false, false>(a, st);
-  } else if (act == 1) {
-    if (out_bf16) return hr ? launch_gemm<1, true, true>(a, st) : launch_gemm<1, true, false>(a, st);
-    return hr ? launch_gemm<1, false, true>(a, st) : launch_gemm<1, false, false>(a, st);
-  } else if (act == 2) {
-    return launch_gemm<2, true, false>(a, st);
-  }
-  return TA_ERR_ARG;
+  return dispatch_gemm(act, out_bf16 != 0, residual != nullptr, a, st);
 }
 
 
@@ -1068,19 +928,15 @@ extern "C" int ta_gemm_bf16_nt_grouped(const void* A, const void* W, void* C, in
   if (n_groups > 8 || (seg != nullptr) == (krange != nullptr) || (K % BK) || (N % 4) || (w_stride % 8) || (c_stride % 4)) return TA_ERR_ARG;
   if (krange && (out_bf16 || bias || act || a_idx || w_stride)) return TA_ERR_ARG;      // K-slice form: plain f32 products
   if (act != 0 && act != 1) return TA_ERR_ARG;
-  GemmArgs a;
-  a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = C; a.bias = bias; a.res = nullptr;
+  GemmArgs a;                                        // plain operands, identity row maps: the defaults
+  a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = C; a.bias = bias;
   a.M = M; a.N = N; a.K = K;
-  a.lda = K; a.a_rpb = 0x7fffffff; a.a_bs = 0; a.ldc = N; a.c_rpb = 0x7fffffff; a.c_bs = 0; a.c_off = 0;
-  a.a_plain = 1; a.c_plain = 1;
+  a.lda = K; a.ldc = N;
   a.a_idx = a_idx; a.seg = seg; a.krange = krange;
-  a.A2 = nullptr; a.W2 = nullptr; a.K2 = 0; a.lda2 = 0; a.res_bf16 = 0;
-  a.rope_tab = nullptr; a.rope_rows = 0; a.rope_cols = 0; a.w_blocked = 0; a.a_blocked = 0;
   a.grp_n = n_groups; a.grp_w_stride = w_stride;
   a.splits = krange ? n_groups : 1;           // K-slice form: z = group, slabs c_stride apart
   a.slab_stride = krange ? c_stride : (long)M * N;
-  if (act == 1) return out_bf16 ? launch_gemm<1, true, false>(a, st) : launch_gemm<1, false, false>(a, st);
-  return out_bf16 ? launch_gemm<0, true, false>(a, st) : launch_gemm<0, false, false>(a, st);
+  return dispatch_gemm(act, out_bf16 != 0, false, a, st);
 }
 
 extern "C" long ta_gemm_splitk_ws_bytes(int M, int N, int splits) {

@@ -1,45 +1,47 @@
-// Shared between the GEMM translation units (gemm.hip: the 8-wave / 4-wave VGPR-accumulator kernels; gemm_v7.hip: the one-wave-per-SIMD
-// AGPR-accumulator kernel): launch arguments, the epilogue of a tile, the tile walk of the persistent kernels.
+// What the kernels of gemm.hip share: the launch arguments, the DMA primitives, the tile walk (tile_ctx: v2, v4 and v5 get their tile
+// from it; the 4-wave kernel keeps a copy, see there), the operand addressing of the DMA sources, the fragment read offsets, the ping-pong K step of the 8-wave kernels
+// (pingpong_ktile) and the epilogue of a tile.
 #pragma once
 #include "common.h"
 #include "../../include/ta355.h"
 #include <type_traits>
 
+// (the defaults are a plain [M, K] x [N, K]^T product with identity row maps; the entry points set what differs)
 struct GemmArgs {
-  const bf16_t* A;
-  const bf16_t* W;
-  void* C;
-  const float* bias;   // [N] or null
-  const float* res;    // f32 residual, same row map as C, or null
-  int M, N, K;
-  long lda; int a_rpb; long a_bs;
-  long ldc; int c_rpb; long c_bs; long c_off;
-  int tiles_m, tiles_n, splits;
-  long slab_stride;    // elements between split-K slabs (C is f32 slabs when splits > 1)
+  const bf16_t* A = nullptr;
+  const bf16_t* W = nullptr;
+  void* C = nullptr;
+  const float* bias = nullptr;   // [N] or null
+  const float* res = nullptr;    // f32 residual, same row map as C, or null
+  int M = 0, N = 0, K = 0;
+  long lda = 0; int a_rpb = 0x7fffffff; long a_bs = 0;
+  long ldc = 0; int c_rpb = 0x7fffffff; long c_bs = 0; long c_off = 0;
+  int tiles_m = 0, tiles_n = 0, splits = 1;
+  long slab_stride = 0;    // elements between split-K slabs (C is f32 slabs when splits > 1)
   // grouped / routed GEMM (MoE experts) without a host round trip: all three are DEVICE pointers or null
-  const int* a_idx;    // A row of logical row r is a_idx[seg_base + r] (gather); null = seg_base + r
-  const int* seg;      // {row base, row count}: this launch covers rows [base, base+count) of A (via a_idx) and of C
-  const int* krange;   // {first, last+1} K-tile (64-wide): contract only over that slice (per-expert dW over sorted slots)
+  const int* a_idx = nullptr;    // A row of logical row r is a_idx[seg_base + r] (gather); null = seg_base + r
+  const int* seg = nullptr;      // {row base, row count}: this launch covers rows [base, base+count) of A (via a_idx) and of C
+  const int* krange = nullptr;   // {first, last+1} K-tile (64-wide): contract only over that slice (per-expert dW over sorted slots)
   // K extension (LoRA): after the K columns of A / W the contraction continues over K2 more columns taken from
   // A2 [M, K2] (row stride lda2) and W2 [N, K2]:  C = A W^T + A2 W2^T  in one accumulator pass
-  const bf16_t* A2; const bf16_t* W2; int K2; long lda2;
-  int res_bf16;        // the residual is bf16 (same row map as C), not f32
+  const bf16_t* A2 = nullptr; const bf16_t* W2 = nullptr; int K2 = 0; long lda2 = 0;
+  int res_bf16 = 0;        // the residual is bf16 (same row map as C), not f32
   // act == 2: partial rotary embedding in the epilogue (GLM-ASR q|k projection).  Heads are 64 columns; the first 32
   // columns of every head hold the 16 rotation pairs INTERLEAVED (pair i = columns 2i, 2i+1), so both members of a pair
   // sit in one lane; rope_tab [rope_rows][16][2] = (cos, sin) of pair i at position (logical row % rope_rows)
-  const float* rope_tab; int rope_rows; int rope_cols;   // rope on columns [0, rope_cols)
-  int group_m;         // tile-order group height (L2 reuse of W panels inside a group of M-tiles)
-  int wide;            // bf16 epilogue may use 16-B (8-column) stores: N, ldc, c_off, c_bs all multiples of 8
-  int w_blocked;       // W is stored as [N/64][K/64][64][64] blocks (8 KB contiguous per 64 rows x one K tile)
-  int a_plain, c_plain; // the row map is the identity (one batch): skips two integer divisions per row in prologue / epilogue
-  int gelu_erf;        // act == 1: the arithmetic erf-GELU (gelu_erf_fast) instead of the chord table
-  int a_blocked;       // A is stored in blocks like W under w_blocked (the persistent kernel only; always 0, see gemm_nt_kernel_v4)
+  const float* rope_tab = nullptr; int rope_rows = 0; int rope_cols = 0;   // rope on columns [0, rope_cols)
+  int group_m = 0;         // tile-order group height (L2 reuse of W panels inside a group of M-tiles)
+  int wide = 0;            // bf16 epilogue may use 16-B (8-column) stores: N, ldc, c_off, c_bs all multiples of 8
+  int w_blocked = 0;       // W is stored as [N/64][K/64][64][64] blocks (8 KB contiguous per 64 rows x one K tile)
+  int a_plain = 1, c_plain = 1; // the row map is the identity (one batch): skips two integer divisions per row in prologue / epilogue
+  int gelu_erf = 0;        // act == 1: the arithmetic erf-GELU (gelu_erf_fast) instead of the chord table
+  int a_blocked = 0;       // A is stored in blocks like W under w_blocked (the persistent kernel only; always 0, see gemm_nt_kernel_v4)
   // Grouped launch (MoE experts in ONE launch, ta_gemm_bf16_nt_grouped):
   //   rows form    seg = int[2 * grp_n] {row base, row count}: M tile indices run over the concatenation of the groups' row
   //                tiles; group e multiplies by W + e * grp_w_stride and adds bias + e * N
   //   K-slice form krange = int[2 * grp_n] K-tile ranges, the launch's z index IS the group: (C + z * slab_stride) gets the
   //                product contracted over slice z (per-expert weight gradients over the slot-sorted token axis)
-  int grp_n; long grp_w_stride;
+  int grp_n = 0; long grp_w_stride = 0;
 };
 
 #define BM 128
@@ -47,9 +49,7 @@ struct GemmArgs {
 #define BK 64
 // per-CU throughput of the 256-row tile variants relative to the 128x128 kernel (two co-resident workgroups),
 // measured with scripts/gemm_bench.py; used only by the launch-time variant choice
-#ifndef TA355_RATE_256x256
-#define TA355_RATE_256x256 0.9      /* simple double buffer: superseded by the ping-pong schedule */
-#define TA355_RATE_256x128 0.5      /* measured slower than 128x128 on every shape */
+#ifndef TA355_RATE_256x256_PP
 #define TA355_RATE_256x256_PP 1.40  /* per unit tile area vs the 128x128 kernel, fitted on profiles/r01_f_gemm_variants.txt (lm_qkv 56 vs 62 us, sq8192 1330 vs 1050 TF/s) */
 #define TA355_RATE_96x128 0.93      /* 3x4 instead of 4x4 MFMAs per fragment set; estimate, to be refitted */
 #define TA355_RATE_192x128 1.1      /* v5 (one 192x128 tile per CU), cold operands, profiles/r02_gemm_v5_ab_cold.txt: 1.05-1.15 in one round (lm o / down / dX: 43.5 / 58.5 / 61.7 / 97.2 us vs 49.4 / 68.4 / 74.3 / 120.2 for 96x128), 0.9-1.03 over several rounds; in the step 1.0 / 1.1 / 1.25 are equal for Qwen3-0.6B and 1.1 is 1 ms better than 1.0 for the 1.7B widths (2-round N = 2048 shapes); 0 = never chosen */
@@ -240,8 +240,7 @@ __device__ __forceinline__ void epilogue_tile_full(const f32x4 (*acc)[NT], const
 //   1  strips in PAIRS: the residual of strips i and i + 1 in one batch (4 round trips per 8 strips; +NT registers)
 //   2  one strip ahead (the one-wave-per-SIMD kernel: registers to spare; in the 8-wave kernels at 256 VGPRs this form spilled
 //      into the main loop)
-// PIN (gemm_v7.hip): the first PIN fragments of a strip are AGPR accumulators and stay there until the strip is processed
-template <int MI, int NT, int ACT, bool OUT_BF16, bool HAS_RES, int AHEAD = 0, bool ELS = false, int PIN = 0>
+template <int MI, int NT, int ACT, bool OUT_BF16, bool HAS_RES, int AHEAD = 0, bool ELS = false>
 __device__ __forceinline__ void epilogue_tile(const f32x4 (*acc)[NT], const GemmArgs& p, char* Cb, int ml0, int Mact, int rbase, int nb,
                                               int g, bool wide, const float* bias, const float2* lut, const char* els = nullptr,
                                               int ecol0 = 0, int erow0 = 0) {
@@ -266,11 +265,6 @@ __device__ __forceinline__ void epilogue_tile(const f32x4 (*acc)[NT], const Gemm
   };
   auto strip = [&](int i, const EpiPre<NT>* pre) {
     const int ml = ml0 + i * 16;
-    if constexpr (PIN > 0) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        if (j < PIN) asm volatile("" : "+a"(const_cast<f32x4&>(acc[i][j])));
-    }
     if (ml < Mact) {
       const int m = rbase + ml;
       epilogue_strip<NT, ACT, OUT_BF16, HAS_RES, ELS>(acc[i], p, Cb, row_off(m), nb, g, wide, m, bias, lut, pre, pre_r, els, ecol0, erow0 + i * 16);
@@ -369,15 +363,13 @@ template <int ACT, bool OUT_BF16, bool HAS_RES>
 __device__ __forceinline__ bool residual_is_start(const GemmArgs& p) {
   return HAS_RES && ACT == 0 && OUT_BF16 && p.res_bf16 && p.splits == 1;
 }
-// HBMAX: strips per batch of loads (0: half the tile, at most 4); PIN (gemm_v7.hip): the first PIN fragments of a strip are AGPR
-// accumulators -- each start value moves there as soon as it is converted
-template <int MI, int NT, int HBMAX = 0, int PIN = 0>
+template <int MI, int NT>
 __device__ __forceinline__ void residual_start(f32x4 (*acc)[NT], const GemmArgs& p, int ml0, int Mact, int rbase, int nb, int g) {
   const int c_rpb_o = opaque_sgpr(p.c_rpb);          // (see epilogue_tile)
   int ncl[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) { const int n = nb + j * 16 + g * 4; ncl[j] = n < p.N ? n : p.N - 4; }
-  constexpr int HB = HBMAX > 0 ? HBMAX : (MI > 4 ? (MI + 1) / 2 : MI);
+  constexpr int HB = MI > 4 ? (MI + 1) / 2 : MI;      // strips per batch of loads: half the tile, at most 4
 #pragma unroll
   for (int i0 = 0; i0 < MI; i0 += HB) {
     uint2 t[HB][NT];
@@ -396,7 +388,6 @@ __device__ __forceinline__ void residual_start(f32x4 (*acc)[NT], const GemmArgs&
         for (int j = 0; j < NT; ++j) {
           const uint2 r = t[i][j];
           acc[i0 + i][j] = (f32x4){bf2f((bf16_t)(r.x & 0xffff)), bf2f((bf16_t)(r.x >> 16)), bf2f((bf16_t)(r.y & 0xffff)), bf2f((bf16_t)(r.y >> 16))};
-          if constexpr (PIN > 0) { if (j < PIN) asm volatile("" : "+a"(acc[i0 + i][j])); }
         }
       }
   }
@@ -423,8 +414,6 @@ __device__ __forceinline__ const float2* stage_gelu_lut(char* smem, const GemmAr
   }
   return nullptr;
 }
-__device__ __forceinline__ bool epilogue_wide_ok(const GemmArgs& p) { return p.wide != 0; }
-
 
 // Group of a tile in a grouped launch (see GemmArgs.grp_n).  rows form: walks the <= 8 segments; returns false for the
 // surplus tiles of the (upper-bound) grid.
@@ -450,6 +439,9 @@ __device__ __forceinline__ bool resolve_group(const GemmArgs& p, int& pm, int z,
 }
 
 struct TileCtx { int ok, m0, n0, kb, ke, Mact, rbase, z; const bf16_t* Wp; const float* biasp; };
+// The tile walk: slot h of `total` (one-tile-per-workgroup launches: blockIdx.x of gridDim.x) -> XCD-aware, grouped
+// tile order (block b runs on XCD b % 8: each XCD gets a contiguous chunk), the tile's group in a grouped launch, its K range under
+// split-K / a K-range table, its row segment.  ok = 0: a surplus tile (block-uniform: the caller leaves before any barrier).
 template <int BM2, int BN2>
 __device__ __forceinline__ TileCtx tile_ctx(const GemmArgs& p, int h, int total) {
   TileCtx c; c.ok = 0;
@@ -473,7 +465,7 @@ __device__ __forceinline__ TileCtx tile_ctx(const GemmArgs& p, int h, int total)
   c.m0 = pm * BM2; c.n0 = pn * BN2; c.z = z;
   const int nkt = p.K / BK;
   c.kb = 0; c.ke = nkt;
-  if (p.splits > 1) { c.kb = (nkt * z) / p.splits; c.ke = (nkt * (z + 1)) / p.splits; }   // 32-bit: the 64-bit quotients of v2 cost ~2 k cycles per tile
+  if (p.splits > 1) { c.kb = (nkt * z) / p.splits; c.ke = (nkt * (z + 1)) / p.splits; }   // 32-bit, and only when split: two 64-bit quotients cost ~2 k cycles per tile
   if (krp) { c.kb = krp[0]; c.ke = krp[1]; }
   c.Mact = p.M; c.rbase = 0;
   if (segp) { c.rbase = segp[0]; c.Mact = segp[1]; if (c.m0 >= c.Mact) return c; }
@@ -483,4 +475,82 @@ __device__ __forceinline__ TileCtx tile_ctx(const GemmArgs& p, int h, int total)
   c.rbase = __builtin_amdgcn_readfirstlane(c.rbase); c.Mact = __builtin_amdgcn_readfirstlane(c.Mact);
   c.ok = 1;
   return c;
+}
+// The tile of this workgroup in a one-tile-per-workgroup launch (v2, v5).  That a tile's origin is a multiple of the tile is said
+// again for the compiler: it loses that fact through the fields tile_ctx leaves unset for a surplus tile, and the rope epilogue
+// drops the fragments that never rotate (columns 32 .. 63 of a head) on the strength of n0 % 64 == 0.
+template <int BMT, int BNT>
+__device__ __forceinline__ TileCtx block_tile(const GemmArgs& p) {
+  const TileCtx c = tile_ctx<BMT, BNT>(p, blockIdx.x, gridDim.x);
+  if (c.ok) {
+    __builtin_assume((c.m0 & ((BMT & -BMT) - 1)) == 0);
+    __builtin_assume((c.n0 & ((BNT & -BNT) - 1)) == 0);
+  }
+  return c;
+}
+
+// ---- operand addressing of the DMA sources (elements)
+// A's row map: logical row gm -> element offset of its first column
+__device__ __forceinline__ long a_row_off(const GemmArgs& p, int gm) {
+  return p.a_plain ? (long)gm * p.lda : (long)(gm / p.a_rpb) * p.a_bs + (long)(gm % p.a_rpb) * p.lda;
+}
+// first element of W row gn in K tile kt (plain [N, K], or [N/64][K/64][64][64] blocks)
+__device__ __forceinline__ long w_tile_off(const GemmArgs& p, int gn, int nkt, int kt) {
+  return p.w_blocked ? ((((long)(gn >> 6) * nkt + kt) << 12) + ((gn & 63) << 6)) : ((long)gn * p.K + (long)kt * BK);
+}
+// the pointer form (v1, v2): this thread's 16-B chunk of A row gm (through the gather table, if there is one) / of W row gn in K tile kt
+__device__ __forceinline__ const char* a_chunk_src(const GemmArgs& p, int gm, int kt, int clog) {
+  if (p.a_idx) gm = p.a_idx[gm];
+  return (const char*)(p.A + a_row_off(p, gm) + (long)kt * BK + clog * 8);
+}
+__device__ __forceinline__ const char* w_chunk_src(const GemmArgs& p, const bf16_t* Wp, int gn, int nkt, int kt, int clog) {
+  return (const char*)(Wp + w_tile_off(p, gn, nkt, kt) + clog * 8);
+}
+// the offset form (v4, v5: uniform base + 32-bit byte offset per 16-B chunk): row `row` relative to the tile's first row `row0`
+__device__ __forceinline__ unsigned rel_off(int row, int row0, long ld, int clog) {
+  return (unsigned)(((long)(row - row0) * ld + clog * 8) * 2);
+}
+
+// ---- per-lane fragment read offsets inside a [rows][128 B] tile image: the 16-B chunk of k columns 8 c .. 8 c + 7 of a row sits at
+// chunk c ^ (row >> 1 & 7) (applied on the source side of the DMA, undone here); lane (l15, g) reads chunks g and 4 + g
+struct FragOff { int k0, k1; };
+__device__ __forceinline__ FragOff frag_koff(int l15, int g) {
+  const int swz = l15 >> 1;
+  return {((0 + g) ^ swz) << 4, ((4 + g) ^ swz) << 4};
+}
+
+// ---- one K tile of the ping-pong schedule (gemm.hip: v2 / v4): for each half kk, L(t, kk) = the NT + MI fragment reads of stage S
+// (+ `issue()`, the caller's DMA requests, when kk = 0) and their counted wait, barrier, C(t, kk) = MI x NT MFMAs, barrier.
+template <int MI, int NT, typename Issue>
+__device__ __forceinline__ void pingpong_ktile(const char* S, int a_rd, int b_rd, FragOff ko2, f32x4 (*acc)[NT], Issue&& issue) {
+  bf16x8 af[MI], bfr[NT];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    const int ko = kk ? ko2.k1 : ko2.k0;
+    // ---- L(t, kk)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) bfr[j] = *(const bf16x8*)(S + b_rd + j * 2048 + ko);
+#pragma unroll
+    for (int i = 0; i < MI; ++i) af[i] = *(const bf16x8*)(S + a_rd + i * 2048 + ko);
+    if (kk == 0) {
+      issue();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- C(t, kk)
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  }
 }
