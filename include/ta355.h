@@ -807,6 +807,72 @@ int ta_ctc_align_f32(const float* emission, long ld, int C, const int* cu_frames
                      int max_T, int max_J, int blank_id, int* frames, float* score, int* status, void* ws, long ws_bytes,
                      float* trellis_out, const long* trellis_off, hipStream_t st);
 
+/* ---- frozen wav2vec2-base CTC acoustic model: the front half of forced alignment (tiny_audio_amd/csrc/wav2vec2.hip).  Replaces the
+ * torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax the reference runs through PyTorch in ForcedAligner.align
+ * (tiny_audio/alignment.py:206-211).  Arithmetic of Wav2Vec2ForCTC.forward (TF:models/wav2vec2/modeling_wav2vec2.py:1667-1700; feature encoder :382-419, projection :422-434,
+ * encoder :657-727, layer :575-608) with
+ * feat_extract_norm="group", conv_bias=False, do_stable_layer_norm=False, no attention mask, no input normalisation; inference only.
+ * Every clip is processed as if alone (the reference aligns one unpadded clip at a time).  Contract: DESIGN.md section 3, "wav2vec2
+ * acoustic model", defined by tests/wav2vec2_ref.py.
+ * ta_enc_layer is reused with ln1_* = layer_norm (behind the attention residual), ln2_* = final_layer_norm, wo/bo = attention.out_proj,
+ * w1/b1 = feed_forward.intermediate_dense, w2/b2 = feed_forward.output_dense, and wqkv_fa / bqkv_fa (REQUIRED) = q | k | v rows in
+ * their natural order with the q rows and q bias multiplied by head_dim^-0.5 * log2(e); k keeps its bias.  wqkv / bqkv are not read. */
+#define TA_W2V_HEAD_PAD 64   /* rows of the zero-padded lm_head image; n_classes <= 64 */
+typedef struct {
+  int hidden, ffn, n_layers, heads, conv_dim, n_classes;   /* hidden = 64 * heads, hidden and ffn multiples of 128, hidden / 16 a
+                                                              multiple of 8 up to 64, conv_dim a multiple of 64 */
+  float ln_eps;
+  const float* conv0_w;        /* f32 [C, 10]: feature_extractor.conv_layers.0.conv.weight */
+  const float *gn_w, *gn_b;    /* [C]: conv_layers.0.layer_norm (GroupNorm, C groups) */
+  const void* conv_w[6];       /* conv_layers.1 .. 6: bf16 [C, k*C], column = tap*C + cin; k = 3,3,3,3,2,2, stride 2 */
+  const float *fp_ln_w, *fp_ln_b;   /* [C]: feature_projection.layer_norm */
+  const void* fp_w;            /* bf16 [H, C]: feature_projection.projection */
+  const float* fp_b;
+  const void* pos_w;           /* bf16 [16][NB*16][128*cg], cg = H/16, NB = ceil(cg/16): group g, output channel co (rows >= cg ZERO),
+                                  column = tap*cg + cin -- pos_conv_embed.conv's weight with its weight norm folded */
+  const float* pos_b;          /* [H] */
+  const float *enc_ln_w, *enc_ln_b; /* encoder.layer_norm */
+  const ta_enc_layer* layers;  /* host array [n_layers] */
+  const void* head_w;          /* bf16 [TA_W2V_HEAD_PAD, H]: lm_head.weight, rows >= n_classes ZERO */
+  const float* head_b;         /* [n_classes] */
+  int res_f32;                 /* storage of the residual stream: 0 = bf16, 1 = fp32 (see the top of this file) */
+} ta_wav2vec2_weights;
+
+/* wav f32 [B, Ls] (clip b = its first lens[b] samples, 400 <= lens[b] <= Ls; the rest is never read) -> emissions f32
+ * [rows, n_classes] log-probabilities, rows = sum of T_b with T_b = (lens[b] - 400) / 320 + 1 ((T - k) / s + 1 per conv layer), clip
+ * b at rows cu_frames[b] .. cu_frames[b + 1]: the layout ta_ctc_align_f32 takes.  Rows past `rows` are not written.
+ * lens_host: HOST int [B] (sets the launch geometry); lens_dev: the same on the DEVICE; cu_frames_dev: DEVICE int [B + 1] built by
+ * the caller from the same lengths (the host cannot read it: a table that disagrees is not detected, as for
+ * ta_encoder_forward_ragged).  ws: ta_wav2vec2_workspace_bytes(w, B, Ls, rows) bytes, no initial contents required; on return its
+ * last rows * TA_W2V_HEAD_PAD floats (rounded up to 256 bytes) hold the lm_head GEMM's f32 output [rows, TA_W2V_HEAD_PAD], bias not added.
+ * Kernel launches on st only: no allocation, copy or synchronisation. */
+long ta_wav2vec2_workspace_bytes(const ta_wav2vec2_weights* w, int B, int Ls, long rows);
+int ta_wav2vec2_forward(const ta_wav2vec2_weights* w, const float* wav, const int* lens_host, const int* lens_dev,
+                        const int* cu_frames_dev, int B, int Ls, float* emissions, void* ws, long ws_bytes, hipStream_t st);
+
+/* Its new kernels, exported for the tests.
+ * Conv layer 0 (k 10, stride 5, no bias) + GroupNorm(C groups: per-channel statistics over the clip's own T0 = (len - 10) / 5 + 1
+ * frames, biased variance, eps) + exact GELU: replaces Wav2Vec2GroupNormConvLayer.forward
+ * (TF:models/wav2vec2/modeling_wav2vec2.py:302-323).  w f32 [C, 10]; out bf16 time-major, clip b's frame t at row b * out_rpb + t
+ * (out_rpb >= (Ls - 10) / 5 + 1); rows t >= T0_b are not written.  The statistics are per-256-frame-chunk (mean, sum of squared
+ * deviations from it) merged pairwise in f64; the conv is recomputed for the apply pass.  ws: ta_w2v_conv0_ws_bytes(B, Ls, C). */
+long ta_w2v_conv0_ws_bytes(int B, int Ls, int C);
+int ta_w2v_conv0_gn_gelu(const float* wav, const int* lens_dev, int B, int Ls, const float* w, const float* gn_w,
+                         const float* gn_b, int C, float eps, void* out_bf16, long out_rpb, void* ws, long ws_bytes,
+                         hipStream_t st);
+/* y = x + gelu(pos_conv(x) + bias) with Conv1d(H, H, k = 128, padding = 64, groups = 16) and its last output frame dropped:
+ * replaces Wav2Vec2PositionalConvEmbedding.forward and the add behind it (TF:models/wav2vec2/modeling_wav2vec2.py:326-379, :689-690).
+ * x, y: [rows, H] in the stream's dtype (x_f32: 0 = bf16, 1 = f32), y != x; clip b owns rows cu_rows[b] .. cu_rows[b + 1] and meets
+ * zeros outside them; max_rows = the longest clip (sizes the grid).  wp / bias: ta_wav2vec2_weights.pos_w / pos_b.  H / 16 must be
+ * a multiple of 8 up to 64 (TA_ERR_ARG otherwise).  bf16 MFMA operands, f32 accumulation. */
+int ta_w2v_pos_conv(const void* x, int x_f32, const void* wp, const float* bias, void* y, const int* cu_rows, int B,
+                    int max_rows, int H, hipStream_t st);
+/* out [rows, n_classes] = log_softmax(logits[:, :n_classes] + bias) in f32, logits f32 [rows, ld] (the lm_head GEMM at its padded
+ * width; columns >= n_classes never enter): replaces lm_head's bias add and torch.log_softmax (tiny_audio/alignment.py:206-211,
+ * TF:models/wav2vec2/modeling_wav2vec2.py:1700).  1 <= n_classes <= TA_W2V_HEAD_PAD, ld >= n_classes. */
+int ta_w2v_head_logsoftmax(const float* logits, long ld, const float* bias, int n_classes, float* out, int rows,
+                           hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ HEADER = os.path.join(ROOT, "include", "ta355.h")
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "libta355.so")
 SOURCES = ["gemm.hip", "gemm_tn.hip", "norm.hip", "attention.hip", "attention_enc.hip", "qkv_post.hip", "elementwise.hip", "loss.hip",
-           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "decode_fused.hip", "augment.hip", "align.hip", "api.hip"]
+           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "decode_fused.hip", "augment.hip", "align.hip", "wav2vec2.hip", "api.hip"]
 
 
 class Ta355Error(RuntimeError):
@@ -50,6 +50,16 @@ class WhisperEncoderWeights(C.Structure):
                 ("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("conv2_w", C.c_void_p), ("conv2_b", C.c_void_p),
                 ("pos_emb", C.c_void_p), ("norm_w", C.c_void_p), ("norm_b", C.c_void_p),
                 ("layers", C.POINTER(EncLayer)), ("res_f32", C.c_int)]
+
+
+class Wav2Vec2Weights(C.Structure):
+    """ta_wav2vec2_weights (include/ta355.h); reuses EncLayer."""
+    _fields_ = [("hidden", C.c_int), ("ffn", C.c_int), ("n_layers", C.c_int), ("heads", C.c_int), ("conv_dim", C.c_int),
+                ("n_classes", C.c_int), ("ln_eps", C.c_float),
+                ("conv0_w", C.c_void_p), ("gn_w", C.c_void_p), ("gn_b", C.c_void_p), ("conv_w", C.c_void_p * 6),
+                ("fp_ln_w", C.c_void_p), ("fp_ln_b", C.c_void_p), ("fp_w", C.c_void_p), ("fp_b", C.c_void_p),
+                ("pos_w", C.c_void_p), ("pos_b", C.c_void_p), ("enc_ln_w", C.c_void_p), ("enc_ln_b", C.c_void_p),
+                ("layers", C.POINTER(EncLayer)), ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("res_f32", C.c_int)]
 
 
 class MlpWeights(C.Structure):

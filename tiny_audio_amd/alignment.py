@@ -10,8 +10,10 @@ What stays in Python, because it is O(tokens) host work in Python float arithmet
 fallback for a clip that cannot be aligned, and the grouping of characters into words (tiny_audio/alignment.py:213-286).
 
 There is no CPU path for the trellis: without a HIP device the methods raise ``Ta355Error``, like the rest of the package.
-The wav2vec2 acoustic model is not part of this library: ``align(..., emission=...)`` and ``align_batch`` take its emissions;
-without ``emission``, ``align`` runs torchaudio's bundle through PyTorch as the reference does, and needs torchaudio installed.
+The wav2vec2 acoustic model is part of this library as an opt-in: ``align(audio, text, acoustic_model=m)`` and
+``align_audio_batch(audios, texts, m)`` take a ``wav2vec2.Wav2Vec2CtcMI355X`` and go waveform -> emissions -> trellis on the device
+with no host round trip of the emissions.  ``align(..., emission=...)`` and ``align_batch`` take emissions computed elsewhere;
+with neither, ``align`` runs torchaudio's bundle through PyTorch as the reference does, and needs torchaudio installed.
 """
 from __future__ import annotations
 
@@ -81,7 +83,15 @@ def _launch(emissions: Sequence[torch.Tensor], tokens: Sequence[Sequence[int]], 
     if any(e.shape[1] != C for e in emissions):
         raise ValueError("every clip of a batch must have the same number of classes")
     dev = _device()
-    Ts, Js = [e.shape[0] for e in emissions], [len(tk) for tk in tokens]
+    em = [e.detach().to(device=dev, dtype=torch.float32) for e in emissions]
+    em = em[0].contiguous() if N == 1 else torch.cat(em, dim=0)
+    return _launch_flat(em, [e.shape[0] for e in emissions], tokens, blank_id, want_trellis)
+
+
+def _launch_flat(em: torch.Tensor, Ts: Sequence[int], tokens: Sequence[Sequence[int]], blank_id: int, want_trellis: bool = False):
+    """``_launch`` on emissions that already sit on the device as one f32 [sum T_n, C] tensor, clip n owning ``Ts[n]`` rows."""
+    N, dev = len(Ts), em.device
+    Js = [len(tk) for tk in tokens]
     cu_f, cu_t = np.zeros(N + 1, np.int32), np.zeros(N + 1, np.int32)
     cu_f[1:], cu_t[1:] = np.cumsum(Ts), np.cumsum(Js)
     flat = np.asarray([int(x) for tk in tokens for x in tk], np.int32)
@@ -90,8 +100,6 @@ def _launch(emissions: Sequence[torch.Tensor], tokens: Sequence[Sequence[int]], 
         sizes = np.asarray([(t + 1) * (j + 1) for t, j in zip(Ts, Js)], np.int64)
         off = np.concatenate([[0], np.cumsum(sizes)])
         tr_off, tr_numel = torch.from_numpy(off[:-1].copy()).to(dev), int(off[-1])
-    em = [e.detach().to(device=dev, dtype=torch.float32) for e in emissions]
-    em = em[0].contiguous() if N == 1 else torch.cat(em, dim=0)
     frames, score, status, trellis = torch.ops.ta355.ctc_align(
         em, torch.from_numpy(cu_f).to(dev), torch.from_numpy(flat).to(dev), torch.from_numpy(cu_t).to(dev), int(blank_id),
         max(Ts), max(Js), tr_off, tr_numel)
@@ -225,16 +233,48 @@ class ForcedAligner:
 
     @classmethod
     def align(cls, audio, text: str, sample_rate: int = 16000, _language: str = "eng", _batch_size: int = 16, *,
-              emission: torch.Tensor | None = None, log_softmax: bool = False) -> list[dict]:
+              emission: torch.Tensor | None = None, log_softmax: bool = False, acoustic_model=None) -> list[dict]:
         """Align transcript to audio -> [{'word', 'start', 'end'}] in seconds.
 
         ``emission`` [num_frames, num_classes]: the acoustic model's log-probabilities (or its logits, with ``log_softmax=True``)
-        over ``LABELS``; with it ``audio`` is not read and no acoustic model is needed."""
+        over ``LABELS``; with it ``audio`` is not read and no acoustic model is needed.
+        ``acoustic_model``: a ``wav2vec2.Wav2Vec2CtcMI355X`` that computes the emissions of ``audio`` (16 kHz: resampling stays the
+        caller's job) on the device instead of torchaudio's bundle; ignored when ``emission`` is given."""
+        if emission is None and acoustic_model is not None:
+            if sample_rate != SAMPLE_RATE:
+                raise ValueError(f"acoustic_model takes {SAMPLE_RATE} Hz audio, got sample_rate={sample_rate}: resample first")
+            return cls.align_audio_batch([audio], [text], acoustic_model)[0]
         if emission is None:
             emission, dictionary, frame_duration = cls._emission_of(audio, sample_rate)
         else:
             dictionary, frame_duration = cls._dict(), FRAME_STRIDE / SAMPLE_RATE
         return cls.align_batch([emission], [text], log_softmax=log_softmax, _dictionary=dictionary, _frame_duration=frame_duration)[0]
+
+    @classmethod
+    def align_audio_batch(cls, audios: Sequence, texts: Sequence[str], acoustic_model, *, blank_id: int = 0) -> list[list[dict]]:
+        """Waveforms -> words for a batch: ``acoustic_model`` (``wav2vec2.Wav2Vec2CtcMI355X``) turns the 16 kHz clips ``audios``
+        (1-D arrays or tensors of any lengths >= 400 samples) into emissions in ONE call, and the trellis kernel reads them where
+        they are: the emissions never visit the host.  Same words as ``align`` per clip."""
+        if len(audios) != len(texts):
+            raise ValueError(f"{len(audios)} clips but {len(texts)} texts")
+        dictionary = cls._dict()
+        out: list[list[dict]] = [[] for _ in texts]
+        if not len(texts):
+            return out
+        if len(texts) > ALIGN_LIMITS["clips"]:
+            raise ValueError(f"{len(texts)} clips: the alignment kernel takes at most {ALIGN_LIMITS['clips']} clips per launch")
+        tokens = [_tokenize(t, dictionary) for t in texts]
+        em, Ts = acoustic_model(list(audios))
+        for n, tk in enumerate(tokens):
+            _check_clip(em[:Ts[n]], tk, blank_id)
+        if not any(tokens):
+            return out
+        frames, _, status, _ = _launch_flat(em, Ts, tokens, blank_id)
+        for n, tk in enumerate(tokens):
+            if tk:
+                spans = _spans(tk, frames[n], status[n] == 1, Ts[n])
+                out[n] = _group_words(texts[n], spans, dictionary, FRAME_STRIDE / SAMPLE_RATE, cls.START_OFFSET, cls.END_OFFSET)
+        return out
 
     @classmethod
     def align_batch(cls, emissions: Sequence[torch.Tensor], texts: Sequence[str], *, log_softmax: bool = False, blank_id: int = 0,

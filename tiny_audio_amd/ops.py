@@ -650,3 +650,51 @@ def token_scores(logits, chosen, V, top_k=0):
     check(lib().ta_token_scores_f32(ptr(logits), ld, V, B, ptr(chosen), None, None, 1, top_k, ptr(logprob), ptr(entropy),
                                     ptr(top_ids) if top_k else None, ptr(top_lp) if top_k else None, stream()), "ta_token_scores_f32")
     return logprob, entropy, top_ids, top_lp
+
+
+# ----------------------------------------------------------------------------- wav2vec2 acoustic model (csrc/wav2vec2.hip)
+def w2v_conv0_gn_gelu(wav, lens, w, gn_w, gn_b, eps=1e-5, out=None, out_rpb=None):
+    """ta_w2v_conv0_gn_gelu: conv layer 0 (k 10, stride 5) + per-channel GroupNorm over each clip's own frames + exact GELU.
+    ``wav`` f32 [B, Ls], ``lens`` int32 [B] on the device, ``w`` f32 [C, 10] -> bf16 [B, out_rpb, C] time-major; clip b's rows
+    t >= (lens[b] - 10) // 5 + 1 are not written (``out``: a tensor to write into)."""
+    _req(wav, F32), _req(w, F32), _req(gn_w, F32), _req(gn_b, F32)
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.device == wav.device
+    B, Ls = wav.shape
+    Cd = w.shape[0]
+    assert w.shape == (Cd, 10) and gn_w.shape == (Cd,) and gn_b.shape == (Cd,) and lens.shape == (B,)
+    T0 = (Ls - 10) // 5 + 1
+    rpb = T0 if out_rpb is None else int(out_rpb)
+    if out is None:
+        out = torch.empty((B, rpb, Cd), device=wav.device, dtype=BF16)
+    assert out.dtype == BF16 and out.is_contiguous() and out.numel() >= B * rpb * Cd
+    n = lib().ta_w2v_conv0_ws_bytes(B, Ls, Cd)
+    ws = torch.empty(max(n, 8), device=wav.device, dtype=torch.uint8)
+    check(lib().ta_w2v_conv0_gn_gelu(ptr(wav), ptr(lens), B, Ls, ptr(w), ptr(gn_w), ptr(gn_b), Cd, float(eps), ptr(out), rpb, ptr(ws),
+                                     ws.numel(), stream()), "ta_w2v_conv0_gn_gelu")
+    return out
+
+
+def w2v_pos_conv(x, wp, bias, cu_rows, max_rows, out=None):
+    """ta_w2v_pos_conv: y = x + gelu(grouped positional conv(x) + bias) per clip.  ``x`` bf16 or f32 [rows, H] (the stream's dtype),
+    ``wp`` the packed bf16 image (``wav2vec2.pack_pos_conv``), ``cu_rows`` int32 [B + 1] on the device -> y like x."""
+    assert x.dtype in (BF16, F32)
+    _req(x), _req(wp, BF16), _req(bias, F32)
+    assert cu_rows.dtype == torch.int32 and cu_rows.is_contiguous() and cu_rows.device == x.device
+    H = x.shape[1]
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == x.dtype and out.shape == x.shape and out.is_contiguous() and out.data_ptr() != x.data_ptr()
+    check(lib().ta_w2v_pos_conv(ptr(x), int(x.dtype == F32), ptr(wp), ptr(bias), ptr(out), ptr(cu_rows), cu_rows.numel() - 1,
+                                int(max_rows), H, stream()), "ta_w2v_pos_conv")
+    return out
+
+
+def w2v_head_logsoftmax(logits, bias, n_classes, out=None):
+    """ta_w2v_head_logsoftmax: log_softmax(logits[:, :n_classes] + bias) -> f32 [rows, n_classes]; logits f32 [rows, ld]."""
+    _req(logits, F32), _req(bias, F32)
+    rows, ld = logits.shape
+    if out is None:
+        out = torch.empty((rows, int(n_classes)), device=logits.device, dtype=F32)
+    assert out.dtype == F32 and out.is_contiguous() and out.numel() >= rows * int(n_classes)
+    check(lib().ta_w2v_head_logsoftmax(ptr(logits), ld, ptr(bias), int(n_classes), ptr(out), rows, stream()), "ta_w2v_head_logsoftmax")
+    return out

@@ -7,6 +7,7 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
+    ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
     ta355::token_scores        compute_transition_scores on one step's processed logits (TF:generation/utils.py); the reference
                                asks HF for no scores (tiny_audio/asr_modeling.py:631-637)
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
@@ -209,6 +210,21 @@ def _(input_features, frame_keep, handle, return_f32):
     enc = module_of(handle)
     B, _, T = input_features.shape
     return input_features.new_empty((B, enc.output_length(T), enc.config.hidden_size), dtype=F32 if return_f32 else BF16)
+
+
+# ============================================================================ wav2vec2 acoustic model
+@torch.library.custom_op("ta355::wav2vec2_emissions", mutates_args=())
+def wav2vec2_emissions(waveforms: Tensor, lengths: List[int], handle: int) -> Tensor:
+    """Frozen wav2vec2 CTC model (``Wav2Vec2CtcMI355X``): f32 [B, Ls] 16 kHz waveforms, clip b = its first ``lengths[b]`` samples
+    (400 <= length <= Ls) -> log-softmax emissions f32 [sum T_b, n_classes], T_b = (lengths[b] - 400) // 320 + 1, on the device in
+    the layout ``ctc_align`` takes.  Replaces the torchaudio forward of tiny_audio/alignment.py:206-211.  No autograd."""
+    return module_of(handle)._forward_impl(waveforms, lengths)
+
+
+@wav2vec2_emissions.register_fake
+def _(waveforms, lengths, handle):
+    from .wav2vec2 import frames_of
+    return waveforms.new_empty((sum(frames_of(n) for n in lengths), module_of(handle).config.n_classes), dtype=F32)
 
 
 # ============================================================================ MLP projector
@@ -654,4 +670,4 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
              "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
-             "token_scores")
+             "token_scores", "wav2vec2_emissions")
