@@ -873,6 +873,106 @@ int ta_w2v_pos_conv(const void* x, int x_f32, const void* wp, const float* bias,
 int ta_w2v_head_logsoftmax(const float* logits, long ld, const float* bias, int n_classes, float* out, int rows,
                            hipStream_t st);
 
+/* ---- frozen ECAPA-TDNN speaker-embedding model: the hot path of speaker diarization (tiny_audio_amd/csrc/ecapa.hip).  Replaces the
+ * loop of the reference's LocalSpeakerDiarizer._extract_embeddings, which reflect-pads every 0.75 s window and pushes it through
+ * SpeechBrain's spkrec-ecapa-voxceleb encode_batch ONE WINDOW PER CALL (tiny_audio/diarization.py:457-517; the call itself :490-502).
+ * Arithmetic: the published ECAPA-TDNN at that checkpoint's hyper-parameters behind SpeechBrain's Fbank (n_fft 400, hop 160, Hamming,
+ * 80 mel, top_db 80) and sentence-mean normalisation; eval-mode BatchNorm folded to (scale, shift) BEHIND each ReLU.  Every window is
+ * processed as if alone.  Contract: DESIGN.md section 3, "Speaker diarization", defined by tests/ecapa_ref.py. */
+#define TA_ECAPA_N_MELS 80
+#define TA_ECAPA_FEAT_STRIDE 128   /* channel stride of the bf16 feature slab (80 mel + 48 zeros): block0's K = 5 * 128 = 640 */
+#define TA_ECAPA_SCALE 8           /* Res2Net sub-bands */
+#define TA_ECAPA_MIN_T 5           /* frames per window, T = window_samples / 160 + 1: the reflect padding of 4 needs 5 */
+#define TA_ECAPA_MAX_T 512
+#define TA_ECAPA_MAX_DILATION 4
+#define TA_ECAPA_MAX_CHANNELS 1024 /* C: a multiple of 128 (sub-band width C / 8 a multiple of 16 up to 128) */
+#define TA_ECAPA_MAX_SE 256
+#define TA_ECAPA_MAX_ATTN 256      /* attention channels: a multiple of 64 */
+#define TA_ECAPA_MAX_EMB 1024      /* embedding width: a multiple of 4 */
+typedef struct {
+  const void* w1;              /* bf16 [C, C]: tdnn1.conv */
+  const float *b1, *bn1_s, *bn1_t;      /* [C]: its bias, and tdnn1.norm folded: scale = g / sqrt(var + eps), shift = b - mean * scale */
+  const void* res_w;           /* bf16 [7][C/8][Kp], Kp = 3 C/8 rounded up to 32: res2net conv m, output channel co, column = tap * C/8 + cin,
+                                  columns >= 3 C/8 ZERO */
+  const float *res_b, *res_s, *res_t;   /* [7 * C/8]: bias, folded norm of res2net conv m at m * C/8 */
+  const void* w2;              /* bf16 [C, C]: tdnn2.conv */
+  const float *b2, *bn2_s, *bn2_t;
+  const float *se_w1t, *se_b1; /* f32 [C, se] (se_block.conv1 weight TRANSPOSED), [se] */
+  const float *se_w2t, *se_b2; /* f32 [se, C] (se_block.conv2 weight TRANSPOSED), [C] */
+  int dilation;                /* 1 .. TA_ECAPA_MAX_DILATION */
+} ta_ecapa_block;
+typedef struct {
+  int channels, se_channels, attn_channels, emb_dim;
+  const float* fb_window;      /* f32 [400] periodic Hamming */
+  const float* fb_twiddle;     /* f32 [400][2] = cos(2 pi j / 400), -sin(2 pi j / 400) */
+  const float* fb_mel;         /* f32 [201, 80] triangular filters, bin-major */
+  const int* fb_mel_range;     /* int [80][2]: first / end bin of every filter's non-zero taps */
+  const void* w0;              /* bf16 [C, 5 * TA_ECAPA_FEAT_STRIDE]: blocks.0.conv, column = tap * stride + mel, columns of mel >= 80 ZERO */
+  const float *b0, *bn0_s, *bn0_t;
+  ta_ecapa_block blocks[3];
+  const void* mfa_w;           /* bf16 [3C, 3C] */
+  const float *mfa_b, *mfa_s, *mfa_t;
+  const void* att_wh;          /* bf16 [A, 3C]: asp.tdnn.conv columns 0 .. 3C (the frames' share) */
+  const void* att_wms;         /* bf16 [A, 6C]: its columns 3C .. 9C (the window mean and std's share) */
+  const float *att_b, *att_s, *att_t;   /* [A] */
+  const void* att_conv_w;      /* bf16 [3C, A]: asp.conv */
+  const float* att_conv_b;     /* [3C] */
+  const float *aspbn_s, *aspbn_t;       /* [6C]: asp_bn folded */
+  const void* fc_w;            /* bf16 [D, 6C] */
+  const float* fc_b;           /* [D] */
+} ta_ecapa_weights;
+
+/* audio f32 [n_audio] (one shared buffer, uploaded once); window i = samples starts[i] .. starts[i] + lens[i], extended on the right
+ * to window_samples by reflection while it is read (sample len + j = sample len - 2 - j: numpy's mode="reflect",
+ * tiny_audio/diarization.py:484-488) -> emb f32 [N, emb_dim].  starts_host / lens_host: HOST int [N] (checked: 1 <= len <=
+ * window_samples, window_samples - len <= len - 1 as np.pad demands, start + len <= n_audio; else TA_ERR_ARG); starts_dev / lens_dev:
+ * the same on the DEVICE.  T = window_samples / 160 + 1 frames, TA_ECAPA_MIN_T <= T <= TA_ECAPA_MAX_T.  The windows go through in
+ * chunks of chunk_windows; ws: ta_ecapa_workspace_bytes(w, min(N, chunk_windows), T) bytes, no initial contents required.  Window i's
+ * embedding does not depend on the other windows or on the chunking.  Kernel launches on st only. */
+long ta_ecapa_workspace_bytes(const ta_ecapa_weights* w, int n_windows, int T);
+int ta_ecapa_forward(const ta_ecapa_weights* w, const float* audio, long n_audio, const int* starts_host, const int* lens_host,
+                     const int* starts_dev, const int* lens_dev, int N, int window_samples, int chunk_windows, float* emb,
+                     void* ws, long ws_bytes, hipStream_t st);
+
+/* Its new kernels, exported for the tests.
+ * Filter bank + sentence-mean normalisation (replaces the compute_features / mean_var_norm front of encode_batch,
+ * tiny_audio/diarization.py:490-502): feat f32 [N, T, 80] = 10 log10(max(mel power, 1e-10)) floored at the window's own maximum
+ * - 80 dB, minus each mel bin's mean over the T frames; slab bf16 [N, T + 4, TA_ECAPA_FEAT_STRIDE]: the same values rounded, frames at
+ * rows 2 .. T + 1, rows 1, 0 = frames 1, 2 and rows T + 2, T + 3 = frames T - 2, T - 3 (block0's reflect padding), channels >= 80
+ * zero.  The starts / lens are trusted (ta_ecapa_forward checks its host copies); a sample outside the audio buffer reads as 0. */
+int ta_ecapa_fbank(const float* audio, long n_audio, const int* starts_dev, const int* lens_dev, int N, int window_samples,
+                   const float* fb_window, const float* fb_twiddle, const float* fb_mel, const int* fb_mel_range,
+                   float* feat, void* slab_bf16, hipStream_t st);
+/* The Res2Net chain of one SERes2NetBlock on MFMA (replaces Res2NetBlock.forward inside encode_batch, tiny_audio/diarization.py:490-502).
+ * z1 bf16: tdnn1's PRE-activation rows, window n's frame t at row n * z_rpw + t, ldz elements apart; y bf16 likewise (y_rpw, ldy):
+ * y[:, 0:w] = x_0, y[:, i w:(i+1) w] = TDNN_{i-1}(x_i + y_{i-1}) with x_i = relu(z1_i) * bn1_s + bn1_t and the operand x_i + y_{i-1}
+ * rounded to bf16 once.  Rows t >= T of a window and columns >= 8 w are neither read nor written.  w a multiple of 16 up to 128,
+ * dilation 1 .. TA_ECAPA_MAX_DILATION, T > dilation; ldz, ldy multiples of 8; z1, y 16-byte aligned. */
+int ta_ecapa_res2net(const void* z1, long ldz, long z_rpw, const float* bn1_s, const float* bn1_t, const void* res_w,
+                     const float* res_b, const float* res_s, const float* res_t, void* y, long ldy, long y_rpw, int N, int T,
+                     int w, int dilation, hipStream_t st);
+/* out bf16 [N T, Cw] = relu(z) * scale + shift from a GEMM's pre-activation bf16 output (the ReLU and BatchNorm of a TDNNBlock,
+ * tiny_audio/diarization.py:490-502).  With stats_f32 and / or stats_bf16 (else NULL): [N, 2 Cw] = each window's mean over time and
+ * sqrt(max(biased variance, 1e-12)) of the rounded output, two passes (the global statistics of attentive pooling). */
+int ta_ecapa_relu_bn(const void* z, const float* scale, const float* shift, void* out, float* stats_f32, void* stats_bf16,
+                     int N, int T, int Cw, hipStream_t st);
+/* out[:, 0:Cw] (rows ldout apart) = (relu(z2) * bn2_s + bn2_t) * gate + residual (rows ldres apart), gate = sigmoid(W2 relu(W1 m + b1)
+ * + b2) with m the window's mean over time of relu(z2) * bn2_s + bn2_t: the SEBlock and the residual add of SERes2NetBlock.forward.
+ * ws: f32 [ta_ecapa_se_ws_floats(N, Cw)]; on return its first N Cw floats hold m, the next N Cw the gate. */
+long ta_ecapa_se_ws_floats(int N, int Cw);
+int ta_ecapa_se_residual(const void* z2, const float* bn2_s, const float* bn2_t, const float* se_w1t, const float* se_b1,
+                         const float* se_w2t, const float* se_b2, const void* residual, long ldres, void* out, long ldout,
+                         int N, int T, int Cw, int se, float* ws, hipStream_t st);
+/* out bf16 [N T, A] = tanh(relu(g + per_window[window]) * scale + shift): asp.tdnn's activation with the window-constant share of its
+ * convolution added (AttentiveStatisticsPooling.forward).  g f32 [N T, A], per_window f32 [N, A]. */
+int ta_ecapa_attn_act(const float* g, const float* per_window, const float* scale, const float* shift, void* out, int N, int T,
+                      int A, hipStream_t st);
+/* Attentive statistics pooling: a = softmax over the window's T frames of logits f32 [N T, Cw] per channel; out bf16 [N, 2 Cw] =
+ * ([sum a h | sqrt(max(sum a (h - mean)^2, 1e-12))]) * aspbn_s + aspbn_t, h bf16 [N T, Cw].  attn_w f32 [N T, Cw] / pooled_f32
+ * [N, 2 Cw] (before asp_bn): optional outputs, or NULL. */
+int ta_ecapa_asp_pool(const float* logits, const void* h, const float* aspbn_s, const float* aspbn_t, void* out, float* attn_w,
+                      float* pooled_f32, int N, int T, int Cw, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

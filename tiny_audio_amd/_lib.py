@@ -22,7 +22,7 @@ HEADER = os.path.join(ROOT, "include", "ta355.h")
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "libta355.so")
 SOURCES = ["gemm.hip", "gemm_tn.hip", "norm.hip", "attention.hip", "attention_enc.hip", "qkv_post.hip", "elementwise.hip", "loss.hip",
-           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "decode_fused.hip", "augment.hip", "align.hip", "wav2vec2.hip", "api.hip"]
+           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "decode_fused.hip", "augment.hip", "align.hip", "wav2vec2.hip", "ecapa.hip", "api.hip"]
 
 
 class Ta355Error(RuntimeError):
@@ -60,6 +60,21 @@ class Wav2Vec2Weights(C.Structure):
                 ("fp_ln_w", C.c_void_p), ("fp_ln_b", C.c_void_p), ("fp_w", C.c_void_p), ("fp_b", C.c_void_p),
                 ("pos_w", C.c_void_p), ("pos_b", C.c_void_p), ("enc_ln_w", C.c_void_p), ("enc_ln_b", C.c_void_p),
                 ("layers", C.POINTER(EncLayer)), ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("res_f32", C.c_int)]
+
+
+class EcapaBlock(C.Structure):
+    """ta_ecapa_block (include/ta355.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "bn1_s", "bn1_t", "res_w", "res_b", "res_s", "res_t", "w2", "b2", "bn2_s", "bn2_t",
+                                          "se_w1t", "se_b1", "se_w2t", "se_b2")] + [("dilation", C.c_int)]
+
+
+class EcapaWeights(C.Structure):
+    """ta_ecapa_weights (include/ta355.h)."""
+    _fields_ = ([("channels", C.c_int), ("se_channels", C.c_int), ("attn_channels", C.c_int), ("emb_dim", C.c_int)] +
+                [(n, C.c_void_p) for n in ("fb_window", "fb_twiddle", "fb_mel", "fb_mel_range", "w0", "b0", "bn0_s", "bn0_t")] +
+                [("blocks", EcapaBlock * 3)] +
+                [(n, C.c_void_p) for n in ("mfa_w", "mfa_b", "mfa_s", "mfa_t", "att_wh", "att_wms", "att_b", "att_s", "att_t",
+                                           "att_conv_w", "att_conv_b", "aspbn_s", "aspbn_t", "fc_w", "fc_b")])
 
 
 class MlpWeights(C.Structure):

@@ -698,3 +698,80 @@ def w2v_head_logsoftmax(logits, bias, n_classes, out=None):
     assert out.dtype == F32 and out.is_contiguous() and out.numel() >= rows * int(n_classes)
     check(lib().ta_w2v_head_logsoftmax(ptr(logits), ld, ptr(bias), int(n_classes), ptr(out), rows, stream()), "ta_w2v_head_logsoftmax")
     return out
+
+
+# ----------------------------------------------------------------------------- ECAPA-TDNN kernels (csrc/ecapa.hip)
+def ecapa_fbank(audio, starts, lens, window_samples, tables):
+    """ta_ecapa_fbank: ``audio`` f32 [n], ``starts`` / ``lens`` int32 [N] on the device, ``tables`` = (window, twiddle, mel, ranges)
+    device tensors (``ecapa.fbank_tables``) -> (feat f32 [N, T, 80], slab bf16 [N, T + 4, 128]), T = window_samples // 160 + 1."""
+    _req(audio, F32)
+    win, tw, mel, rng = tables
+    _req(win, F32), _req(tw, F32), _req(mel, F32), _req(rng, torch.int32), _req(starts, torch.int32), _req(lens, torch.int32)
+    N, T = starts.numel(), int(window_samples) // 160 + 1
+    feat = torch.empty((N, T, 80), device=audio.device, dtype=F32)
+    slab = torch.empty((N, T + 4, 128), device=audio.device, dtype=BF16)
+    check(lib().ta_ecapa_fbank(ptr(audio), audio.numel(), ptr(starts), ptr(lens), N, int(window_samples), ptr(win), ptr(tw), ptr(mel),
+                               ptr(rng), ptr(feat), ptr(slab), stream()), "ta_ecapa_fbank")
+    return feat, slab
+
+
+def ecapa_res2net(z1, bn1_s, bn1_t, res_w, res_b, res_s, res_t, T, w, dilation, out):
+    """ta_ecapa_res2net: ``z1`` bf16 [N, z_rpw, ldz] (tdnn1's pre-activation rows, window n's frames at rows 0 .. T - 1 of slab n),
+    ``res_w`` the packed image (``ecapa.pack_res2net``) -> ``out`` bf16 [N, y_rpw, ldy], columns 0 .. 8 w of rows 0 .. T - 1 written."""
+    _req(z1, BF16), _req(out, BF16), _req(res_w, BF16)
+    for t in (bn1_s, bn1_t, res_b, res_s, res_t):
+        _req(t, F32)
+    N, z_rpw, ldz = z1.shape
+    assert out.shape[0] == N
+    check(lib().ta_ecapa_res2net(ptr(z1), ldz, z_rpw, ptr(bn1_s), ptr(bn1_t), ptr(res_w), ptr(res_b), ptr(res_s), ptr(res_t), ptr(out),
+                                 out.shape[2], out.shape[1], N, int(T), int(w), int(dilation), stream()), "ta_ecapa_res2net")
+    return out
+
+
+def ecapa_relu_bn(z, scale, shift, N, T, want_stats=False):
+    """ta_ecapa_relu_bn: ``z`` bf16 [N T, Cw] -> bf16 [N T, Cw] (and with ``want_stats`` the f32 and bf16 [N, 2 Cw] mean | std)."""
+    _req(z, BF16), _req(scale, F32), _req(shift, F32)
+    Cw = z.shape[1]
+    out = torch.empty_like(z)
+    sf = torch.empty((N, 2 * Cw), device=z.device, dtype=F32) if want_stats else None
+    sb = torch.empty((N, 2 * Cw), device=z.device, dtype=BF16) if want_stats else None
+    check(lib().ta_ecapa_relu_bn(ptr(z), ptr(scale), ptr(shift), ptr(out), ptr(sf), ptr(sb), int(N), int(T), Cw, stream()), "ta_ecapa_relu_bn")
+    return (out, sf, sb) if want_stats else out
+
+
+def ecapa_se_residual(z2, bn2_s, bn2_t, se_w1t, se_b1, se_w2t, se_b2, residual, out, col0, N, T):
+    """ta_ecapa_se_residual: ``z2`` bf16 [N T, Cw], ``residual`` bf16 [N T, ldres] (its first Cw columns) -> columns
+    col0 .. col0 + Cw of ``out`` bf16 [N T, ldout]; -> (out, window means f32 [N, Cw], gates f32 [N, Cw])."""
+    _req(z2, BF16), _req(residual, BF16), _req(out, BF16)
+    for t in (bn2_s, bn2_t, se_w1t, se_b1, se_w2t, se_b2):
+        _req(t, F32)
+    Cw, se = z2.shape[1], se_b1.numel()
+    assert col0 % 2 == 0 and col0 + Cw <= out.shape[1] and se_w1t.shape == (Cw, se) and se_w2t.shape == (se, Cw)
+    ws = torch.empty(max(lib().ta_ecapa_se_ws_floats(int(N), Cw), 1), device=z2.device, dtype=F32)
+    check(lib().ta_ecapa_se_residual(ptr(z2), ptr(bn2_s), ptr(bn2_t), ptr(se_w1t), ptr(se_b1), ptr(se_w2t), ptr(se_b2), ptr(residual),
+                                     residual.shape[1], C.c_void_p(out.data_ptr() + 2 * col0), out.shape[1], int(N), int(T), Cw, se, ptr(ws),
+                                     stream()), "ta_ecapa_se_residual")
+    return out, ws[:N * Cw].reshape(N, Cw), ws[N * Cw:2 * N * Cw].reshape(N, Cw)
+
+
+def ecapa_attn_act(g, per_window, scale, shift, N, T):
+    """ta_ecapa_attn_act: ``g`` f32 [N T, A], ``per_window`` f32 [N, A] -> bf16 [N T, A]."""
+    for t in (g, per_window, scale, shift):
+        _req(t, F32)
+    out = torch.empty(g.shape, device=g.device, dtype=BF16)
+    check(lib().ta_ecapa_attn_act(ptr(g), ptr(per_window), ptr(scale), ptr(shift), ptr(out), int(N), int(T), g.shape[1], stream()),
+          "ta_ecapa_attn_act")
+    return out
+
+
+def ecapa_asp_pool(logits, h, aspbn_s, aspbn_t, N, T):
+    """ta_ecapa_asp_pool: ``logits`` f32 [N T, Cw], ``h`` bf16 [N T, Cw] -> (out bf16 [N, 2 Cw], attention weights f32 [N T, Cw],
+    pooled f32 [N, 2 Cw] before asp_bn)."""
+    _req(logits, F32), _req(h, BF16), _req(aspbn_s, F32), _req(aspbn_t, F32)
+    Cw = logits.shape[1]
+    out = torch.empty((N, 2 * Cw), device=h.device, dtype=BF16)
+    aw = torch.empty_like(logits)
+    pooled = torch.empty((N, 2 * Cw), device=h.device, dtype=F32)
+    check(lib().ta_ecapa_asp_pool(ptr(logits), ptr(h), ptr(aspbn_s), ptr(aspbn_t), ptr(out), ptr(aw), ptr(pooled), int(N), int(T), Cw,
+                                  stream()), "ta_ecapa_asp_pool")
+    return out, aw, pooled

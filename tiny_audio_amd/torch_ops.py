@@ -8,6 +8,7 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
+    ta355::ecapa_embeddings    SpeechBrain ECAPA-TDNN encode_batch, one call per window   tiny_audio/diarization.py:457-517
     ta355::token_scores        compute_transition_scores on one step's processed logits (TF:generation/utils.py); the reference
                                asks HF for no scores (tiny_audio/asr_modeling.py:631-637)
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
@@ -225,6 +226,20 @@ def wav2vec2_emissions(waveforms: Tensor, lengths: List[int], handle: int) -> Te
 def _(waveforms, lengths, handle):
     from .wav2vec2 import frames_of
     return waveforms.new_empty((sum(frames_of(n) for n in lengths), module_of(handle).config.n_classes), dtype=F32)
+
+
+# ============================================================================ ECAPA-TDNN speaker embeddings
+@torch.library.custom_op("ta355::ecapa_embeddings", mutates_args=())
+def ecapa_embeddings(audio: Tensor, starts: List[int], lengths: List[int], window_samples: int, handle: int) -> Tensor:
+    """Frozen ECAPA-TDNN (``EcapaTdnnMI355X``): f32 [n] 16 kHz audio, window i = its samples ``starts[i] .. starts[i] + lengths[i]``
+    reflect-padded on the right to ``window_samples`` -> embeddings f32 [N, lin_neurons] on the device.  Replaces the
+    one-window-per-call SpeechBrain loop of tiny_audio/diarization.py:457-517.  No autograd."""
+    return module_of(handle)._embed_impl(audio, starts, lengths, window_samples)
+
+
+@ecapa_embeddings.register_fake
+def _(audio, starts, lengths, window_samples, handle):
+    return audio.new_empty((len(starts), module_of(handle).config.lin_neurons), dtype=F32)
 
 
 # ============================================================================ MLP projector
@@ -670,4 +685,4 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
              "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
-             "token_scores", "wav2vec2_emissions")
+             "token_scores", "wav2vec2_emissions", "ecapa_embeddings")
