@@ -973,6 +973,43 @@ int ta_ecapa_attn_act(const float* g, const float* per_window, const float* scal
 int ta_ecapa_asp_pool(const float* logits, const void* h, const float* aspbn_s, const float* aspbn_t, void* out, float* attn_w,
                       float* pooled_f32, int N, int T, int Cw, hipStream_t st);
 
+/* ---- speaker clustering: the spectral embedding behind the window embeddings (tiny_audio_amd/csrc/cluster.hip).  Replaces the dense
+ * float64 host chain of the reference's SpectralCluster -- cosine_similarity, argpartition pruning, symmetrisation, the Laplacian and
+ * scipy.linalg.eigh of the whole [N, N] matrix (tiny_audio/diarization.py:49-106) -- by f32 kernels and a block Lanczos iteration that
+ * tiny_audio_amd/spectral.py drives over them.  Everything is f32 in and out, row-major with explicit leading dimensions (in elements);
+ * no floating-point atomics: equal inputs give equal bits.  Contract: DESIGN.md section 3, "Spectral clustering", defined by
+ * tests/cluster_ref.py. */
+#define TA_SPK_MIN_N 6        /* fewer rows are one speaker on the host (SpeakerClusterer) */
+#define TA_SPK_MAX_N 32768    /* a row of the affinity has to fit in LDS: 82 minutes of pure speech at STEP_SIZE 0.15 */
+#define TA_SPK_MAX_D 256      /* embedding width (the checkpoint's is 192) */
+#define TA_SPK_MAX_P 32       /* columns of a block the Laplacian is applied to, of a panel that is updated or combined */
+#define TA_SPK_MAX_COLS 1024  /* columns of the Krylov basis */
+/* E [N, D] -> W [N, N] (leading dimension ldw >= N) and deg [N]: get_sim_mat, p_pruning, 0.5 (P + P^T), fill_diagonal(0) and the row
+ * sums of the Laplacian (tiny_audio/diarization.py:49-86).  phases is a mask, 7 = all of it in order:
+ *   1  rows of E normalised (a zero row stays zero), S = E^ E^T with f32 accumulation; S[i, j] and S[j, i] are bitwise equal
+ *   2  every row of W keeps its `keep` largest entries (1 <= keep <= N; the diagonal counts), the others become 0; entries equal to the
+ *      keep-th largest are kept lowest column first until exactly `keep` survive.  kept_count int [N] (or NULL): the survivors per row
+ *   4  W = 0.5 (W + W^T), diagonal 0, deg[i] = sum_j W[i, j] in a fixed order
+ * ws: f32 [ta_spk_affinity_ws_floats(N, D)], 16-byte aligned, needed by phase 1 only.  Columns N .. ldw of W are never touched. */
+long ta_spk_affinity_ws_floats(int N, int D);
+int ta_spk_affinity_f32(const float* E, int N, int D, int keep, float* W, long ldw, float* deg, int* kept_count, float* ws, int phases,
+                        hipStream_t st);
+/* Y [N, p] = diag(deg) X - W X, the unnormalised Laplacian (tiny_audio/diarization.py:87-89) applied to a block X [N, p],
+ * 1 <= p <= TA_SPK_MAX_P, without forming it: one pass over W.  ws: f32 [ta_spk_lapmul_ws_floats(N, p)].  X != Y.  W is read 16 bytes
+ * per lane when ldw is a multiple of 4 and W is 16-byte aligned, 4 bytes otherwise. */
+long ta_spk_lapmul_ws_floats(int N, int p);
+int ta_spk_laplacian_matmul_f32(const float* W, long ldw, const float* deg, const float* X, long ldx, float* Y, long ldy, int N, int p,
+                                float* ws, hipStream_t st);
+/* Panel algebra of the Krylov basis that replaces scipy.linalg.eigh (tiny_audio/diarization.py:91-106).  C [a, b] = A^T B for
+ * A [N, a], B [N, b], a, b <= TA_SPK_MAX_COLS; ws: f32 [ta_spk_gram_ws_floats(N, a, b)]. */
+long ta_spk_gram_ws_floats(int N, int a, int b);
+int ta_spk_panel_gram_f32(const float* A, long lda, int a, const float* B, long ldb, int b, int N, float* C, long ldc, float* ws,
+                          hipStream_t st);
+/* B [N, b] -= A [N, a] C [a, b], b <= TA_SPK_MAX_P, summed in increasing k (one Gram-Schmidt sweep against the basis). */
+int ta_spk_panel_update_f32(float* B, long ldb, int b, const float* A, long lda, int a, const float* C, long ldc, int N, hipStream_t st);
+/* Y [N, m] = V [N, c] Z [c, m], m <= TA_SPK_MAX_P (Ritz vectors; a block times the inverse of its Cholesky factor).  Y != V. */
+int ta_spk_panel_combine_f32(const float* V, long ldv, int c, const float* Z, long ldz, int m, float* Y, long ldy, int N, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """tiny_audio_amd -- the MI355X-native hot path of tiny-audio.  Submodules are imported where they are used; the names below (the
 speaker-diarization entry points) resolve lazily so that importing the package stays free of torch and of the HIP library."""
 _LAZY = {"EcapaConfig": "ecapa", "EcapaTdnnMI355X": "ecapa", "SpectralCluster": "diarization", "SpeakerClusterer": "diarization",
-         "LocalSpeakerDiarizer": "diarization", "SpeakerDiarizer": "diarization"}
+         "LocalSpeakerDiarizer": "diarization", "SpeakerDiarizer": "diarization", "DeviceSpectralCluster": "spectral"}
 __all__ = sorted(_LAZY)
 
 

@@ -6,8 +6,11 @@ tiny_audio/asr_pipeline.py:133-152): the same class names, class constants, argu
 differs is the hot path.  The reference pushes every 0.75 s window through SpeechBrain's ``encode_batch`` one window per call
 (tiny_audio/diarization.py:490-502); with ``speaker_model=`` (an ``EcapaTdnnMI355X``) every window of every segment goes through ONE
 ``embed_windows`` call on the device -- the audio is uploaded once and the windows are cut and reflect-padded by the feature kernel.
-Everything behind the ``[N, 192]`` embeddings (spectral clustering, voting, merging) is O(N) host arithmetic and stays in numpy,
-scipy and scikit-learn exactly as the reference has it.
+Voting and merging behind the ``[N, 192]`` embeddings are O(N) host arithmetic and stay in numpy, scipy and scikit-learn exactly as the
+reference has them.  Spectral clustering is not: ``SpectralCluster`` restates the reference's dense float64 affinity, Laplacian and full
+``scipy.linalg.eigh`` -- O(N^2) memory and O(N^3) time, seconds at N = 4 000 windows (10 minutes of speech) and tens of minutes at an
+hour.  It stays the default; ``cluster_device=`` (``SpeakerClusterer(device=...)``) moves the affinity, the Laplacian and the few
+eigenpairs that are read onto the device (``tiny_audio_amd/spectral.py``) and leaves the eigengap rule, k-means and merging here.
 
 Third-party pieces that are not rebuilt: the VAD (``ten_vad``, a compiled library; pass ``speech_frames=`` or ``vad=`` to do without
 it), file reading and resampling (``librosa``), and -- only without ``speaker_model`` -- SpeechBrain.  Each raises ``ImportError``
@@ -77,13 +80,20 @@ class SpeakerClusterer:
     """Spectral clustering of speaker embeddings, then -- without an oracle count -- speakers whose centroids are closer than
     ``merge_thr`` in cosine are merged (tiny_audio/diarization.py:118-218)."""
 
-    def __init__(self, min_num_spks: int = 2, max_num_spks: int = 10, merge_thr: float = 0.90):
-        self.min_num_spks, self.max_num_spks, self.merge_thr = min_num_spks, max_num_spks, merge_thr
+    def __init__(self, min_num_spks: int = 2, max_num_spks: int = 10, merge_thr: float = 0.90, device=None):
+        """device: None -- the host ``SpectralCluster``, as in the reference; a torch device -- ``spectral.DeviceSpectralCluster`` on
+        it (which still hands small or undecided inputs to the host class; see its ``last_info``)."""
+        self.min_num_spks, self.max_num_spks, self.merge_thr, self.device = min_num_spks, max_num_spks, merge_thr, device
         self._spectral_cluster: SpectralCluster | None = None
 
     def _get_spectral_cluster(self) -> SpectralCluster:
         if self._spectral_cluster is None:
-            self._spectral_cluster = SpectralCluster(min_num_spks=self.min_num_spks, max_num_spks=self.max_num_spks)
+            if self.device is None:
+                self._spectral_cluster = SpectralCluster(min_num_spks=self.min_num_spks, max_num_spks=self.max_num_spks)
+            else:
+                from .spectral import DeviceSpectralCluster
+                self._spectral_cluster = DeviceSpectralCluster(min_num_spks=self.min_num_spks, max_num_spks=self.max_num_spks,
+                                                               device=self.device)
         return self._spectral_cluster
 
     def __call__(self, embeddings: np.ndarray, num_speakers: int | None = None) -> np.ndarray:
@@ -191,8 +201,10 @@ class LocalSpeakerDiarizer:
     # ------------------------------------------------------------------ the pipeline
     @classmethod
     def diarize(cls, audio, sample_rate: int = 16000, num_speakers: int | None = None, min_speakers: int = 2, max_speakers: int = 10,
-                *, speaker_model=None, speech_frames=None, vad=None, **_kwargs) -> list[dict]:
+                *, speaker_model=None, speech_frames=None, vad=None, cluster_device=None, **_kwargs) -> list[dict]:
         """audio: a waveform array or the path of an audio file -> ``[{"speaker": "SPEAKER_k", "start": s, "end": s}, ...]``.
+
+        cluster_device: a torch device for the spectral clustering (``SpeakerClusterer(device=...)``); None keeps it on the host.
 
         speaker_model: an ``EcapaTdnnMI355X``; every window of every segment goes through one ``embed_windows`` call.  Without it
             SpeechBrain runs through PyTorch one window per call, as in the reference.
@@ -213,7 +225,7 @@ class LocalSpeakerDiarizer:
         embeddings, window_segments = cls._extract_embeddings(audio, segments, sample_rate, speaker_model=speaker_model)
         if len(embeddings) == 0:
             return []
-        labels = SpeakerClusterer(min_num_spks=min_speakers, max_num_spks=max_speakers)(embeddings, num_speakers)
+        labels = SpeakerClusterer(min_num_spks=min_speakers, max_num_spks=max_speakers, device=cluster_device)(embeddings, num_speakers)
         return cls._postprocess_segments(window_segments, labels, total_duration, vad_frames)
 
     @classmethod
@@ -398,10 +410,11 @@ class SpeakerDiarizer:
 
     @classmethod
     def diarize(cls, audio, sample_rate: int = 16000, num_speakers: int | None = None, min_speakers: int | None = None,
-                max_speakers: int | None = None, *, speaker_model=None, speech_frames=None, vad=None, **_kwargs) -> list[dict]:
+                max_speakers: int | None = None, *, speaker_model=None, speech_frames=None, vad=None, cluster_device=None,
+                **_kwargs) -> list[dict]:
         return LocalSpeakerDiarizer.diarize(audio, sample_rate=sample_rate, num_speakers=num_speakers, min_speakers=min_speakers or 2,
                                             max_speakers=max_speakers or 10, speaker_model=speaker_model, speech_frames=speech_frames,
-                                            vad=vad)
+                                            vad=vad, cluster_device=cluster_device)
 
     @classmethod
     def assign_speakers_to_words(cls, words: list[dict], speaker_segments: list[dict]) -> list[dict]:

@@ -775,3 +775,93 @@ def ecapa_asp_pool(logits, h, aspbn_s, aspbn_t, N, T):
     check(lib().ta_ecapa_asp_pool(ptr(logits), ptr(h), ptr(aspbn_s), ptr(aspbn_t), ptr(out), ptr(aw), ptr(pooled), int(N), int(T), Cw,
                                   stream()), "ta_ecapa_asp_pool")
     return out, aw, pooled
+
+
+# ----------------------------------------------------------------------------- speaker clustering kernels (csrc/cluster.hip)
+SPK_MIN_N, SPK_MAX_N, SPK_MAX_D, SPK_MAX_P, SPK_MAX_COLS = 6, 32768, 256, 32, 1024
+
+
+def _mat(t):
+    """A 2-D f32 matrix with unit column stride (a column slice of a wider one is fine) -> its leading dimension."""
+    assert (t.is_cuda or _lib.DRY_RUN) and t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1], \
+        "ta355 spk ops need 2-D f32 CUDA(HIP) tensors with contiguous rows"
+    return t.stride(0)
+
+
+def _ws(n, like):
+    return torch.empty(max(int(n), 1), device=like.device, dtype=F32)
+
+
+def spk_keep(n: int, pval: float) -> int:
+    """Entries a row of the affinity keeps: the reference's ``int(max(pval, 6 / n) * n)``, at least 1 (tiny_audio/diarization.py:63-66)."""
+    return max(1, int(max(pval, 6.0 / n) * n))
+
+
+def spk_affinity(E, keep, *, out=None, deg=None, want_kept=False, phases=7):
+    """ta_spk_affinity_f32: ``E`` f32 [N, D] -> (W f32 [N, N]: pruned, symmetrised cosine affinity with a zero diagonal; deg f32 [N]: its
+    row sums; the survivors per row before symmetrisation int32 [N], or None).  ``out``: a [N, N] matrix (or column slice) to write;
+    by default its rows are padded to a multiple of 4 floats, which is what lets ``spk_laplacian_matmul`` read 16 bytes per lane.
+    ``phases``: 1 cosine, 2 pruning, 4 symmetrisation and degrees (each needs the ones before it to have run on ``out``)."""
+    _req(E, F32)
+    N, D = E.shape
+    if N > SPK_MAX_N:
+        raise ValueError(f"speaker clustering on the device takes at most {SPK_MAX_N} windows, got {N}")
+    if out is None:
+        out = torch.empty((N, (N + 3) // 4 * 4), device=E.device, dtype=F32)[:, :N]
+    ld = _mat(out)
+    assert out.shape == (N, N)
+    deg = torch.empty(N, device=E.device, dtype=F32) if deg is None else _req(deg, F32)
+    kept = torch.empty(N, device=E.device, dtype=torch.int32) if want_kept else None
+    ws = _ws(lib().ta_spk_affinity_ws_floats(N, D), E)
+    check(lib().ta_spk_affinity_f32(ptr(E), N, D, int(keep), ptr(out), ld, ptr(deg), ptr(kept), ptr(ws), int(phases), stream()),
+          "ta_spk_affinity_f32")
+    return out, deg, kept
+
+
+def spk_laplacian_matmul(W, deg, X, *, out=None):
+    """ta_spk_laplacian_matmul_f32: Y [N, p] = diag(deg) X - W X for ``X`` f32 [N, p <= 32]."""
+    ldw, ldx = _mat(W), _mat(X)
+    _req(deg, F32)
+    N, p = X.shape
+    assert W.shape == (N, N) and deg.numel() == N
+    out = torch.empty((N, p), device=X.device, dtype=F32) if out is None else out
+    ldy = _mat(out)
+    assert out.shape == (N, p)
+    ws = _ws(lib().ta_spk_lapmul_ws_floats(N, p), X)
+    check(lib().ta_spk_laplacian_matmul_f32(ptr(W), ldw, ptr(deg), ptr(X), ldx, ptr(out), ldy, N, p, ptr(ws), stream()),
+          "ta_spk_laplacian_matmul_f32")
+    return out
+
+
+def spk_panel_gram(A, B, *, out=None):
+    """ta_spk_panel_gram_f32: C [a, b] = A^T B for ``A`` [N, a], ``B`` [N, b]."""
+    lda, ldb = _mat(A), _mat(B)
+    (N, a), b = A.shape, B.shape[1]
+    assert B.shape[0] == N
+    out = torch.empty((a, b), device=A.device, dtype=F32) if out is None else out
+    ldc = _mat(out)
+    assert out.shape == (a, b)
+    ws = _ws(lib().ta_spk_gram_ws_floats(N, a, b), A)
+    check(lib().ta_spk_panel_gram_f32(ptr(A), lda, a, ptr(B), ldb, b, N, ptr(out), ldc, ptr(ws), stream()), "ta_spk_panel_gram_f32")
+    return out
+
+
+def spk_panel_update(B, A, C):
+    """ta_spk_panel_update_f32: ``B`` [N, b <= 32] -= ``A`` [N, a] ``C`` [a, b], in place.  -> B."""
+    ldb, lda, ldc = _mat(B), _mat(A), _mat(C)
+    (N, b), a = B.shape, A.shape[1]
+    assert A.shape[0] == N and C.shape == (a, b)
+    check(lib().ta_spk_panel_update_f32(ptr(B), ldb, b, ptr(A), lda, a, ptr(C), ldc, N, stream()), "ta_spk_panel_update_f32")
+    return B
+
+
+def spk_panel_combine(V, Z, *, out=None):
+    """ta_spk_panel_combine_f32: Y [N, m <= 32] = ``V`` [N, c] ``Z`` [c, m]."""
+    ldv, ldz = _mat(V), _mat(Z)
+    (N, c), m = V.shape, Z.shape[1]
+    assert Z.shape[0] == c
+    out = torch.empty((N, m), device=V.device, dtype=F32) if out is None else out
+    ldy = _mat(out)
+    assert out.shape == (N, m)
+    check(lib().ta_spk_panel_combine_f32(ptr(V), ldv, c, ptr(Z), ldz, m, ptr(out), ldy, N, stream()), "ta_spk_panel_combine_f32")
+    return out

@@ -9,6 +9,9 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
     ta355::ecapa_embeddings    SpeechBrain ECAPA-TDNN encode_batch, one call per window   tiny_audio/diarization.py:457-517
+    ta355::spk_affinity        SpectralCluster.get_sim_mat / p_pruning / get_laplacian   tiny_audio/diarization.py:49-89
+    ta355::spk_laplacian_matmul, spk_panel_gram / _update / _combine   the products scipy.linalg.eigh is replaced by
+                               (block Lanczos, tiny_audio_amd/spectral.py)   tiny_audio/diarization.py:91-106
     ta355::token_scores        compute_transition_scores on one step's processed logits (TF:generation/utils.py); the reference
                                asks HF for no scores (tiny_audio/asr_modeling.py:631-637)
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
@@ -240,6 +243,71 @@ def ecapa_embeddings(audio: Tensor, starts: List[int], lengths: List[int], windo
 @ecapa_embeddings.register_fake
 def _(audio, starts, lengths, window_samples, handle):
     return audio.new_empty((len(starts), module_of(handle).config.lin_neurons), dtype=F32)
+
+
+# ============================================================================ speaker clustering
+@torch.library.custom_op("ta355::spk_affinity", mutates_args=())
+def spk_affinity(embeddings: Tensor, keep: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """f32 [N, D] window embeddings -> (W f32 [N, N]: cosine affinity, every row pruned to its ``keep`` largest entries, symmetrised,
+    zero diagonal; deg f32 [N]: its row sums; the survivors per row before symmetrisation i32 [N]).  Replaces get_sim_mat / p_pruning
+    / get_laplacian's host matrices (tiny_audio/diarization.py:49-89; ``ops.spk_affinity``).  No autograd."""
+    from . import ops
+    W, deg, kept = ops.spk_affinity(embeddings, keep, want_kept=True)
+    return W, deg, kept
+
+
+@spk_affinity.register_fake
+def _(embeddings, keep):
+    N = embeddings.shape[0]
+    return embeddings.new_empty((N, N)), embeddings.new_empty((N,)), embeddings.new_empty((N,), dtype=torch.int32)
+
+
+@torch.library.custom_op("ta355::spk_laplacian_matmul", mutates_args=())
+def spk_laplacian_matmul(W: Tensor, deg: Tensor, X: Tensor) -> Tensor:
+    """Y [N, p] = diag(deg) X - W X, p <= 32: the graph Laplacian of tiny_audio/diarization.py:87-89 applied without forming it."""
+    from . import ops
+    return ops.spk_laplacian_matmul(W, deg, X)
+
+
+@spk_laplacian_matmul.register_fake
+def _(W, deg, X):
+    return X.new_empty(X.shape)
+
+
+@torch.library.custom_op("ta355::spk_panel_gram", mutates_args=())
+def spk_panel_gram(A: Tensor, B: Tensor) -> Tensor:
+    """C [a, b] = A^T B for two panels of N rows, summed in a fixed order (``ops.spk_panel_gram``)."""
+    from . import ops
+    return ops.spk_panel_gram(A, B)
+
+
+@spk_panel_gram.register_fake
+def _(A, B):
+    return A.new_empty((A.shape[1], B.shape[1]))
+
+
+@torch.library.custom_op("ta355::spk_panel_update", mutates_args=())
+def spk_panel_update(B: Tensor, A: Tensor, C: Tensor) -> Tensor:
+    """B - A C for ``B`` [N, b <= 32], ``A`` [N, a], ``C`` [a, b] (``ops.spk_panel_update`` on a copy of B)."""
+    from . import ops
+    return ops.spk_panel_update(B.clone(memory_format=torch.contiguous_format), A, C)
+
+
+@spk_panel_update.register_fake
+def _(B, A, C):
+    return B.new_empty(B.shape)
+
+
+@torch.library.custom_op("ta355::spk_panel_combine", mutates_args=())
+def spk_panel_combine(V: Tensor, Z: Tensor) -> Tensor:
+    """Y [N, m <= 32] = V Z (``ops.spk_panel_combine``)."""
+    from . import ops
+    return ops.spk_panel_combine(V, Z)
+
+
+@spk_panel_combine.register_fake
+def _(V, Z):
+    return V.new_empty((V.shape[0], Z.shape[1]))
 
 
 # ============================================================================ MLP projector
@@ -685,4 +753,5 @@ lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
              "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
-             "token_scores", "wav2vec2_emissions", "ecapa_embeddings")
+             "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
+             "spk_panel_update", "spk_panel_combine")
