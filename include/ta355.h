@@ -385,6 +385,49 @@ int ta_sample_f32(const float* logits, long ld, int V, int B, unsigned long long
  * min_new, logits[b, ids[e]] = -inf for every eos id.  Call between ta_logits_process and ta_argmax_f32. */
 int ta_logits_suppress_until(float* logits, long ld, int V, const long* ids, int n_ids, int min_new, const int* step_dev, int B,
                              hipStream_t st);
+/* ---- Decoding options: HF's remaining single-hypothesis logits processors (TF:generation/logits_process.py; the reference forwards
+ * **generate_kwargs to language_model.generate, tiny_audio/asr_modeling.py:625-637, :723-729).  All three work in place on the step's
+ * logits f32 [B, ld] (V valid columns; columns >= V are never read or written), read the step from *step_dev (tokens generated so far)
+ * and take tables that live in device memory, so their launch arguments are step-invariant (hipGraph-capturable).  HF's order
+ * (TF:generation/utils.py _get_logits_processor): ta_logits_sequence_bias (sequence_bias) -> ta_logits_process ->
+ * ta_logits_sequence_bias (bad_words_ids) -> ta_logits_suppress_until -> ta_logits_step_rules -> ta_logits_warp -> ta_logits_warp_ext.
+ *
+ * ta_logits_sequence_bias: SequenceBiasLogitsProcessor; NoBadWordsLogitsProcessor is the same with every bias -inf.  The context of row
+ * b is prompt_ids[b, :L] followed by the first *step_dev tokens of out_seq[b] (L = 0: the generated tokens only).  A length-1 sequence
+ * always adds its bias to its token; a longer one adds it to its last token iff it is not longer than the context and its first len-1
+ * tokens equal the last len-1 tokens of the context.  The table: seq_tokens i64 [n_tokens] (the sequences, flattened), seq_offsets i32
+ * [n_seq + 1], seq_bias f32 [n_seq], SORTED by last token with group_starts i32 [n_groups + 1] delimiting the runs of equal last token
+ * (distinct between groups).  One lane owns a group and adds its matching biases in table order to 0, then the sum to the score: no
+ * float atomics, HF's f32 result bit for bit when a group lists its length-1 entry first and then HF's order (ops.build_sequence_table).
+ * n_seq <= TA_SEQ_BIAS_MAX_SEQS, every sequence <= TA_SEQ_BIAS_MAX_LEN tokens (n_tokens <= n_seq * TA_SEQ_BIAS_MAX_LEN), else TA_ERR_ARG. */
+#define TA_SEQ_BIAS_MAX_SEQS 4096
+#define TA_SEQ_BIAS_MAX_LEN 32
+int ta_logits_sequence_bias(float* logits, long ld, int V, const long* prompt_ids, int L, const long* out_seq, int max_new,
+                            const int* step_dev, int B, const long* seq_tokens, const int* seq_offsets, const float* seq_bias,
+                            const int* group_starts, int n_seq, int n_groups, int n_tokens, hipStream_t st);
+/* ta_logits_step_rules: the four processors that depend on t = *step_dev only, in HF's order, one launch; any subset may be absent
+ * (count 0 / NULL):
+ *   ForcedEOSTokenLogitsProcessor          at t == max_new - 1 the row becomes -inf and forced_eos_ids [n_forced] become 0;
+ *   ExponentialDecayLengthPenalty          for t > decay_start: score[e] += |score[e]| * decay_mult[t] for every id e of eos_ids [n_eos]
+ *                                          (decay_mult f32 [max_new] = f32(factor ** (t - decay_start) - 1), computed on the host exactly
+ *                                          as HF's Python does; NULL = off; one rounded multiply, one rounded add, no pow on the device);
+ *   SuppressTokensLogitsProcessor          suppress_ids [n_suppress] -> -inf at every step;
+ *   SuppressTokensAtBeginLogitsProcessor   begin_suppress_ids [n_begin] -> -inf at t == 0.
+ * The prompt length cancels out of all four HF conditions. */
+int ta_logits_step_rules(float* logits, long ld, int V, int B, const int* step_dev, int max_new, const long* forced_eos_ids,
+                         int n_forced, const long* eos_ids, int n_eos, int decay_start, const float* decay_mult,
+                         const long* suppress_ids, int n_suppress, const long* begin_suppress_ids, int n_begin, hipStream_t st);
+/* ta_logits_warp_ext: the warpers ta_logits_warp lacks, after it, in HF's order, each on the row its predecessor left
+ * (min_tokens_to_keep = 1):
+ *   MinPLogitsWarper (min_p in [0, 1], 0 = off)          remove p < min_p * max p;
+ *   TypicalLogitsWarper (typical_p in (0, 1], 1 = off)   s_i = |-log p_i - H|; keep s_i <= s_cut, the shifted score at which the
+ *                                                        cumulative probability in ascending s first reaches typical_p (ties with s_cut
+ *                                                        all survive; like HF this can remove the row maximum);
+ *   EpsilonLogitsWarper (epsilon_cutoff in [0, 1), 0 = off)   remove p < eps, never the row maximum;
+ *   EtaLogitsWarper (eta_cutoff in [0, 1), 0 = off)           remove p < min(eps, sqrt(eps) exp(-H)), never the row maximum.
+ * Removed entries become -inf, survivors keep their value.  One 1024-lane workgroup per row; s_cut by bisection, no sort. */
+int ta_logits_warp_ext(float* logits, long ld, int V, int B, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff,
+                       hipStream_t st);
 int ta_greedy_advance(const long* amax, const long* eos_ids, int n_eos, long pad_id, int* finished, long* next_ids,
                       long* out_seq, int max_new, int* step_dev, int* slot_dev, int* pos, int* kmask, int Lmax, int B,
                       int* n_unfinished, hipStream_t st);

@@ -2,7 +2,9 @@
 """Greedy-generation timing at full model size (secondary metric: the WER loop's inference side).
 B clips of 10 s, prompt = 3 + 125 <audio> + 24 tokens, N new tokens; reports prompt-pass and per-token latency.
 ``gen_bench.py [B [N]] [--scores] [--top-logprobs K]``: the same loop with the decoding scores on (token log-probability and entropy,
-K alternatives per step)."""
+K alternatives per step).  Decoding options: ``--bad-words`` (256 two-token entries), ``--suppress`` (64 suppressed ids), ``--min-p P`` and
+``--typical-p P`` (both switch sampling on: HF's warpers act under do_sample only); ``--options-sweep`` measures none, each of the four alone
+and all of them in one process, one JSON line each."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,12 +13,23 @@ from tiny_audio_amd.asr_config import ASRConfig
 from tiny_audio_amd.asr_modeling import ASRModel
 
 argv, scores, top_lp = [], False, 0
+bad_words, suppress, min_p, typical_p, sweep = False, False, None, None, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--scores":
         scores = True
     elif a == "--top-logprobs":
         top_lp = int(next(it))
+    elif a == "--bad-words":
+        bad_words = True
+    elif a == "--suppress":
+        suppress = True
+    elif a == "--min-p":
+        min_p = float(next(it))
+    elif a == "--typical-p":
+        typical_p = float(next(it))
+    elif a == "--options-sweep":
+        sweep = True
     else:
         argv.append(a)
 B = int(argv[0]) if len(argv) > 0 else 32
@@ -29,14 +42,46 @@ ids = torch.tensor([[5, 6, 7] + [cfg.audio_token_id] * 125 + list(range(100, 124
 kw = dict(input_ids=ids, input_features=feats, audio_attention_mask=amask, attention_mask=torch.ones_like(ids), eos_token_id=[])
 if scores or top_lp:
     kw.update(return_token_scores=scores, top_logprobs=top_lp)
-res = {}
-for n in (1, N):
-    m.generate(**kw, max_new_tokens=n); torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(3):
-        out = m.generate(**kw, max_new_tokens=n)
-    torch.cuda.synchronize()
-    res[n] = (time.perf_counter() - t0) / 3
+
+
+def option_kwargs(bad_words, suppress, min_p, typical_p):
+    o = {}
+    if bad_words:       # 256 two-token entries over 16 last tokens: groups of 16 sequences
+        o["bad_words_ids"] = [[2000 + i, 3000 + i % 16] for i in range(256)]
+    if suppress:
+        o["suppress_tokens"] = list(range(4000, 4064))
+    if min_p is not None or typical_p is not None:
+        o.update(do_sample=True, seed=0)
+        if min_p is not None:
+            o["min_p"] = min_p
+        if typical_p is not None:
+            o["typical_p"] = typical_p
+    return o
+
+
+def measure(options):
+    res = {}
+    for n in (1, N):
+        m.generate(**kw, **options, max_new_tokens=n); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            m.generate(**kw, **options, max_new_tokens=n)
+        torch.cuda.synchronize()
+        res[n] = (time.perf_counter() - t0) / 3
+    return res
+
+
+if sweep:
+    for name, o in (("none", option_kwargs(False, False, None, None)), ("sampling only", dict(do_sample=True, seed=0)),
+                    ("bad_words", option_kwargs(True, False, None, None)), ("suppress", option_kwargs(False, True, None, None)),
+                    ("min_p", option_kwargs(False, False, 0.05, None)), ("typical_p", option_kwargs(False, False, None, 0.9)),
+                    ("all", option_kwargs(True, True, 0.05, 0.9))):
+        r = measure(o)
+        print(json.dumps({"B": B, "new_tokens": N, "options": name, "prompt_pass_ms": round(r[1] * 1e3, 2),
+                          "per_token_ms": round((r[N] - r[1]) / (N - 1) * 1e3, 3)}), flush=True)
+    sys.exit(0)
+options = option_kwargs(bad_words, suppress, min_p, typical_p)
+res = measure(options)
 per_tok = (res[N] - res[1]) / (N - 1)
 # decode roofline: a step streams every LM weight once (bf16 linears of all layers + the tied lm_head) and the KV cache of the
 # positions so far (prompt 152 + on average N / 2 generated); HBM peak 8 TB/s (MI355X_MICROARCH.md)
@@ -54,4 +99,5 @@ print(json.dumps({"B": B, "new_tokens": N, "prompt_pass_ms": round(res[1] * 1e3,
                                "achieved": round((w_bytes + kv_bytes) / per_tok / 1e9, 1),
                                "frac": round(floor_ms / (per_tok * 1e3), 4), "floor_ms_per_token": round(floor_ms, 4),
                                "frac_weights_only": round(w_bytes / 8e12 / per_tok, 4)},
-                  "fused": os.environ.get("TA355_DECODE_FUSED", "1") != "0", "token_scores": bool(scores or top_lp), "top_logprobs": top_lp}))
+                  "fused": os.environ.get("TA355_DECODE_FUSED", "1") != "0", "token_scores": bool(scores or top_lp), "top_logprobs": top_lp,
+                  "options": sorted(k for k in options if k not in ("do_sample", "seed"))}))

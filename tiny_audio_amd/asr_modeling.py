@@ -613,6 +613,7 @@ class ASRModel(nn.Module):
             eos_ids = [self.config.eos_token_id, self.config.pad_token_id]
         eos_ids = [int(e) for e in (eos_ids if isinstance(eos_ids, (list, tuple)) else [eos_ids]) if e is not None]
         pad_id = int(kw.pop("pad_token_id", self.config.pad_token_id))
+        options = self._decoding_options(kw, eos_ids, min_new, sampling is not None)
         dev = self.device_
         feats = input_features.to(dev)
         B = feats.shape[0]
@@ -634,7 +635,50 @@ class ASRModel(nn.Module):
         src_row = ops.audio_index(ids, counts, N, self.audio_token_id)
         return dict(input_ids=ids, src_row=src_row, audio=y.reshape(B * N, -1), attention_mask=attention_mask,
                     max_new_tokens=max_new, eos_ids=eos_ids, pad_id=pad_id, repetition_penalty=rep, no_repeat_ngram_size=ngram,
-                    min_new_tokens=min_new, sampling=sampling)
+                    min_new_tokens=min_new, sampling=sampling, **options)
+
+    def _decoding_options(self, kw, eos_ids, min_new, do_sample):
+        """HF's remaining single-hypothesis options, each read from the call's keywords, then from ``self.config``
+        (``_generation_setting``), validated with HF's wording -> the decoding-option keywords of ``greedy_decode_iter`` (only those
+        that are set: with none, the decode loop gets nothing new).  ``bad_words_ids``, ``sequence_bias`` (both HF forms),
+        ``suppress_tokens``, ``begin_suppress_tokens``, ``forced_eos_token_id``, ``exponential_decay_length_penalty``; under
+        ``do_sample`` also ``min_p``, ``typical_p``, ``epsilon_cutoff``, ``eta_cutoff`` (HF builds no warper otherwise; neither do we).
+        ``renormalize_logits=True`` is accepted and launches nothing: the selection (argmax, or a draw from the softmax) is invariant
+        under a per-row shift, and ``ta_token_scores_f32`` already reports normalised log-probabilities."""
+        V = int(self.language_model.config.vocab_size)
+        get = lambda name: self._generation_setting(name, None, kw)  # noqa: E731
+        out = {}
+        sb = get("sequence_bias")
+        if sb is not None:
+            out["sequence_bias"] = ops.normalize_sequence_bias(sb)
+            ops.build_sequence_table(out["sequence_bias"], V, "cpu", "sequence_bias")       # the id and limit checks, before any device work
+        bw = get("bad_words_ids")
+        if bw is not None:
+            bad = ops.normalize_bad_words(bw, eos_ids)
+            ops.build_sequence_table(bad, V, "cpu", "bad_words_ids")
+            if bad:
+                out["bad_words"] = bad
+        forced = get("forced_eos_token_id")
+        if forced is not None:
+            out["forced_eos_ids"] = ops.id_list(forced, V, "forced_eos_token_id")
+        decay = get("exponential_decay_length_penalty")
+        if decay is not None and eos_ids:
+            if not isinstance(decay, (tuple, list)) or len(decay) != 2:
+                raise ValueError(f"`exponential_decay_length_penalty` has to be a (start_index, decay_factor) pair, but is {decay}")
+            if min_new > int(decay[0]):
+                raise ValueError(f"min_new_tokens ({min_new}) > exponential_decay_length_penalty start ({decay[0]}): HF forms "
+                                 "-inf + inf = NaN on the eos scores in that window; refused")
+            ops.id_list(eos_ids, V, "eos_token_id")
+            out["exponential_decay_length_penalty"] = (int(decay[0]), float(decay[1]))
+        for name in ("suppress_tokens", "begin_suppress_tokens"):
+            v = get(name)
+            if v is not None and len(v):
+                out[name] = ops.id_list(list(v), V, name)
+        wx = ops.check_warp_ext(get("min_p"), get("typical_p"), get("epsilon_cutoff"), get("eta_cutoff"))
+        if do_sample and wx != (0.0, 1.0, 0.0, 0.0):
+            out["warp_ext"] = wx
+        kw.pop("renormalize_logits", None)
+        return out
 
     @staticmethod
     def _check_top_logprobs(top_logprobs) -> int:

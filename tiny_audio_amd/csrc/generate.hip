@@ -889,6 +889,218 @@ extern "C" int ta_token_scores_f32(const float* logits, long ld, int V, int B, c
   return TA_OK;
 }
 
+// ---- decoding options (HF's remaining single-hypothesis logits processors, TF:generation/logits_process.py; _get_logits_processor applies
+// sequence_bias -> repetition_penalty -> no_repeat_ngram -> bad_words -> min_new_tokens -> forced_eos -> exponential decay -> suppress ->
+// begin_suppress -> [do_sample: temperature -> top_k -> top_p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff]).  Every launch takes
+// step-invariant arguments: the step is *step_p, the tables are uploaded before the first step (hipGraph-capturable).
+//
+// SequenceBiasLogitsProcessor (and NoBadWordsLogitsProcessor = the same with bias -inf).  HF builds bias = 0, adds the length-1 entries,
+// then every longer sequence whose first len-1 tokens close the context, in the order given, and returns scores + bias.  The table is
+// sorted by last token on the host (length-1 entry first, then the given order), one lane owns one last token and adds its matches in
+// that order: no float atomics, the same f32 sums as HF.  The context of row b is prompt[b, :L] followed by *step_p tokens of out_seq[b].
+__global__ __launch_bounds__(256) void logits_sequence_bias_kernel(float* __restrict__ logits, long ld, int V, const long* __restrict__ prompt,
+                                                                   int L, const long* __restrict__ out_seq, int max_new,
+                                                                   const int* __restrict__ step_p, const long* __restrict__ toks,
+                                                                   const int* __restrict__ offs, const float* __restrict__ bias,
+                                                                   const int* __restrict__ gstart, int n_groups) {
+  const int b = blockIdx.x, t = *step_p, n = L + (t < max_new ? t : max_new);
+  float* row = logits + (long)b * ld;
+  const long* pr = prompt + (long)b * L;
+  const long* gen = out_seq + (long)b * max_new;
+  auto tok = [&](int i) -> long { return i < L ? pr[i] : gen[i - L]; };
+  for (int g = threadIdx.x; g < n_groups; g += blockDim.x) {
+    const int s0 = gstart[g], s1 = gstart[g + 1];
+    if (s1 <= s0) continue;
+    const long last = toks[offs[s0 + 1] - 1];
+    if (last < 0 || last >= V) continue;
+    float acc = 0.f;
+    for (int s = s0; s < s1; ++s) {
+      const int o = offs[s], pre = offs[s + 1] - o - 1;             // pre = the prefix length; HF skips a sequence longer than the context
+      bool hit = pre == 0 || pre + 1 <= n;
+      for (int j = 0; hit && j < pre; ++j) hit = toks[o + j] == tok(n - pre + j);
+      if (hit) acc = acc + bias[s];
+    }
+    row[last] = row[last] + acc;                                    // IEEE: -inf + finite = -inf either way round
+  }
+}
+extern "C" int ta_logits_sequence_bias(float* logits, long ld, int V, const long* prompt_ids, int L, const long* out_seq, int max_new,
+                                       const int* step_dev, int B, const long* seq_tokens, const int* seq_offsets, const float* seq_bias,
+                                       const int* group_starts, int n_seq, int n_groups, int n_tokens, hipStream_t st) {
+  if (B <= 0 || n_seq <= 0) return TA_OK;
+  if (!logits || V <= 0 || ld < V || L < 0 || max_new < 0 || (L > 0 && !prompt_ids) || (max_new > 0 && !out_seq) || !step_dev ||
+      !seq_tokens || !seq_offsets || !seq_bias || !group_starts)
+    return TA_ERR_ARG;
+  if (n_seq > TA_SEQ_BIAS_MAX_SEQS || n_groups <= 0 || n_groups > n_seq || n_tokens < n_seq ||
+      (long)n_tokens > (long)n_seq * TA_SEQ_BIAS_MAX_LEN)
+    return TA_ERR_ARG;
+  TA_LAUNCH(logits_sequence_bias_kernel, dim3(B), dim3(256), 0, st, logits, ld, V, prompt_ids, L, out_seq, max_new, step_dev, seq_tokens,
+            seq_offsets, seq_bias, group_starts, n_groups);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// The four rules that depend on the step t = *step_p (tokens generated so far) only, in HF's order, one workgroup per row:
+//   ForcedEOSTokenLogitsProcessor       t == max_new - 1: the row becomes -inf, the forced ids 0
+//   ExponentialDecayLengthPenalty       t > start: score[e] += |score[e]| * mult[t] for every eos id e (mult[t] = f32(factor^(t-start) - 1)
+//                                       from the host, as HF's Python computes it; separate multiply and add, as torch's two kernels)
+//   SuppressTokensLogitsProcessor       the listed ids -> -inf
+//   SuppressTokensAtBeginLogitsProcessor  the listed ids -> -inf at t == 0
+__global__ __launch_bounds__(1024) void logits_step_rules_kernel(float* __restrict__ logits, long ld, int V, const int* __restrict__ step_p,
+                                                                 int max_new, const long* __restrict__ forced, int n_forced,
+                                                                 const long* __restrict__ eos, int n_eos, int decay_start,
+                                                                 const float* __restrict__ decay_mult, const long* __restrict__ sup, int n_sup,
+                                                                 const long* __restrict__ bsup, int n_bsup) {
+  const int t = *step_p, tid = threadIdx.x;
+  float* row = logits + (long)blockIdx.x * ld;
+  if (n_forced > 0 && t == max_new - 1) {
+    for (int j = tid; j < V; j += 1024) row[j] = -INFINITY;
+    __syncthreads();
+    for (int i = tid; i < n_forced; i += 1024) { const long id = forced[i]; if (id >= 0 && id < V) row[id] = 0.f; }
+    __syncthreads();
+  }
+  if (decay_mult && n_eos > 0 && t > decay_start && t < max_new) {
+    const float mult = decay_mult[t];
+    for (int i = tid; i < n_eos; i += 1024) {
+      const long id = eos[i];
+      bool first = id >= 0 && id < V;                               // an id listed twice is penalised once (HF assigns, then adds)
+      for (int j = 0; j < i; ++j) first &= eos[j] != id;
+      if (first) {
+#pragma clang fp contract(off)                                      // two roundings, as torch's mul and add kernels: never one fma
+        const float v = row[id];
+        const float pen = fabsf(v) * mult;
+        row[id] = v + pen;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < n_sup; i += 1024) { const long id = sup[i]; if (id >= 0 && id < V) row[id] = -INFINITY; }
+  if (t == 0)
+    for (int i = tid; i < n_bsup; i += 1024) { const long id = bsup[i]; if (id >= 0 && id < V) row[id] = -INFINITY; }
+}
+extern "C" int ta_logits_step_rules(float* logits, long ld, int V, int B, const int* step_dev, int max_new, const long* forced_eos_ids,
+                                    int n_forced, const long* eos_ids, int n_eos, int decay_start, const float* decay_mult,
+                                    const long* suppress_ids, int n_suppress, const long* begin_suppress_ids, int n_begin, hipStream_t st) {
+  const bool decay = decay_mult != nullptr && n_eos > 0;
+  if (B <= 0 || (n_forced <= 0 && !decay && n_suppress <= 0 && n_begin <= 0)) return TA_OK;
+  if (!logits || V <= 0 || ld < V || !step_dev || max_new <= 0 || (n_forced > 0 && !forced_eos_ids) || (decay && (!eos_ids || decay_start < 0)) ||
+      (n_suppress > 0 && !suppress_ids) || (n_begin > 0 && !begin_suppress_ids))
+    return TA_ERR_ARG;
+  TA_LAUNCH(logits_step_rules_kernel, dim3(B), dim3(1024), 0, st, logits, ld, V, step_dev, max_new, forced_eos_ids, n_forced > 0 ? n_forced : 0,
+            eos_ids, decay ? n_eos : 0, decay_start, decay ? decay_mult : nullptr, suppress_ids, n_suppress > 0 ? n_suppress : 0,
+            begin_suppress_ids, n_begin > 0 ? n_begin : 0);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
+// The remaining warpers, after ta_logits_warp, in HF's order and each on the row its predecessor left (HF recomputes the softmax in each):
+//   MinPLogitsWarper      remove p < min_p * max p          <=> e^(x - max) < min_p
+//   TypicalLogitsWarper   s_i = |-log p_i - H|; keep s_i <= s_cut, the smallest s at which the mass of {s_j <= s} reaches `mass`
+//   EpsilonLogitsWarper   remove p < eps, never the maximum
+//   EtaLogitsWarper       remove p < min(eps, sqrt(eps) e^-H), never the maximum
+// One 1024-lane workgroup per row.  log Z and H come from the one-pass (m, s, t) statistics of token_scores_kernel (-inf skipped).
+// s_cut by bisection on the integer image of s >= 0 (its bit pattern) with mass-summing passes over the row; once at most WX_CAP
+// elements lie between the bounds they go to an LDS list (image, e^(x-m)) and the rest of the bisection runs there.  Elements tied
+// with s_cut all survive (HF removes s > s_cut only).
+#define WX_CAP 4096
+__global__ __launch_bounds__(1024) void logits_warp_ext_kernel(float* __restrict__ logits, long ld, int V, float min_p, float typical_p,
+                                                               float eps_cut, float eta_cut) {
+  __shared__ float rm[16], rs[16], rt[16];
+  __shared__ float red[17];
+  __shared__ int c_ord[WX_CAP];
+  __shared__ float c_e[WX_CAP];
+  __shared__ int ncand;
+  float* row = logits + (long)blockIdx.x * ld;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float m, s, t;
+  auto stats = [&]() {
+    float lm = -INFINITY, ls = 0.f, lt = 0.f;
+    for (int j = tid; j < V; j += 1024) { const float v = row[j]; if (v > -INFINITY) lse_merge(lm, ls, lt, v, 1.f, 0.f); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(lm, ls, lt, __shfl_xor(lm, o, 64), __shfl_xor(ls, o, 64), __shfl_xor(lt, o, 64));
+    __syncthreads();
+    if (lane == 0) { rm[wave] = lm; rs[wave] = ls; rt[wave] = lt; }
+    __syncthreads();
+    m = rm[0]; s = rs[0]; t = rt[0];
+    for (int w = 1; w < 16; ++w) lse_merge(m, s, t, rm[w], rs[w], rt[w]);    // the same order in every lane
+  };
+  stats();
+  if (m == -INFINITY) return;                                     // an all -inf row: nothing to do
+  bool fresh = true;                                              // (m, s, t) describe the row as it stands
+  if (min_p > 0.f) {
+    for (int j = tid; j < V; j += 1024) { const float v = row[j]; if (v > -INFINITY && v < m && __expf(v - m) < min_p) row[j] = -INFINITY; }
+    fresh = false;
+  }
+  if (typical_p > 0.f && typical_p < 1.0f) {
+    if (!fresh) stats();
+    const float lz = m + logf(s), H = logf(s) - t / s;
+    auto s_ord = [&](float v) { return __float_as_int(fabsf((lz - v) - H)); };      // >= 0: the bit pattern orders it
+    int smx = 0; float cnt = 0.f;
+    for (int j = tid; j < V; j += 1024) { const float v = row[j]; if (v > -INFINITY) { smx = max(smx, s_ord(v)); cnt += 1.f; } }
+    smx = __float_as_int(block_max_1024(__int_as_float(smx), red));
+    cnt = block_sum_1024(cnt, red);
+    // invariant: mass(s <= lo) < target <= mass(s <= hi); cnt = elements with lo < s <= hi; base = mass(s <= lo)
+    int lo = -1, hi = smx, nc = 0;
+    float base = 0.f;
+    bool listed = false;
+    const float target = typical_p * s;
+    while (hi - lo > 1) {
+      if (!listed && cnt <= (float)WX_CAP) {
+        if (tid == 0) ncand = 0;
+        __syncthreads();
+        for (int j = tid; j < V; j += 1024) {
+          const float v = row[j];
+          if (v > -INFINITY) {
+            const int o = s_ord(v);
+            if (o > lo && o <= hi) { const int q = atomicAdd(&ncand, 1); if (q < WX_CAP) { c_ord[q] = o; c_e[q] = __expf(v - m); } }
+          }
+        }
+        __syncthreads();
+        nc = ncand < WX_CAP ? ncand : WX_CAP;
+        listed = true;
+      }
+      const int mid = lo + (hi - lo) / 2;
+      float ms = 0.f, c = 0.f;
+      if (listed) {
+        for (int q = tid; q < nc; q += 1024) { const int o = c_ord[q]; if (o > lo && o <= mid) ms += c_e[q]; }
+        ms = base + block_sum_1024(ms, red);
+      } else {
+        for (int j = tid; j < V; j += 1024) {
+          const float v = row[j];
+          if (v > -INFINITY) { const int o = s_ord(v); if (o <= mid) { ms += __expf(v - m); c += o > lo ? 1.f : 0.f; } }
+        }
+        ms = block_sum_1024(ms, red);
+        c = block_sum_1024(c, red);
+      }
+      if (ms >= target) { hi = mid; cnt = c; } else { lo = mid; cnt -= c; base = ms; }
+    }
+    for (int j = tid; j < V; j += 1024) { const float v = row[j]; if (v > -INFINITY && s_ord(v) > hi) row[j] = -INFINITY; }
+    fresh = false;
+  }
+  if (eps_cut > 0.f) {
+    if (!fresh) stats();
+    const float thr = eps_cut * s;
+    for (int j = tid; j < V; j += 1024) { const float v = row[j]; if (v > -INFINITY && v < m && __expf(v - m) < thr) row[j] = -INFINITY; }
+    fresh = false;
+  }
+  if (eta_cut > 0.f) {
+    if (!fresh) stats();
+    const float H = logf(s) - t / s;
+    const float thr = fminf(eta_cut, sqrtf(eta_cut) * __expf(-H)) * s;
+    for (int j = tid; j < V; j += 1024) { const float v = row[j]; if (v > -INFINITY && v < m && __expf(v - m) < thr) row[j] = -INFINITY; }
+  }
+}
+extern "C" int ta_logits_warp_ext(float* logits, long ld, int V, int B, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff,
+                                  hipStream_t st) {
+  if (B <= 0) return TA_OK;
+  if (!logits || V <= 0 || ld < V || !(min_p >= 0.f && min_p <= 1.0f) || !(typical_p > 0.f && typical_p <= 1.0f) ||
+      !(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.0f) || !(eta_cutoff >= 0.f && eta_cutoff < 1.0f))
+    return TA_ERR_ARG;
+  if (min_p == 0.f && typical_p == 1.0f && epsilon_cutoff == 0.f && eta_cutoff == 0.f) return TA_OK;
+  TA_LAUNCH(logits_warp_ext_kernel, dim3(B), dim3(1024), 0, st, logits, ld, V, min_p, typical_p, epsilon_cutoff, eta_cutoff);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+
 extern "C" int ta_greedy_advance(const long* amax, const long* eos_ids, int n_eos, long pad_id, int* finished, long* next_ids,
                                  long* out_seq, int max_new, int* step_dev, int* slot_dev, int* pos, int* kmask, int Lmax,
                                  int B, int* n_unfinished, hipStream_t st) {

@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .asr_config import LMConfig
 from .ops import BF16, F32, ptr, stream
 
@@ -637,19 +637,23 @@ class Qwen3MI355X(torch.nn.Module):
     @torch.no_grad()
     def greedy_decode(self, input_ids, src_row, audio, attention_mask=None, max_new_tokens=128, eos_ids=(), pad_id=0,
                       sync_every=8, use_graph=True, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sampling=None,
-                      token_scores=False, top_logprobs=0):
+                      token_scores=False, top_logprobs=0, **decode_options):
         """-> int64 [B, n_new], or with ``token_scores`` / ``top_logprobs`` the pair (that tensor, the scores dict); see
-        ``greedy_decode_iter`` (this drains it, polling the device every ``sync_every`` steps only)."""
+        ``greedy_decode_iter`` (this drains it, polling the device every ``sync_every`` steps only).  ``decode_options``: its
+        decoding-option keywords (``sequence_bias`` ... ``warp_ext``)."""
         out = None
         for out in self.greedy_decode_iter(input_ids, src_row, audio, attention_mask, max_new_tokens, eos_ids, pad_id,
                                            sync_every, use_graph, per_token=False, repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens, sampling=sampling,
-                                           no_repeat_ngram_size=no_repeat_ngram_size, token_scores=token_scores, top_logprobs=top_logprobs):
+                                           no_repeat_ngram_size=no_repeat_ngram_size, token_scores=token_scores, top_logprobs=top_logprobs,
+                                           **decode_options):
             pass
         return out
 
     def greedy_decode_iter(self, input_ids, src_row, audio, attention_mask=None, max_new_tokens=128, eos_ids=(), pad_id=0,
                            sync_every=8, use_graph=True, per_token=True, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
-                           processors_see_prompt=True, sampling=None, token_scores=False, top_logprobs=0):
+                           processors_see_prompt=True, sampling=None, token_scores=False, top_logprobs=0, sequence_bias=None,
+                           bad_words=None, forced_eos_ids=None, exponential_decay_length_penalty=None, suppress_tokens=None,
+                           begin_suppress_tokens=None, warp_ext=None):
         """HF greedy search with a KV cache (what ``language_model.generate`` does for the reference's generation
         config, tiny_audio/asr_config.py:103-111): prompt pass, then one token per clip per step until every clip has
         emitted an eos id or ``max_new_tokens`` is reached.  -> int64 [B, n_new] (prompt stripped; finished clips are
@@ -665,7 +669,17 @@ class Qwen3MI355X(torch.nn.Module):
         selection and the bookkeeping, also inside the captured step.  The last item is then ``(sequences, scores)`` with scores =
         {``token_logprobs`` f32 [B, n_new], ``token_entropy`` f32 [B, n_new], ``top_token_ids`` int64 [B, n_new, k] or None,
         ``top_logprobs`` f32 [B, n_new, k] or None} (positions after a clip's eos: 0 / 0 / -1 / -inf), and with ``per_token`` every
-        step yields ``(tokens [B], logprob [B])`` host tensors."""
+        step yields ``(tokens [B], logprob [B])`` host tensors.
+
+        Decoding options (all off by default, and then nothing below is launched or allocated), HF's processors in HF's order
+        (TF:generation/utils.py _get_logits_processor), device-side and inside the captured step; their tables are uploaded before the
+        prompt pass.  ``sequence_bias`` / ``bad_words``: [(tuple of ids, bias)] in HF's order (``ops.normalize_sequence_bias`` /
+        ``ops.normalize_bad_words``) -> ``ta_logits_sequence_bias`` before / after ``ta_logits_process``; their context is the prompt
+        plus the generated tokens, or the generated tokens alone with ``processors_see_prompt=False``.  ``forced_eos_ids``,
+        ``exponential_decay_length_penalty`` = (start, factor) (acts on ``eos_ids``), ``suppress_tokens``, ``begin_suppress_tokens`` ->
+        one ``ta_logits_step_rules`` after the min-new-tokens rule.  ``warp_ext`` = (min_p, typical_p, epsilon_cutoff, eta_cutoff) with
+        the off values (0, 1, 0, 0) -> ``ta_logits_warp_ext`` after ``ta_logits_warp``; it acts under ``sampling`` only, as HF's
+        warpers do.  All run before the scores kernel: scores and alternatives are those of the fully processed row."""
         n_top = int(top_logprobs or 0)
         if not 0 <= n_top <= 8:
             raise ValueError(f"top_logprobs must be within [0, 8]; got {top_logprobs}")
@@ -726,19 +740,55 @@ class Qwen3MI355X(torch.nn.Module):
                 sc_ids = torch.full((B, max_new, n_top), -1, dtype=i64, device=dev)
                 sc_top = torch.full((B, max_new, n_top), float("-inf"), dtype=F32, device=dev)
 
+        # decoding options: tables to the device now, so that the step's launches take pointers that never change
+        V = c.vocab_size
+        n_ctx = L if processors_see_prompt else 0
+        tab_bias = ops.build_sequence_table(sequence_bias or [], V, dev, "sequence_bias")
+        tab_bad = ops.build_sequence_table(bad_words or [], V, dev, "bad_words_ids")
+        ids_of = lambda v, what: torch.tensor(ops.id_list(v, V, what), dtype=i64, device=dev) if v else None  # noqa: E731
+        forced, sup = ids_of(forced_eos_ids, "forced_eos_token_id"), ids_of(suppress_tokens, "suppress_tokens")
+        bsup = ids_of(begin_suppress_tokens, "begin_suppress_tokens")
+        decay_start, decay_mult = 0, None
+        if exponential_decay_length_penalty is not None and n_eos:
+            if min_new > int(exponential_decay_length_penalty[0]):
+                raise ValueError(f"min_new_tokens ({min_new}) > exponential_decay_length_penalty start ({exponential_decay_length_penalty[0]}): "
+                                 "HF forms -inf + inf = NaN on the eos scores in that window; refused")
+            decay_start, decay_mult = ops.decay_multipliers(exponential_decay_length_penalty, max_new)
+            decay_mult = decay_mult.to(dev)
+        step_rules = forced is not None or decay_mult is not None or sup is not None or bsup is not None
+        n_of = lambda t: 0 if t is None else t.numel()  # noqa: E731
+        wx = None
+        if warp_ext is not None and sampling is not None and tuple(float(x) for x in warp_ext) != (0.0, 1.0, 0.0, 0.0):
+            wx = tuple(float(x) for x in warp_ext)
+
+        def seq_bias(tab):
+            _lib.check(L_.ta_logits_sequence_bias(ptr(logits), self.vocab_pad, V, ptr(ids), n_ctx, ptr(out_seq), max_new, ptr(step_dev), B,
+                                                  ptr(tab["tokens"]), ptr(tab["offsets"]), ptr(tab["bias"]), ptr(tab["groups"]),
+                                                  tab["n_seq"], tab["n_groups"], tab["n_tokens"], stream()), "ta_logits_sequence_bias")
+
         def advance():
+            if tab_bias is not None:                # HF SequenceBiasLogitsProcessor: first of all, so the repetition penalty sees it
+                seq_bias(tab_bias)
             if rep != 1.0 or ngram > 0:            # HF logits processors over prompt ids + generated tokens (device-side, graph-safe)
                 # processors_see_prompt=False: the generated tokens only -- what HF's processors see when generate() is given
                 # inputs_embeds WITHOUT input_ids (the reference's generate_streaming, tiny_audio/asr_modeling.py:723-729)
                 _lib.check(L_.ta_logits_process(ptr(logits), self.vocab_pad, c.vocab_size, ptr(ids), L if processors_see_prompt else 0, ptr(out_seq), max_new,
                                                 ptr(step_dev), B, rep, ngram, stream()), "ta_logits_process")
+            if tab_bad is not None:                 # HF NoBadWordsLogitsProcessor: the same kernel, every bias -inf
+                seq_bias(tab_bad)
             if min_new > 0 and n_eos:               # HF MinNewTokensLengthLogitsProcessor: no eos before min_new_tokens tokens exist
                 _lib.check(L_.ta_logits_suppress_until(ptr(logits), self.vocab_pad, c.vocab_size, ptr(eos), n_eos, min_new, ptr(step_dev), B,
                                                        stream()), "ta_logits_suppress_until")
+            if step_rules:                          # HF forced eos, exponential-decay length penalty, suppress, begin-suppress: one launch
+                _lib.check(L_.ta_logits_step_rules(ptr(logits), self.vocab_pad, V, B, ptr(step_dev), max_new, ptr(forced), n_of(forced),
+                                                   ptr(eos), n_eos if decay_mult is not None else 0, decay_start, ptr(decay_mult),
+                                                   ptr(sup), n_of(sup), ptr(bsup), n_of(bsup), stream()), "ta_logits_step_rules")
             if sampling is not None:                # do_sample: HF's warpers (temperature, top-k, top-p), then one multinomial draw per clip
                 temp, top_k, top_p, seed = sampling
                 _lib.check(L_.ta_logits_warp(ptr(logits), self.vocab_pad, c.vocab_size, B, float(temp), int(top_k), float(top_p), stream()),
                            "ta_logits_warp")
+                if wx is not None:                  # HF min-p, typical, epsilon, eta warpers
+                    _lib.check(L_.ta_logits_warp_ext(ptr(logits), self.vocab_pad, V, B, *wx, stream()), "ta_logits_warp_ext")
                 _lib.check(L_.ta_sample_f32(ptr(logits), self.vocab_pad, c.vocab_size, B, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step_dev),
                                             ptr(amax), stream()), "ta_sample_f32")
             else:

@@ -652,6 +652,196 @@ def token_scores(logits, chosen, V, top_k=0):
     return logprob, entropy, top_ids, top_lp
 
 
+# ----------------------------------------------------------------------------- decoding options (csrc/generate.hip)
+SEQ_BIAS_MAX_SEQS = 4096      # TA_SEQ_BIAS_MAX_SEQS / TA_SEQ_BIAS_MAX_LEN of include/ta355.h
+SEQ_BIAS_MAX_LEN = 32
+
+
+def normalize_sequence_bias(sequence_bias):
+    """HF's two forms of ``sequence_bias`` -- {tuple of ids: float} or [[ids, float], ...] -> [(tuple of ids, float)] in HF's order
+    (a dict's; the list form becomes a dict first, so a repeated sequence keeps its first place and its last bias).  Raises HF's
+    ValueErrors (TF:generation/logits_process.py SequenceBiasLogitsProcessor._validate_arguments)."""
+    import numpy as np
+    sb = sequence_bias
+    if not isinstance(sb, (dict, list)) or len(sb) == 0:
+        raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sb}.")
+    if isinstance(sb, dict):
+        if any(not isinstance(k, tuple) for k in sb):
+            raise ValueError(f"`sequence_bias` has to be a dict with tuples as keys, but is {sb}.")
+        if any(len(k) == 0 or any(not isinstance(t, (int, np.integer)) or t < 0 for t in k) for k in sb):
+            raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sb}.")
+        if any(not isinstance(b, float) for b in sb.values()):
+            raise ValueError(f"`sequence_bias` has to be a dict with floats as values, but is {sb}.")
+    else:
+        def ok(e):
+            return (isinstance(e, (list, tuple)) and len(e) == 2 and isinstance(e[0], list) and len(e[0]) > 0
+                    and all(isinstance(t, (int, np.integer)) and t > 0 for t in e[0]) and isinstance(e[1], float))
+        if any(not ok(e) for e in sb):
+            raise ValueError("Each element in `sequence_bias` has to be a non-empty list of lists of positive integers and float, "
+                             f"but is {sb}.")
+        sb = {tuple(e[0]): e[1] for e in sb}
+    return [(tuple(int(t) for t in k), float(b)) for k, b in sb.items()]
+
+
+def normalize_bad_words(bad_words_ids, eos_ids=()):
+    """``bad_words_ids`` -> [(tuple of ids, -inf)] as NoBadWordsLogitsProcessor builds it: HF's ValueErrors, entries that are exactly
+    ``[eos]`` dropped, repeated sequences once."""
+    import numpy as np
+    bw = bad_words_ids
+    if not isinstance(bw, list) or len(bw) == 0:
+        raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+    if any(not isinstance(w, list) for w in bw):
+        raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+    if any(any(not isinstance(t, (int, np.integer)) or t < 0 for t in w) for w in bw):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+    eos = [int(e) for e in eos_ids]
+    kept = [w for w in bw if all(list(w) != [e] for e in eos)]
+    return [(k, float("-inf")) for k in dict.fromkeys(tuple(int(t) for t in w) for w in kept)]
+
+
+def build_sequence_table(entries, vocab_size, device="cpu", what="sequence_bias"):
+    """[(tuple of ids, bias)] in HF's order -> the device table of ``ta_logits_sequence_bias``: dict(tokens i64 [n_tokens], offsets i32
+    [n_seq + 1], bias f32 [n_seq], groups i32 [n_groups + 1], n_seq, n_groups, n_tokens), sorted by last token.  Inside a group the
+    length-1 entry stands first and the longer ones keep the given order: the order in which HF's f32 bias row receives them.  None for
+    an empty list.  ValueError for an id >= vocab_size (HF's wording), an empty sequence, or a table beyond the library's limits."""
+    entries = [(tuple(k), float(b)) for k, b in entries]
+    if not entries:
+        return None
+    if any(len(k) == 0 for k, _ in entries):
+        raise ValueError(f"{what}: an empty token sequence")
+    bad = [t for k, _ in entries for t in k if t >= vocab_size or t < 0]
+    if bad:
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but the following tokens were being biased: {bad}")
+    if len(entries) > SEQ_BIAS_MAX_SEQS:
+        raise ValueError(f"{what}: {len(entries)} sequences exceed the limit of {SEQ_BIAS_MAX_SEQS} (TA_SEQ_BIAS_MAX_SEQS)")
+    longest = max(len(k) for k, _ in entries)
+    if longest > SEQ_BIAS_MAX_LEN:
+        raise ValueError(f"{what}: a sequence of {longest} tokens exceeds the limit of {SEQ_BIAS_MAX_LEN} (TA_SEQ_BIAS_MAX_LEN)")
+    order = sorted(range(len(entries)), key=lambda i: (entries[i][0][-1], len(entries[i][0]) != 1, i))
+    toks, offs, bias, groups = [], [0], [], []
+    for n, i in enumerate(order):
+        k, b = entries[i]
+        if n == 0 or entries[order[n - 1]][0][-1] != k[-1]:
+            groups.append(n)
+        toks.extend(k)
+        offs.append(len(toks))
+        bias.append(b)
+    groups.append(len(order))
+    return dict(tokens=torch.tensor(toks, dtype=torch.int64, device=device), offsets=torch.tensor(offs, dtype=torch.int32, device=device),
+                bias=torch.tensor(bias, dtype=torch.float64).to(F32).to(device), groups=torch.tensor(groups, dtype=torch.int32, device=device),
+                n_seq=len(order), n_groups=len(groups) - 1, n_tokens=len(toks))
+
+
+def decay_multipliers(exponential_decay_length_penalty, max_new):
+    """(start, factor) -> (start, f32 [max_new] with m[t] = float32(factor ** (t - start) - 1) for t > start, else 0): the scalar HF's
+    ExponentialDecayLengthPenalty multiplies |score[eos]| with, computed by the same Python ``pow`` in float64 and rounded once."""
+    start, factor = exponential_decay_length_penalty
+    start, factor = int(start), float(factor)
+    if start < 0:
+        raise ValueError(f"exponential_decay_length_penalty: start_index must be >= 0; got {start}")
+    m = torch.zeros(max(int(max_new), 1), dtype=torch.float64)
+    for t in range(start + 1, int(max_new)):
+        try:
+            m[t] = pow(factor, t - start) - 1
+        except OverflowError:
+            m[t] = float("inf")
+    return start, m.to(F32)
+
+
+def id_list(ids, vocab_size, what):
+    """An id or a list of ids -> [int]; ValueError for an id outside [0, vocab_size)."""
+    if torch.is_tensor(ids):
+        ids = ids.tolist()
+    ids = [int(i) for i in (ids if isinstance(ids, (list, tuple)) else [ids])]
+    bad = [i for i in ids if not 0 <= i < vocab_size]
+    if bad:
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but `{what}` holds the token ids {bad}")
+    return ids
+
+
+def check_warp_ext(min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+    """HF's argument checks (MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper) -> the four floats of
+    ``ta_logits_warp_ext`` with its "off" values (0, 1, 0, 0) for None."""
+    if min_p is not None and not 0 <= float(min_p) <= 1.0:
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    if typical_p is not None and not 0 < float(typical_p) <= 1:      # (1.0 is HF's "off": _get_logits_processor builds no warper for it)
+        raise ValueError(f"`typical_p` has to be a float > 0 and < 1, but is {float(typical_p)}")
+    if epsilon_cutoff is not None and not 0 <= float(epsilon_cutoff) < 1:      # (0.0 is HF's "off")
+        raise ValueError(f"`epsilon_cutoff` has to be a float > 0 and < 1, but is {float(epsilon_cutoff)}")
+    if eta_cutoff is not None and not 0 <= float(eta_cutoff) < 1:
+        raise ValueError(f"`eta_cutoff` has to be a float > 0 and < 1, but is {float(eta_cutoff)}")
+    return (0.0 if min_p is None else float(min_p), 1.0 if typical_p is None else float(typical_p),
+            0.0 if epsilon_cutoff is None else float(epsilon_cutoff), 0.0 if eta_cutoff is None else float(eta_cutoff))
+
+
+def _logits_rows(logits, V, what):
+    if not (logits.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error(f"{what} needs the logits on a HIP device: there is no CPU path")
+    if logits.dim() != 2 or logits.dtype != F32 or not (logits.stride(1) == 1 or logits.numel() == 0):
+        raise ValueError(f"{what}: logits must be f32 [B, ld] with unit column stride")
+    B, V = logits.shape[0], int(V)
+    ld = logits.stride(0) if B > 1 else logits.shape[1]
+    if not 0 < V <= logits.shape[1]:
+        raise ValueError(f"{what}: V = {V} is outside (0, {logits.shape[1]}]")
+    if ld < V:
+        raise ValueError(f"{what}: logits rows overlap")
+    return B, V, ld
+
+
+def _ids_tensor(ids, V, dev, what):
+    return None if not ids else torch.tensor(id_list(ids, V, what), dtype=torch.int64, device=dev)
+
+
+def logits_sequence_bias(logits, V, context, entries):
+    """ta_logits_sequence_bias on logits a caller holds, IN PLACE: ``logits`` f32 [B, ld] (V valid columns), ``context`` int64 [B, n]
+    (the ids so far; n may be 0), ``entries`` [(tuple of ids, bias)] in HF's order (``normalize_sequence_bias`` /
+    ``normalize_bad_words``), or a table ``build_sequence_table`` made on the logits' device.  -> logits."""
+    B, V, ld = _logits_rows(logits, V, "logits_sequence_bias")
+    dev = logits.device
+    if context.dtype != torch.int64 or context.dim() != 2 or context.shape[0] != B or context.device != dev:
+        raise ValueError(f"logits_sequence_bias: context must be int64 [{B}, n] on the logits' device")
+    tab = entries if isinstance(entries, dict) else build_sequence_table(entries, V, dev)
+    if tab is None:
+        return logits
+    ctx = context.contiguous()
+    n = ctx.shape[1]
+    step = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().ta_logits_sequence_bias(ptr(logits), ld, V, ptr(ctx) if n else None, n, None, 0, ptr(step), B, ptr(tab["tokens"]),
+                                        ptr(tab["offsets"]), ptr(tab["bias"]), ptr(tab["groups"]), tab["n_seq"], tab["n_groups"],
+                                        tab["n_tokens"], stream()), "ta_logits_sequence_bias")
+    return logits
+
+
+def logits_step_rules(logits, V, step, max_new, forced_eos_ids=None, eos_ids=None, exponential_decay_length_penalty=None,
+                      suppress_tokens=None, begin_suppress_tokens=None):
+    """ta_logits_step_rules on logits a caller holds, IN PLACE, for step ``step`` (tokens generated so far) of ``max_new``: HF's
+    forced-eos, exponential-decay length penalty (needs ``eos_ids``), suppress and begin-suppress processors, in that order.  -> logits."""
+    B, V, ld = _logits_rows(logits, V, "logits_step_rules")
+    dev, max_new = logits.device, int(max_new)
+    if not 0 <= int(step) < max_new:
+        raise ValueError(f"logits_step_rules: step = {step} is outside [0, {max_new})")
+    forced, eos = _ids_tensor(forced_eos_ids, V, dev, "forced_eos_token_id"), _ids_tensor(eos_ids, V, dev, "eos_token_id")
+    sup, bsup = _ids_tensor(suppress_tokens, V, dev, "suppress_tokens"), _ids_tensor(begin_suppress_tokens, V, dev, "begin_suppress_tokens")
+    start, mult = 0, None
+    if exponential_decay_length_penalty is not None and eos is not None:
+        start, mult = decay_multipliers(exponential_decay_length_penalty, max_new)
+        mult = mult.to(dev)
+    n = lambda t: 0 if t is None else t.numel()  # noqa: E731
+    step_dev = torch.tensor([int(step)], dtype=torch.int32, device=dev)
+    check(lib().ta_logits_step_rules(ptr(logits), ld, V, B, ptr(step_dev), max_new, ptr(forced), n(forced), ptr(eos), n(eos), start,
+                                     ptr(mult), ptr(sup), n(sup), ptr(bsup), n(bsup), stream()), "ta_logits_step_rules")
+    return logits
+
+
+def logits_warp_ext(logits, V, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+    """ta_logits_warp_ext on logits a caller holds, IN PLACE: HF's min-p, typical, epsilon and eta warpers in HF's order with
+    min_tokens_to_keep = 1 (None = off).  Removed entries become -inf, survivors keep their value.  -> logits."""
+    B, V, ld = _logits_rows(logits, V, "logits_warp_ext")
+    a = check_warp_ext(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    check(lib().ta_logits_warp_ext(ptr(logits), ld, V, B, *a, stream()), "ta_logits_warp_ext")
+    return logits
+
+
 # ----------------------------------------------------------------------------- wav2vec2 acoustic model (csrc/wav2vec2.hip)
 def w2v_conv0_gn_gelu(wav, lens, w, gn_w, gn_b, eps=1e-5, out=None, out_rpb=None):
     """ta_w2v_conv0_gn_gelu: conv layer 0 (k 10, stride 5) + per-channel GroupNorm over each clip's own frames + exact GELU.

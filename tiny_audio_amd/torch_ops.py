@@ -14,6 +14,8 @@ reference has no FFI; its seams are nn.Module boundaries,
                                (block Lanczos, tiny_audio_amd/spectral.py)   tiny_audio/diarization.py:91-106
     ta355::token_scores        compute_transition_scores on one step's processed logits (TF:generation/utils.py); the reference
                                asks HF for no scores (tiny_audio/asr_modeling.py:631-637)
+    ta355::logits_sequence_bias, logits_step_rules, logits_warp_ext   HF's remaining single-hypothesis logits processors, which the
+                               reference reaches through **generate_kwargs (tiny_audio/asr_modeling.py:625-637); in place
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
     ta355::encoder_forward_ragged   the same seam, every clip at its own length (opt-in; what the reference computes for a
                                clip encoded alone, tiny_audio/asr_modeling.py:198-200)
@@ -169,6 +171,35 @@ def token_scores(logits: Tensor, chosen: Tensor, V: int, top_k: int) -> Tuple[Te
 def _(logits, chosen, V, top_k):
     B = logits.shape[0]
     return (logits.new_empty((B,)), logits.new_empty((B,)), chosen.new_empty((B, top_k)), logits.new_empty((B, top_k)))
+
+
+# ============================================================================ decoding options
+@torch.library.custom_op("ta355::logits_sequence_bias", mutates_args=("logits",))
+def logits_sequence_bias(logits: Tensor, V: int, context: Tensor, seq_tokens: Tensor, seq_offsets: Tensor, seq_bias: Tensor,
+                         group_starts: Tensor) -> None:
+    """SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor on f32 logits [B, ld] (V valid columns), IN PLACE, given the ids so far
+    ``context`` i64 [B, n] and the four tensors of ``ops.build_sequence_table`` (tokens, offsets, bias, groups) on the same device."""
+    from . import ops
+    tab = dict(tokens=seq_tokens, offsets=seq_offsets, bias=seq_bias, groups=group_starts, n_seq=seq_bias.numel(),
+               n_groups=group_starts.numel() - 1, n_tokens=seq_tokens.numel())
+    ops.logits_sequence_bias(logits, V, context, tab)
+
+
+@torch.library.custom_op("ta355::logits_step_rules", mutates_args=("logits",))
+def logits_step_rules(logits: Tensor, V: int, step: int, max_new: int, forced_eos_ids: Sequence[int], eos_ids: Sequence[int],
+                      decay_start: int, decay_factor: float, suppress_tokens: Sequence[int], begin_suppress_tokens: Sequence[int]) -> None:
+    """ForcedEOSToken, ExponentialDecayLengthPenalty (``decay_start`` < 0 = off), SuppressTokens and SuppressTokensAtBegin on f32 logits
+    [B, ld], IN PLACE, for step ``step`` (tokens generated so far) of ``max_new``; empty lists switch a rule off."""
+    from . import ops
+    ops.logits_step_rules(logits, V, step, max_new, list(forced_eos_ids), list(eos_ids),
+                          None if decay_start < 0 else (decay_start, decay_factor), list(suppress_tokens), list(begin_suppress_tokens))
+
+
+@torch.library.custom_op("ta355::logits_warp_ext", mutates_args=("logits",))
+def logits_warp_ext(logits: Tensor, V: int, min_p: float, typical_p: float, epsilon_cutoff: float, eta_cutoff: float) -> None:
+    """MinP, Typical, Epsilon and Eta warpers on f32 logits [B, ld], IN PLACE, in HF's order (off: 0, 1, 0, 0)."""
+    from . import ops
+    ops.logits_warp_ext(logits, V, min_p, typical_p, epsilon_cutoff, eta_cutoff)
 
 
 # ============================================================================ frozen encoder
@@ -754,4 +785,4 @@ OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backwa
              "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
              "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
-             "spk_panel_update", "spk_panel_combine")
+             "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext")
