@@ -205,20 +205,64 @@ def test_lora_dropout_reproducible_and_eval_untouched():
     assert torch.equal(t1, t0)
 
 
-def test_lora_dropout_ops_pass_opcheck():
-    from tiny_audio_amd import torch_ops
-    cfg = R.SMALL["lm"]
-    lm = _lm(cfg, 8, 32, None, 0.1, _adapters(cfg, 8, None), OW.init_lm(cfg, seed=1))
-    x, att, lab = R.lm_input()
+def _op_inputs(cfg, packed):
+    """-> (ids, src_row, audio f32 [B*L, D], kmask, label rows, label targets, n, pos, seg): the rows of ``R.lm_input()`` or -- ``packed`` --
+    the smallest packed batch tests/test_gpu_packing.py builds (two clips in one row, one clip in the other), inputs_embeds fed as
+    <audio> rows."""
+    if packed:
+        from tests.test_gpu_packing import packed_batch
+        x, sid, lab, _ = packed_batch([[40, 56], [96]], cfg["hidden"], cfg["vocab"])
+        s = torch.from_numpy(sid).to(DEV)
+        kmask = (s != 0).int().contiguous()
+        seg, pos = ops.segment_table(s)
+    else:
+        x, att, lab = R.lm_input()
+        kmask, seg, pos = torch.from_numpy(att).to(DEV).int(), None, None
     B, L, D = x.shape
     ids = torch.full((B, L), cfg["vocab"] - 1, dtype=torch.int64, device=DEV)
     src = torch.arange(B * L, dtype=torch.int32, device=DEV)
     rows, tg, n = ops.label_rows(torch.from_numpy(lab).to(DEV))
-    n = int(n.item())
-    audio = torch.from_numpy(x.reshape(B * L, D)).to(DEV).requires_grad_(True)
-    args = (audio, list(lm.lora_parameters()), torch_ops.register_module(lm), ids, src, torch.from_numpy(att).to(DEV).int(), rows, tg, n,
-            1.0 / n, False, None, 0.1, 12345, 3)
-    torch.library.opcheck(torch.ops.ta355.lm_forward_loss_drop, args, test_utils=("test_schema", "test_faketensor", "test_autograd_registration"))
+    return ids, src, torch.from_numpy(x.reshape(B * L, D)).to(DEV), kmask, rows, tg, int(n.item()), pos, seg
+
+
+def test_lora_dropout_ops_pass_opcheck():
+    """The one LM operator in its three forms: no options, LoRA dropout, a segment table with that dropout."""
+    from tiny_audio_amd import torch_ops
+    cfg = R.SMALL["lm"]
+    lm = _lm(cfg, 8, 32, None, 0.1, _adapters(cfg, 8, None), OW.init_lm(cfg, seed=1))
+    utils = ("test_schema", "test_faketensor", "test_autograd_registration")
+    for packed, options in ((False, ()), (False, (None, 0.1, 12345, 3)), (True, (0.1, 12345, 3))):
+        ids, src, audio, kmask, rows, tg, n, pos, seg = _op_inputs(cfg, packed)
+        args = (audio.requires_grad_(True), list(lm.lora_parameters()), torch_ops.register_module(lm), ids, src, kmask, rows, tg, n, 1.0 / n,
+                False, pos, *((seg,) if packed else ()), *options)
+        torch.library.opcheck(torch.ops.ta355.lm_forward_loss, args, test_utils=utils)
+
+
+@pytest.mark.parametrize("drop", [None, (0.1, 777, 5)], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("packed", [False, True], ids=["rows", "packed"])
+def test_operator_route_equals_the_direct_calls_bit_for_bit(packed, drop):
+    """``FrozenLMLoss.apply`` + ``loss.backward()`` (the custom-operator pair and its autograd node) against ``forward_loss`` /
+    ``backward_from_ctx`` handed the same table and the same (p, seed, offset): both routes issue the same launches with the same
+    arguments and d(loss) is exactly 1, so every result is the same bits (a repeated descriptor reproduces them:
+    test_lora_dropout_reproducible_and_eval_untouched)."""
+    cfg = R.SMALL["lm"]
+    lm = _lm(cfg, 8, 32, None, drop[0] if drop else 0.0, _adapters(cfg, 8, None), OW.init_lm(cfg, seed=1))
+    ids, src, audio, kmask, rows, tg, n, pos, seg = _op_inputs(cfg, packed)
+    loss, nll, logits, ctx = lm.forward_loss(ids, src, audio, kmask, rows, tg, n, 1.0 / n, want_logits=True, pos=pos, lora_dropout=drop, seg=seg)
+    d_audio, _, lg = lm.backward_from_ctx(ctx, audio.shape[0])
+    lm.train()
+    if drop:
+        lm.lora_drop_seed, lm.lora_drop_offset = drop[1], drop[2]
+    a = audio.clone().requires_grad_(True)
+    params = lm.lora_parameters()
+    o_loss, o_nll, o_logits = FrozenLMLoss.apply(a, lm, ids, src, kmask, rows, tg, n, 1.0 / n, True, *params, pos=pos, seg=seg)
+    o_loss.backward()
+    assert lm.lora_drop_offset == (drop[2] + 1 if drop else 0)
+    assert torch.equal(o_loss, loss.reshape(())) and torch.equal(o_nll, nll) and torch.equal(o_logits, logits)
+    assert torch.equal(a.grad, d_audio)
+    assert len(params) == len(lg) == 8
+    for p_, g_ in zip(params, lg):
+        assert g_.abs().sum() > 0 and torch.equal(p_.grad, g_)
 
 
 def test_stage2_trains_with_lora_dropout():

@@ -140,6 +140,31 @@ def test_dropout_call_sequence(dry, monkeypatch):
     assert lm.lora_drop_offset == 2                                  # only training forwards draw
 
 
+def test_backward_keeps_its_forward_stream_modes_behind_66_forwards(dry, monkeypatch):
+    """The stream modes a tape was recorded in travel with its autograd node: 66 outstanding forwards, the modes flipped, and the
+    backward of the FIRST forward still hands ta_lm_backward a handle in that forward's modes (a table of 64 tapes kept beside the
+    module had forgotten it by then and read the tape in the new modes).  The next forward and its backward carry the new ones."""
+    m, batch = _model_and_batch(0.0)
+    lm = m.language_model
+    seen = []
+    stub = dry.ta_lm_backward
+
+    def rec(*args):
+        w = args[0]._obj                                             # the ta_lm_weights this backward was handed
+        seen.append((w.res_f32, w.dx_f32))
+        return stub(*args)
+    monkeypatch.setattr(dry, "ta_lm_backward", rec, raising=False)
+    m.train()
+    outs = [m(**batch) for _ in range(66)]
+    m.config.model_dtype = "float32"                                 # the owner's switch: the next forward runs in fp32 streams ...
+    lm.res_f32 = lm.dx_f32 = True                                    # ... and this is what it sets on the LM
+    outs[0].loss.backward()
+    assert seen == [(0, 0)]
+    assert lm.res_f32 and lm._w.res_f32 == 1 and lm._w.dx_f32 == 1  # the module is left as found
+    m(**batch).loss.backward()
+    assert seen[1:] == [(1, 1)]
+
+
 def test_zero_dropout_issues_todays_calls(dry, monkeypatch):
     rec = _Recorder(dry, monkeypatch)
     seqs = []

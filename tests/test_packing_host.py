@@ -206,6 +206,10 @@ def test_packed_training_step_plumbing(dry, mode):
 
 def test_new_operators_are_registered():
     from tiny_audio_amd import torch_ops
-    assert {"lm_forward_loss_seg", "lm_backward_seg"} <= set(torch_ops.OPERATORS)
-    s = str(torch.ops.ta355.lm_forward_loss_seg.default._schema)
-    assert "Tensor seg" in s and "Tensor? pos" in s
+    assert {"lm_forward_loss", "lm_backward"} <= set(torch_ops.OPERATORS)
+    s = str(torch.ops.ta355.lm_forward_loss.default._schema)
+    assert "Tensor? seg" in s and "Tensor? pos" in s and "float lora_p" in s
+    assert "Tensor? seg" in str(torch.ops.ta355.lm_backward.default._schema)
+    # one pair serves packed rows and LoRA dropout: the per-option copies are gone
+    for gone in (op + option for op in ("lm_forward_loss", "lm_backward") for option in ("_drop", "_seg")):
+        assert not hasattr(torch_ops, gone) and gone not in torch_ops.OPERATORS, gone

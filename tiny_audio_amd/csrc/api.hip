@@ -616,13 +616,6 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
   return TA_OK;
 }
 
-extern "C" int ta_lm_forward_loss(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
-                                  const int* kmask, const int* pos, int B, int L, const int* label_rows,
-                                  const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
-                                  void* logits_out, void* tape, void* ws, long ws_bytes, hipStream_t st) {
-  return ta_lm_forward_loss_ex(w, ids, src_row, audio, kmask, pos, B, L, label_rows, label_targets, n_lab, loss_scale, loss, nll_rows,
-                               logits_out, tape, ws, ws_bytes, nullptr, st);
-}
 // LoRA dropout descriptor -> device form (nullptr = off); TA_ERR_ARG for p outside [0, 1) or p > 0 without adapters
 static int lm_lora_drop(const ta_lm_weights* w, const ta_lora_dropout* drop, LoraDropDev* dd, const LoraDropDev** out) {
   *out = nullptr;
@@ -673,6 +666,13 @@ static int lm_forward_loss_impl(const ta_lm_weights* w, const long* ids, const i
   return TA_OK;
 }
 
+extern "C" int ta_lm_forward_loss(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                                  const int* kmask, const int* pos, int B, int L, const int* label_rows,
+                                  const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
+                                  void* logits_out, void* tape, void* ws, long ws_bytes, hipStream_t st) {
+  return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, nullptr, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
+                              nll_rows, logits_out, tape, ws, ws_bytes, nullptr, st);
+}
 extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
                                      const int* kmask, const int* pos, int B, int L, const int* label_rows,
                                      const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
@@ -738,32 +738,6 @@ extern "C" int ta_lm_prefill(const ta_lm_weights* w, const long* ids, const int*
   return TA_OK;
 }
 
-extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
-                              const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
-                              const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
-                              void* ws, long ws_bytes, hipStream_t st) {
-  return ta_lm_backward_ex(w, src_row, kmask, pos, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids, tape,
-                           ws, ws_bytes, nullptr, st);
-}
-static int lm_backward_impl(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B, int L,
-                            const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
-                            const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
-                            void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st);
-extern "C" int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
-                                 const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
-                                 const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
-                                 void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
-  return lm_backward_impl(w, src_row, kmask, pos, nullptr, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
-                          tape, ws, ws_bytes, drop, st);
-}
-// the backward of a ta_lm_forward_loss_seg forward: the same table (the tape does not hold it)
-extern "C" int ta_lm_backward_seg(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B,
-                                  int L, const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
-                                  const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
-                                  void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
-  return lm_backward_impl(w, src_row, kmask, pos, seg, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
-                          tape, ws, ws_bytes, drop, st);
-}
 static int lm_backward_impl(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B, int L,
                             const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
                             const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
@@ -983,4 +957,27 @@ static int lm_backward_impl(const ta_lm_weights* w, const int* src_row, const in
     RC(ta_i_lora_reduce_parts(rd, w->n_layers, st));
   }
   return TA_OK;
+}
+
+extern "C" int ta_lm_backward(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
+                              const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                              const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                              void* ws, long ws_bytes, hipStream_t st) {
+  return lm_backward_impl(w, src_row, kmask, pos, nullptr, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
+                          tape, ws, ws_bytes, nullptr, st);
+}
+extern "C" int ta_lm_backward_ex(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, int B, int L,
+                                 const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                                 const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                                 void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
+  return lm_backward_impl(w, src_row, kmask, pos, nullptr, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
+                          tape, ws, ws_bytes, drop, st);
+}
+// the backward of a ta_lm_forward_loss_seg forward: the same table (the tape does not hold it)
+extern "C" int ta_lm_backward_seg(const ta_lm_weights* w, const int* src_row, const int* kmask, const int* pos, const int* seg, int B,
+                                  int L, const int* label_rows, int n_lab, float* d_audio, long n_audio_rows, float* d_embeds,
+                                  const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wg, const long* ids, const void* tape,
+                                  void* ws, long ws_bytes, const ta_lora_dropout* drop, hipStream_t st) {
+  return lm_backward_impl(w, src_row, kmask, pos, seg, B, L, label_rows, n_lab, d_audio, n_audio_rows, d_embeds, lora_grads, wg, ids,
+                          tape, ws, ws_bytes, drop, st);
 }

@@ -56,7 +56,6 @@ class Qwen3MI355X(torch.nn.Module):
         self._ft_versions = None
         self.accumulate_into_grad = False   # trainer opt-in: weight gradients are added straight into Parameter.grad
         self._res_f32 = self._dx_f32 = False   # storage of the residual / d(x) streams (ta_lm_weights.res_f32 / dx_f32): bf16
-        self._tape_modes = {}
 
     # ------------------------------------------------------------------ LoRA (stage 2; asr_modeling.py:289-301)
     # storage of the forward residual stream (+ its tape rows) and of the backward d(x) stream: fields of THIS model's weights handle
@@ -541,32 +540,16 @@ class Qwen3MI355X(torch.nn.Module):
         loss = torch.zeros(1, device=dev, dtype=F32)
         nll = torch.empty(max(n_label_rows, 1), device=dev, dtype=F32)
         logits = torch.empty((B * L, self.vocab_pad), device=dev, dtype=BF16) if want_logits else None
-        drop = _lora_drop_desc(lora_dropout)
-        if seg is not None:
-            if seg.dtype != torch.int32 or seg.numel() != 2 * B * L or not seg.is_contiguous():
-                raise ValueError(f"seg must be a contiguous int32 [2, {B * L}] segment table; got {seg.dtype} {tuple(seg.shape)}")
-            _lib.check(L_.ta_lm_forward_loss_seg(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos), ptr(seg),
-                                                 B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
-                                                 ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(),
-                                                 None if drop is None else C.byref(drop), stream()), "ta_lm_forward_loss_seg")
-        elif drop is None:
-            _lib.check(L_.ta_lm_forward_loss(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos),
-                                             B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
-                                             ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), stream()),
-                       "ta_lm_forward_loss")
-        else:
-            _lib.check(L_.ta_lm_forward_loss_ex(C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos),
-                                                B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss),
-                                                ptr(nll), ptr(logits), ptr(tape), ptr(ws), ws.numel(), C.byref(drop), stream()),
-                       "ta_lm_forward_loss_ex")
+        if seg is not None and (seg.dtype != torch.int32 or seg.numel() != 2 * B * L or not seg.is_contiguous()):
+            raise ValueError(f"seg must be a contiguous int32 [2, {B * L}] segment table; got {seg.dtype} {tuple(seg.shape)}")
+        _lm_call("forward", (C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos)), seg,
+                 (B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss), ptr(nll), ptr(logits), ptr(tape),
+                  ptr(ws), ws.numel()), _lora_drop_desc(lora_dropout))
+        # ``modes``: the tape's residual-stream rows are in the storage dtype this handle carries NOW; the backward must read them as
+        # that even if the owner flips ``res_f32`` in between
         ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
-                   n_label_rows=n_label_rows, ids=input_ids, lora_dropout=lora_dropout, seg=seg)
-        # The tape's residual-stream rows are in the storage dtype this handle carried NOW: the backward must read them as that even
-        # if the owner flips ``res_f32`` in between.  Keyed by the tape's address, since the custom operator hands the backward only
-        # tensors.
-        if len(self._tape_modes) > 64:
-            self._tape_modes.clear()
-        self._tape_modes[tape.data_ptr()] = (int(self._w.res_f32), int(self._w.dx_f32))
+                   n_label_rows=n_label_rows, ids=input_ids, lora_dropout=lora_dropout, seg=seg,
+                   modes=(bool(self._w.res_f32), bool(self._w.dx_f32)))
         return loss, nll, logits, ctx
 
     def backward_from_ctx(self, ctx, n_audio_rows, want_d_embeds=False, want_d_audio=True):
@@ -605,33 +588,16 @@ class Qwen3MI355X(torch.nn.Module):
             keep = (arr, bufs)
             lg = [None] * len(ps) if direct else bufs
         w = self._w
-        recorded = self._tape_modes.pop(ctx["tape"].data_ptr(), None)
-        if recorded is not None and recorded != (int(w.res_f32), int(w.dx_f32)):
+        if ctx["modes"] != (bool(w.res_f32), bool(w.dx_f32)):
             w = _lib.LmWeights.from_buffer_copy(self._w)          # same pointers, the modes the forward ran in
-            w.res_f32, w.dx_f32 = recorded
-        drop = _lora_drop_desc(ctx.get("lora_dropout"))       # the descriptor its forward ran with
-        if ctx.get("seg") is not None:                        # ... and the segment table
-            _lib.check(_lib.lib().ta_lm_backward_seg(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]), ptr(ctx["seg"]),
-                                                     ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
-                                                     ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
-                                                     None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
-                                                     ptr(ctx["ws"]), ctx["ws"].numel(), None if drop is None else C.byref(drop), stream()),
-                       "ta_lm_backward_seg")
-        elif drop is None:
-            _lib.check(_lib.lib().ta_lm_backward(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]),
-                                                 ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
-                                                 ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
-                                                 None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
-                                                 ptr(ctx["ws"]), ctx["ws"].numel(), stream()), "ta_lm_backward")
-        else:
-            _lib.check(_lib.lib().ta_lm_backward_ex(C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"]),
-                                                    ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"],
-                                                    ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
-                                                    None if wg is None else C.byref(wg), ptr(ctx.get("ids")), ptr(ctx["tape"]),
-                                                    ptr(ctx["ws"]), ctx["ws"].numel(), C.byref(drop), stream()), "ta_lm_backward_ex")
+            w.res_f32, w.dx_f32 = (int(v) for v in ctx["modes"])
+        # ... with the segment table and the dropout descriptor its forward ran with
+        _lm_call("backward", (C.byref(w), ptr(ctx["src_row"]), ptr(ctx["kmask"]), ptr(ctx["pos"])), ctx["seg"],
+                 (ctx["B"], ctx["L"], ptr(ctx["label_rows"]), ctx["n_label_rows"], ptr(d_audio), n_audio_rows, ptr(d_emb), lg_arr,
+                  None if wg is None else C.byref(wg), ptr(ctx["ids"]), ptr(ctx["tape"]), ptr(ctx["ws"]), ctx["ws"].numel()),
+                 _lora_drop_desc(ctx["lora_dropout"]))
         del keep
         return d_audio, d_emb, lg
-
 
     # ------------------------------------------------------------------ greedy decoding
     @torch.no_grad()
@@ -855,10 +821,33 @@ def _lora_drop_desc(d):
     return _lib.LoraDropout(p=float(d[0]), seed=int(d[1]) & 0xFFFFFFFFFFFFFFFF, offset=int(d[2]) & 0xFFFFFFFFFFFFFFFF)
 
 
+_LM_ENTRY = {"forward": ("ta_lm_forward_loss", "ta_lm_forward_loss_ex", "ta_lm_forward_loss_seg"),
+             "backward": ("ta_lm_backward", "ta_lm_backward_ex", "ta_lm_backward_seg")}
+
+
+def _lm_call(direction, head, seg, tail, drop):
+    """Run the LM entry point of ``direction`` that (seg, drop) select: the plain one with neither, _ex with a dropout descriptor only,
+    _seg with a segment table (its descriptor may be NULL).  All three take ``head`` (... pos), then the table, then ``tail``
+    (B ... ws_bytes), then the descriptor, then the stream."""
+    plain, ex, packed = _LM_ENTRY[direction]
+    d = None if drop is None else C.byref(drop)
+    if seg is not None:
+        name, args = packed, (*head, ptr(seg), *tail, d, stream())
+    elif drop is not None:
+        name, args = ex, (*head, *tail, d, stream())
+    else:
+        name, args = plain, (*head, *tail, stream())
+    _lib.check(getattr(_lib.lib(), name)(*args), name)
+
+
 class FrozenLMLoss:
     """loss = CE(frozen_LM(embed(ids) with <audio> rows := audio_embeds)) through ``torch.ops.ta355.lm_forward_loss``
     (torch_ops.py); grad flows to audio_embeds and to the trainable LM tensors passed as trailing inputs -- the LoRA masters
     (``*lm.lora_parameters()``) or, with a trainable base LM, its fp32 masters (``*lm.ft_parameters()``).
+
+    One operator pair (``lm_forward_loss`` / ``lm_backward``) serves every configuration: ``seg`` (the table of
+    ``ops.segment_table``) selects packed rows, and the (p, seed, offset) of ``lm.next_lora_dropout()`` selects LoRA dropout, p = 0
+    being "off".  The autograd node keeps both, and the two residual-stream modes the forward ran in, for ITS backward.
 
     accumulate_into_grad (full decoder fine-tuning under ASRTrainer): the kernels add the LM's weight gradients straight
     into the trainer's flat buffer, so d(loss) cannot be applied to them afterwards.  ASRTrainer is the only caller that
@@ -869,19 +858,11 @@ class FrozenLMLoss:
     def apply(audio_embeds, lm, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
               want_logits, *trainable, pos=None, seg=None):
         from . import torch_ops
-        drop = lm.next_lora_dropout()                 # training forwards of a p > 0 model only: a fresh Philox offset each
-        if seg is not None:                           # packed rows: one operator pair, with or without dropout (p = 0: off)
-            loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss_seg(
-                audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
-                int(n_label_rows), float(loss_scale), bool(want_logits), pos, seg, *(drop or (0.0, 0, 0)))
-        elif drop is None:
-            loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss(
-                audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
-                int(n_label_rows), float(loss_scale), bool(want_logits), pos)
-        else:
-            loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss_drop(
-                audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
-                int(n_label_rows), float(loss_scale), bool(want_logits), pos, *drop)
+        # training forwards of a p > 0 model only: a fresh Philox offset each; lora_p = 0 is "no dropout"
+        drop = lm.next_lora_dropout() or (0.0, 0, 0)
+        loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss(
+            audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
+            int(n_label_rows), float(loss_scale), bool(want_logits), pos, seg, *drop)
         # a fresh tensor: the outputs of a multi-output custom op may not be modified in place, and HF Trainer does
         # `loss *= ...` on what the model returns (TF:trainer.py compute_loss)
         return loss.clone(), nll, logits

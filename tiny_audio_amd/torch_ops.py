@@ -564,21 +564,27 @@ moe_projector.register_autograd(_moe_bwd, setup_context=_moe_setup)
 @torch.library.custom_op("ta355::lm_forward_loss", mutates_args=())
 def lm_forward_loss(audio: Tensor, trainable: Sequence[Tensor], handle: int, input_ids: Tensor, src_row: Optional[Tensor],
                     kmask: Optional[Tensor], label_rows: Optional[Tensor], label_targets: Optional[Tensor], n_label_rows: int,
-                    loss_scale: float, want_logits: bool, pos: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+                    loss_scale: float, want_logits: bool, pos: Optional[Tensor], seg: Optional[Tensor] = None, lora_p: float = 0.0,
+                    lora_seed: int = 0, lora_offset: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """-> (loss f32 [], per-row nll f32 [max(n, 1)], logits bf16 [B*L, vocab_pad] or empty, tape, workspace).
     ``audio`` f32 [rows, D]: the projector's output rows that replace the <audio> positions (``src_row`` from
     ta_audio_index); ``trainable``: the LoRA masters or, with a trainable base LM, its fp32 masters (autograd inputs);
-    ``pos`` int32 [B*L]: RoPE position of every token row (the reference's ``position_ids``; None = arange(L) per clip)."""
+    ``pos`` int32 [B*L]: RoPE position of every token row (the reference's ``position_ids``; None = arange(L) per clip);
+    ``seg`` int32 [2, B*L]: the table of ops.segment_table for packed rows (block-diagonal attention inside every row; None = one
+    clip per row); ``lora_p``, ``lora_seed``, ``lora_offset``: LoRA dropout (peft lora_dropout p > 0, training forwards), the triple
+    that names the Philox masks (include/ta355.h ta_lora_dropout); lora_p == 0 is "no dropout".  The autograd node keeps the table,
+    the triple and the module's two stream modes and hands them to ITS backward, so gradient accumulation and backwards run out
+    of order regenerate the right masks and read the tape as it was recorded."""
     lm = module_of(handle)
     a = audio.detach().to(F32).contiguous()
     loss, nll, logits, c = lm.forward_loss(input_ids, src_row, a, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits,
-                                           pos=pos)
+                                           pos=pos, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg)
     return loss.reshape(()), nll, (logits if logits is not None else _empty(a.device)), c["tape"], c["ws"]
 
 
 @lm_forward_loss.register_fake
-def _lm_fwd_fake(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits,
-                 pos):
+def _(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits, pos,
+      seg=None, lora_p=0.0, lora_seed=0, lora_offset=0):
     lm = module_of(handle)
     B, L = input_ids.shape
     logits = audio.new_empty((B * L, lm.vocab_pad), dtype=BF16) if want_logits else audio.new_empty((0,))
@@ -592,13 +598,17 @@ def _lm_fwd_fake(audio, trainable, handle, input_ids, src_row, kmask, label_rows
 @torch.library.custom_op("ta355::lm_backward", mutates_args=())
 def lm_backward(tape: Tensor, ws: Tensor, handle: int, input_ids: Tensor, src_row: Optional[Tensor], kmask: Optional[Tensor],
                 label_rows: Optional[Tensor], n_label_rows: int, n_audio_rows: int, want_d_audio: bool,
-                pos: Optional[Tensor]) -> List[Tensor]:
+                pos: Optional[Tensor], seg: Optional[Tensor] = None, lora_p: float = 0.0, lora_seed: int = 0, lora_offset: int = 0,
+                res_f32: bool = False, dx_f32: bool = False) -> List[Tensor]:
     """loss.backward() through the LM for d(loss) = 1 -> [d_audio f32 [n_audio_rows, D] (or empty), then one gradient per
-    tensor of ``trainable`` (empty tensors when the LM accumulates straight into Parameter.grad: ASRTrainer's mode)]."""
+    tensor of ``trainable`` (empty tensors when the LM accumulates straight into Parameter.grad: ASRTrainer's mode)].
+    ``seg``, ``lora_p``, ``lora_seed``, ``lora_offset``: what the forward was given; ``res_f32``, ``dx_f32``: the stream modes the
+    forward recorded ``tape`` in."""
     lm = module_of(handle)
     B, L = input_ids.shape
     ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
-               n_label_rows=n_label_rows, ids=input_ids)
+               n_label_rows=n_label_rows, ids=input_ids, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg,
+               modes=(res_f32, dx_f32))
     d_audio, _, lg = lm.backward_from_ctx(ctx, n_audio_rows, want_d_audio=want_d_audio)
     dev = tape.device
     out = [d_audio if d_audio is not None else _empty(dev)]
@@ -608,7 +618,8 @@ def lm_backward(tape: Tensor, ws: Tensor, handle: int, input_ids: Tensor, src_ro
 
 
 @lm_backward.register_fake
-def _lm_bwd_fake(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos):
+def _(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos, seg=None, lora_p=0.0,
+      lora_seed=0, lora_offset=0, res_f32=False, dx_f32=False):
     lm = module_of(handle)
     f = lambda *s: tape.new_empty(s, dtype=F32)
     ps = lm.lora_parameters() or lm.ft_parameters() or []
@@ -616,173 +627,44 @@ def _lm_bwd_fake(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_labe
 
 
 def _lm_setup(ctx, inputs, output):
-    (audio, trainable, handle, input_ids, src_row, kmask, label_rows, _targets, n_label_rows, _scale, _want, pos) = inputs
+    (audio, trainable, handle, input_ids, src_row, kmask, label_rows, _targets, n_label_rows, _scale, _want, pos, seg, *drop) = inputs
     ctx.handle, ctx.n_label_rows, ctx.n_audio, ctx.n_train = handle, n_label_rows, audio.shape[0], len(trainable)
+    ctx.drop = tuple(drop)
     ctx.module = module_of(handle)
+    # this runs on the forward's thread, directly behind the forward: the stream modes its tape was recorded in
+    ctx.modes = (ctx.module.res_f32, ctx.module.dx_f32)
     ctx.want_d_audio = audio.requires_grad
     # without this autograd materialises ZERO gradients for the unused outputs on every backward -- the tape alone is
     # 8.9 GB at B = 32 (a 1.35 ms fill per step, measured), the workspace 1.2 GB
     ctx.set_materialize_grads(False)
-    ctx.present = [t is not None for t in (src_row, kmask, label_rows, pos)]
-    ctx.save_for_backward(output[3], output[4], input_ids, *[t for t in (src_row, kmask, label_rows, pos) if t is not None])
+    optional = (src_row, kmask, label_rows, pos, seg)
+    ctx.present = [t is not None for t in optional]
+    ctx.save_for_backward(output[3], output[4], input_ids, *[t for t in optional if t is not None])
 
 
 def _lm_bwd(ctx, g_loss, _g_nll, _g_logits, _g_tape, _g_ws):
+    # every input behind (audio, trainable), as many as this call was dispatched with: trailing arguments that equal their defaults
+    # are not among them
+    rest_none = (None,) * (len(ctx.needs_input_grad) - 2)
     if g_loss is None:                                        # the loss was not used
-        return (None, [None] * ctx.n_train) + (None,) * 10
+        return (None, [None] * ctx.n_train) + rest_none
     tape, ws, ids, *rest = ctx.saved_tensors
     it = iter(rest)
-    src_row, kmask, label_rows, pos = (next(it) if p else None for p in ctx.present)
+    src_row, kmask, label_rows, pos, seg = (next(it) if p else None for p in ctx.present)
     out = torch.ops.ta355.lm_backward(tape, ws, ctx.handle, ids, src_row, kmask, label_rows, ctx.n_label_rows, ctx.n_audio,
-                                      ctx.want_d_audio, pos)
+                                      ctx.want_d_audio, pos, seg, *ctx.drop, *ctx.modes)
     d_audio = out[0] * g_loss if ctx.want_d_audio else None
     # gradients of the trainable LM tensors: scaled by d(loss) -- except in accumulate_into_grad mode, where the kernels
     # have already added them to Parameter.grad (empty placeholders come back) and d(loss) is 1 by ASRTrainer's contract
     tg = [(g * g_loss if g.numel() else None) for g in out[1:]]
     tg += [None] * (ctx.n_train - len(tg))
-    return (d_audio, tg[: ctx.n_train]) + (None,) * 10
+    return (d_audio, tg[: ctx.n_train]) + rest_none
 
 
 lm_forward_loss.register_autograd(_lm_bwd, setup_context=_lm_setup)
 
 
-# ---- the same pair under LoRA dropout (peft lora_dropout p > 0, training forwards): (p, seed, offset) name the Philox masks
-# (include/ta355.h ta_lora_dropout).  The autograd node keeps the forward's triple and hands it to ITS backward, so gradient
-# accumulation and backwards run out of order regenerate the right masks.
-@torch.library.custom_op("ta355::lm_forward_loss_drop", mutates_args=())
-def lm_forward_loss_drop(audio: Tensor, trainable: Sequence[Tensor], handle: int, input_ids: Tensor, src_row: Optional[Tensor],
-                         kmask: Optional[Tensor], label_rows: Optional[Tensor], label_targets: Optional[Tensor], n_label_rows: int,
-                         loss_scale: float, want_logits: bool, pos: Optional[Tensor], lora_p: float, lora_seed: int,
-                         lora_offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """``lm_forward_loss`` with LoRA dropout (p, seed, offset)."""
-    lm = module_of(handle)
-    a = audio.detach().to(F32).contiguous()
-    loss, nll, logits, c = lm.forward_loss(input_ids, src_row, a, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits,
-                                           pos=pos, lora_dropout=(lora_p, lora_seed, lora_offset))
-    return loss.reshape(()), nll, (logits if logits is not None else _empty(a.device)), c["tape"], c["ws"]
-
-
-@lm_forward_loss_drop.register_fake
-def _(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits, pos,
-      lora_p, lora_seed, lora_offset):
-    return _lm_fwd_fake(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-                        want_logits, pos)
-
-
-@torch.library.custom_op("ta355::lm_backward_drop", mutates_args=())
-def lm_backward_drop(tape: Tensor, ws: Tensor, handle: int, input_ids: Tensor, src_row: Optional[Tensor], kmask: Optional[Tensor],
-                     label_rows: Optional[Tensor], n_label_rows: int, n_audio_rows: int, want_d_audio: bool,
-                     pos: Optional[Tensor], lora_p: float, lora_seed: int, lora_offset: int) -> List[Tensor]:
-    """``lm_backward`` of a ``lm_forward_loss_drop`` forward: the same (p, seed, offset)."""
-    lm = module_of(handle)
-    B, L = input_ids.shape
-    ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
-               n_label_rows=n_label_rows, ids=input_ids, lora_dropout=(lora_p, lora_seed, lora_offset))
-    d_audio, _, lg = lm.backward_from_ctx(ctx, n_audio_rows, want_d_audio=want_d_audio)
-    dev = tape.device
-    out = [d_audio if d_audio is not None else _empty(dev)]
-    for g in (lg or []):
-        out.append(g if g is not None else _empty(dev))
-    return out
-
-
-@lm_backward_drop.register_fake
-def _(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos, lora_p, lora_seed,
-      lora_offset):
-    return _lm_bwd_fake(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos)
-
-
-def _lm_drop_setup(ctx, inputs, output):
-    _lm_setup(ctx, inputs[:12], output)
-    ctx.drop = tuple(inputs[12:15])
-
-
-def _lm_drop_bwd(ctx, g_loss, _g_nll, _g_logits, _g_tape, _g_ws):
-    if g_loss is None:
-        return (None, [None] * ctx.n_train) + (None,) * 13
-    tape, ws, ids, *rest = ctx.saved_tensors
-    it = iter(rest)
-    src_row, kmask, label_rows, pos = (next(it) if p else None for p in ctx.present)
-    out = torch.ops.ta355.lm_backward_drop(tape, ws, ctx.handle, ids, src_row, kmask, label_rows, ctx.n_label_rows, ctx.n_audio,
-                                           ctx.want_d_audio, pos, *ctx.drop)
-    d_audio = out[0] * g_loss if ctx.want_d_audio else None
-    tg = [(g * g_loss if g.numel() else None) for g in out[1:]]
-    tg += [None] * (ctx.n_train - len(tg))
-    return (d_audio, tg[: ctx.n_train]) + (None,) * 13
-
-
-lm_forward_loss_drop.register_autograd(_lm_drop_bwd, setup_context=_lm_drop_setup)
-
-# ---- the same pair over packed rows (sequence packing): ``seg`` int32 [2, B*L] is the table of ops.segment_table.  One pair serves
-# both dropout settings -- lora_p == 0 is "no dropout", the library's _seg entry points take an optional descriptor.
-@torch.library.custom_op("ta355::lm_forward_loss_seg", mutates_args=())
-def lm_forward_loss_seg(audio: Tensor, trainable: Sequence[Tensor], handle: int, input_ids: Tensor, src_row: Optional[Tensor],
-                        kmask: Optional[Tensor], label_rows: Optional[Tensor], label_targets: Optional[Tensor], n_label_rows: int,
-                        loss_scale: float, want_logits: bool, pos: Optional[Tensor], seg: Tensor, lora_p: float, lora_seed: int,
-                        lora_offset: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """``lm_forward_loss`` with block-diagonal attention inside every row."""
-    lm = module_of(handle)
-    a = audio.detach().to(F32).contiguous()
-    loss, nll, logits, c = lm.forward_loss(input_ids, src_row, a, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits,
-                                           pos=pos, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg)
-    return loss.reshape(()), nll, (logits if logits is not None else _empty(a.device)), c["tape"], c["ws"]
-
-
-@lm_forward_loss_seg.register_fake
-def _(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits, pos, seg,
-      lora_p, lora_seed, lora_offset):
-    return _lm_fwd_fake(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-                        want_logits, pos)
-
-
-@torch.library.custom_op("ta355::lm_backward_seg", mutates_args=())
-def lm_backward_seg(tape: Tensor, ws: Tensor, handle: int, input_ids: Tensor, src_row: Optional[Tensor], kmask: Optional[Tensor],
-                    label_rows: Optional[Tensor], n_label_rows: int, n_audio_rows: int, want_d_audio: bool,
-                    pos: Optional[Tensor], seg: Tensor, lora_p: float, lora_seed: int, lora_offset: int) -> List[Tensor]:
-    """``lm_backward`` of a ``lm_forward_loss_seg`` forward: the same table, the same (p, seed, offset)."""
-    lm = module_of(handle)
-    B, L = input_ids.shape
-    ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
-               n_label_rows=n_label_rows, ids=input_ids, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg)
-    d_audio, _, lg = lm.backward_from_ctx(ctx, n_audio_rows, want_d_audio=want_d_audio)
-    dev = tape.device
-    out = [d_audio if d_audio is not None else _empty(dev)]
-    for g in (lg or []):
-        out.append(g if g is not None else _empty(dev))
-    return out
-
-
-@lm_backward_seg.register_fake
-def _(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos, seg, lora_p, lora_seed,
-      lora_offset):
-    return _lm_bwd_fake(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_audio_rows, want_d_audio, pos)
-
-
-def _lm_seg_setup(ctx, inputs, output):
-    _lm_setup(ctx, inputs[:12], output)
-    ctx.drop = tuple(inputs[13:16])
-    src_row, kmask, label_rows, pos = inputs[4], inputs[5], inputs[6], inputs[11]
-    ctx.save_for_backward(output[3], output[4], inputs[3], inputs[12], *[t for t in (src_row, kmask, label_rows, pos) if t is not None])
-
-
-def _lm_seg_bwd(ctx, g_loss, _g_nll, _g_logits, _g_tape, _g_ws):
-    if g_loss is None:
-        return (None, [None] * ctx.n_train) + (None,) * 14
-    tape, ws, ids, seg, *rest = ctx.saved_tensors
-    it = iter(rest)
-    src_row, kmask, label_rows, pos = (next(it) if p else None for p in ctx.present)
-    out = torch.ops.ta355.lm_backward_seg(tape, ws, ctx.handle, ids, src_row, kmask, label_rows, ctx.n_label_rows, ctx.n_audio,
-                                          ctx.want_d_audio, pos, seg, *ctx.drop)
-    d_audio = out[0] * g_loss if ctx.want_d_audio else None
-    tg = [(g * g_loss if g.numel() else None) for g in out[1:]]
-    tg += [None] * (ctx.n_train - len(tg))
-    return (d_audio, tg[: ctx.n_train]) + (None,) * 14
-
-
-lm_forward_loss_seg.register_autograd(_lm_seg_bwd, setup_context=_lm_seg_setup)
-
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
-             "lm_forward_loss", "lm_backward", "lm_forward_loss_drop", "lm_backward_drop", "whisper_encoder_forward",
-             "lm_forward_loss_seg", "lm_backward_seg", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
+             "lm_forward_loss", "lm_backward", "whisper_encoder_forward", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
              "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext")
