@@ -850,6 +850,38 @@ int ta_ctc_align_f32(const float* emission, long ld, int C, const int* cu_frames
                      int max_T, int max_J, int blank_id, int* frames, float* score, int* status, void* ws, long ws_bytes,
                      float* trellis_out, const long* trellis_off, hipStream_t st);
 
+/* ---- forced alignment, long form: the same alignment for transcripts beyond TA_ALIGN_MAX_TOKENS and recordings beyond
+ * TA_ALIGN_MAX_FRAMES (tiny_audio_amd/csrc/align_long.hip) -- the whole-recording call ForcedAligner.align(whole_audio, whole_text) of
+ * the reference's pipeline (tiny_audio/asr_pipeline.py:117-131; trellis and walk tiny_audio/alignment.py:47-152).  Contract: that of
+ * ta_ctc_align_f32 in every respect (tests/align_ref.py; DESIGN.md section 3, "Forced alignment", "Long form"): the same ragged
+ * layout, the same f32 recurrence with one f32 add per candidate, ties to moving, the same status 0 / 1 / 2, frames strictly
+ * increasing and written for status 0 only, score = trellis[T_n, J_n], J_n = 0 legal, trellis_out / trellis_off as there.  The
+ * results are the reference's bytes, and on any clip inside the old envelope the bytes ta_ctc_align_f32 gives.
+ * A clip's trellis is cut into tiles of col_block columns by frame_block frames (0 = the defaults below; col_block a multiple of 64
+ * up to TA_ALIGN_LONG_MAX_COL_BLOCK, frame_block >= 1, else TA_ERR_ARG; the results do not depend on either).  Launch k runs every
+ * tile (cb, fb) with cb + fb == k of every clip, one workgroup per tile; a tile's entering row and the column to its left reach it
+ * through the workspace from the launch before, so ceil((max_J + 1) / col_block) + ceil(max_T / frame_block) - 1 tile launches on
+ * `st`, one launch before them (the per-clip checks) and one after (the walk, one wave per clip) make the call.  No kernel waits
+ * for another workgroup.
+ * ws: ta_ctc_align_long_workspace_bytes(N, max_T, max_J, col_block, frame_block) bytes (-1 for a tiling that would be refused),
+ * no initial contents required: the decision bits, max_T * ceil((max_J + 1) / 64) * 8 bytes per clip (1.35 GB for max_T = 180 000,
+ * max_J = 60 000; 34 GB at the limits), and the two carries, (col_block + max_T) * ceil((max_J + 1) / col_block) floats per clip.
+ * Limits (TA_ERR_ARG beyond them): N <= TA_ALIGN_LONG_MAX_CLIPS, max_T <= TA_ALIGN_LONG_MAX_FRAMES (5.8 h of 20 ms frames),
+ * max_J <= TA_ALIGN_LONG_MAX_TOKENS, C <= TA_ALIGN_LONG_MAX_CLASSES; also 0 <= blank_id < C <= ld.
+ * The trellis is f32, as the reference's is: at one hour |trellis| is around 2e5, where one ulp is about 0.016, so late decisions
+ * between candidates closer than that are decided by rounding -- identically here and in the reference; nothing is renormalised. */
+#define TA_ALIGN_LONG_MAX_TOKENS 262144
+#define TA_ALIGN_LONG_MAX_FRAMES 1048576
+#define TA_ALIGN_LONG_MAX_CLASSES 65536
+#define TA_ALIGN_LONG_MAX_CLIPS 64
+#define TA_ALIGN_LONG_MAX_COL_BLOCK 2048   /* a tile's two rows, column ids and staged emissions fit one workgroup's LDS */
+#define TA_ALIGN_LONG_COL_BLOCK 256        /* the default tile: the best of those measured (profiles/forced_alignment.md) */
+#define TA_ALIGN_LONG_FRAME_BLOCK 64
+long ta_ctc_align_long_workspace_bytes(int N, int max_T, int max_J, int col_block, int frame_block);
+int ta_ctc_align_long_f32(const float* emission, long ld, int C, const int* cu_frames, const int* tokens, const int* cu_tokens, int N,
+                          int max_T, int max_J, int blank_id, int col_block, int frame_block, int* frames, float* score, int* status,
+                          void* ws, long ws_bytes, float* trellis_out, const long* trellis_off, hipStream_t st);
+
 /* ---- frozen wav2vec2-base CTC acoustic model: the front half of forced alignment (tiny_audio_amd/csrc/wav2vec2.hip).  Replaces the
  * torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax the reference runs through PyTorch in ForcedAligner.align
  * (tiny_audio/alignment.py:206-211).  Arithmetic of Wav2Vec2ForCTC.forward (TF:models/wav2vec2/modeling_wav2vec2.py:1667-1700; feature encoder :382-419, projection :422-434,

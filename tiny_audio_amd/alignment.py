@@ -14,6 +14,11 @@ The wav2vec2 acoustic model is part of this library as an opt-in: ``align(audio,
 ``align_audio_batch(audios, texts, m)`` take a ``wav2vec2.Wav2Vec2CtcMI355X`` and go waveform -> emissions -> trellis on the device
 with no host round trip of the emissions.  ``align(..., emission=...)`` and ``align_batch`` take emissions computed elsewhere;
 with neither, ``align`` runs torchaudio's bundle through PyTorch as the reference does, and needs torchaudio installed.
+
+Those calls stop at 2048 tokens and 32768 frames per clip (one workgroup per clip).  A whole recording against its whole transcript
+-- the call the reference's pipeline makes (tiny_audio/asr_pipeline.py:117-131) -- goes through the explicit long form,
+``align_long`` / ``align_long_batch`` (``torch.ops.ta355.ctc_align_long``, csrc/align_long.hip: the same trellis as a tiled wavefront
+of launches, the same bytes), with ``Wav2Vec2CtcMI355X.emissions_long`` for the emissions.  The short calls never dispatch to it.
 """
 from __future__ import annotations
 
@@ -24,7 +29,7 @@ import torch
 
 from . import _lib
 from . import torch_ops  # noqa: F401  (registers torch.ops.ta355.ctc_align)
-from .ops import ALIGN_LIMITS
+from .ops import ALIGN_LIMITS, ALIGN_LONG_LIMITS
 
 # torchaudio.pipelines.WAV2VEC2_ASR_BASE_960H.get_labels(): blank, the word separator, then the letters by frequency
 LABELS = ("-", "|", "E", "T", "A", "O", "N", "I", "H", "S", "R", "D", "L", "U", "M", "W", "C", "F", "G", "Y", "P", "B", "V", "K", "'",
@@ -112,6 +117,64 @@ def _launch_flat(em: torch.Tensor, Ts: Sequence[int], tokens: Sequence[Sequence[
         tc = trellis.cpu()
         trs = [tc[off[n]:off[n + 1]].reshape(Ts[n] + 1, Js[n] + 1).clone() for n in range(N)]
     return per_clip, score, status, trs
+
+
+def _check_clip_long(emission: torch.Tensor, tokens: Sequence[int], blank_id: int) -> None:
+    """``_check_clip`` against the long form's envelope (``ops.ALIGN_LONG_LIMITS``)."""
+    if emission.dim() != 2:
+        raise ValueError(f"emission must be [frames, classes], got {tuple(emission.shape)}")
+    T, C = emission.shape
+    if not 1 <= C <= ALIGN_LONG_LIMITS["classes"]:
+        raise ValueError(f"{C} classes: the long alignment kernel takes 1 .. {ALIGN_LONG_LIMITS['classes']} classes")
+    if T > ALIGN_LONG_LIMITS["frames"]:
+        raise ValueError(f"{T} frames: the long alignment kernel takes at most {ALIGN_LONG_LIMITS['frames']} frames per clip")
+    if len(tokens) > ALIGN_LONG_LIMITS["tokens"]:
+        raise ValueError(f"{len(tokens)} tokens: the long alignment kernel takes at most {ALIGN_LONG_LIMITS['tokens']} tokens per clip")
+    if not 0 <= int(blank_id) < C:
+        raise ValueError(f"blank_id {blank_id} is outside [0, {C})")
+    tk = np.asarray(tokens, np.int64).reshape(-1)
+    bad = np.flatnonzero((tk < 0) | (tk >= C))
+    if bad.size:
+        raise ValueError(f"token {int(bad[0])} has id {int(tk[bad[0]])}, outside [0, {C})")
+
+
+def _check_tile(col_block: int, frame_block: int) -> None:
+    if col_block < 0 or col_block % 64 or col_block > ALIGN_LONG_LIMITS["col_block"]:
+        raise ValueError(f"col_block {col_block}: a multiple of 64 up to {ALIGN_LONG_LIMITS['col_block']}, or 0 for the default")
+    if frame_block < 0:
+        raise ValueError(f"frame_block {frame_block}: at least 1, or 0 for the default")
+
+
+def _launch_long(emissions: Sequence[torch.Tensor], tokens: Sequence[Sequence[int]], blank_id: int, col_block: int = 0,
+                 frame_block: int = 0):
+    """``_launch`` through ``torch.ops.ta355.ctc_align_long`` -> (frames per clip, score, status) on the host."""
+    N = len(emissions)
+    if N != len(tokens):
+        raise ValueError(f"{N} emission matrices but {len(tokens)} token sequences")
+    if N > ALIGN_LONG_LIMITS["clips"]:
+        raise ValueError(f"{N} clips: the long alignment kernel takes at most {ALIGN_LONG_LIMITS['clips']} clips per call")
+    _check_tile(int(col_block), int(frame_block))
+    if N == 0:
+        return [], [], []
+    for e, tk in zip(emissions, tokens):
+        _check_clip_long(e, tk, blank_id)
+    C = emissions[0].shape[1]
+    if any(e.shape[1] != C for e in emissions):
+        raise ValueError("every clip of a batch must have the same number of classes")
+    dev = _device()
+    em = [e.detach().to(device=dev, dtype=torch.float32) for e in emissions]
+    em = em[0].contiguous() if N == 1 else torch.cat(em, dim=0)
+    Ts, Js = [e.shape[0] for e in emissions], [len(tk) for tk in tokens]
+    cu_f, cu_t = np.zeros(N + 1, np.int32), np.zeros(N + 1, np.int32)
+    cu_f[1:], cu_t[1:] = np.cumsum(Ts), np.cumsum(Js)
+    flat = np.concatenate([np.asarray(tk, np.int32).reshape(-1) for tk in tokens])
+    frames, score, status, _ = torch.ops.ta355.ctc_align_long(
+        em, torch.from_numpy(cu_f).to(dev), torch.from_numpy(flat).to(dev), torch.from_numpy(cu_t).to(dev), int(blank_id),
+        max(Ts), max(Js), int(col_block), int(frame_block), None, 0, None)
+    frames, status, score = frames.cpu().tolist(), status.cpu().tolist(), score.cpu().tolist()
+    if any(s not in (0, 1) for s in status) and not _lib.DRY_RUN:
+        raise _lib.Ta355Error(f"ta_ctc_align_long_f32 refused a clip (status {status})")
+    return [frames[cu_t[n]:cu_t[n + 1]] for n in range(N)], score, status
 
 
 def _uniform_spans(tokens: Sequence[int], num_frames: int) -> list[tuple[int, float, float]]:
@@ -296,3 +359,49 @@ class ForcedAligner:
             spans = _spans(tokens[n], frames[i], status[i] == 1, em[i].shape[0])
             out[n] = _group_words(texts[n], spans, dictionary, _frame_duration, cls.START_OFFSET, cls.END_OFFSET)
         return out
+
+    # ------------------------------------------------------------------ long form
+    @classmethod
+    def align_long_batch(cls, emissions: Sequence[torch.Tensor], texts: Sequence[str], *, log_softmax: bool = False, blank_id: int = 0,
+                         col_block: int = 0, frame_block: int = 0) -> list[list[dict]]:
+        """``align_batch`` beyond its envelope: up to 64 clips of up to 1 048 576 frames against up to 262 144 characters each, in one
+        call of ``torch.ops.ta355.ctc_align_long``.  Same word lists (the reference's two quirks of ``_group_words`` included);
+        ``col_block`` x ``frame_block`` is the trellis tile (0 = the default) and does not change the result."""
+        if len(emissions) != len(texts):
+            raise ValueError(f"{len(emissions)} emission matrices but {len(texts)} texts")
+        _check_tile(int(col_block), int(frame_block))
+        dictionary = cls._dict()
+        tokens = [_tokenize(t, dictionary) for t in texts]
+        live = [n for n, tk in enumerate(tokens) if tk]
+        out: list[list[dict]] = [[] for _ in texts]
+        if not live:
+            return out
+        em = [emissions[n] for n in live]
+        if log_softmax:
+            em = [torch.log_softmax(e.to(_device()).float(), dim=-1) for e in em]
+        frames, _, status = _launch_long(em, [tokens[n] for n in live], blank_id, col_block, frame_block)
+        for i, n in enumerate(live):
+            spans = _spans(tokens[n], frames[i], status[i] == 1, em[i].shape[0])
+            out[n] = _group_words(texts[n], spans, dictionary, FRAME_STRIDE / SAMPLE_RATE, cls.START_OFFSET, cls.END_OFFSET)
+        return out
+
+    @classmethod
+    def align_long(cls, audio, text: str, sample_rate: int = 16000, *, emission: torch.Tensor | None = None, acoustic_model=None,
+                   window_s: float = 30.0, context_s: float = 2.0) -> list[dict]:
+        """``align`` for a whole recording against its whole transcript -> [{'word', 'start', 'end'}] in seconds.
+
+        ``emission`` [num_frames, num_classes]: log-probabilities over ``LABELS`` computed elsewhere (``audio`` is then not read).
+        ``acoustic_model``: a ``wav2vec2.Wav2Vec2CtcMI355X``; the emissions of the 16 kHz ``audio`` come from its ``emissions_long``
+        in windows of ``window_s`` seconds with ``context_s`` seconds of context on both sides, and stay on the device.  One of the
+        two is required: torchaudio's bundle is not run over a whole recording."""
+        if emission is None:
+            if acoustic_model is None:
+                raise ValueError("align_long needs emission=... or acoustic_model=...")
+            if sample_rate != SAMPLE_RATE:
+                raise ValueError(f"acoustic_model takes {SAMPLE_RATE} Hz audio, got sample_rate={sample_rate}: resample first")
+            n_tokens = len(_tokenize(text, cls._dict()))
+            if n_tokens > ALIGN_LONG_LIMITS["tokens"]:                                  # before the acoustic model runs for nothing
+                raise ValueError(f"{n_tokens} tokens: the long alignment kernel takes at most {ALIGN_LONG_LIMITS['tokens']} tokens "
+                                 "per clip")
+            emission = acoustic_model.emissions_long(audio, window_s=window_s, context_s=context_s)
+        return cls.align_long_batch([emission], [text])[0]

@@ -617,6 +617,67 @@ def ctc_align(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_
     return frames, score, status, trellis
 
 
+# ----------------------------------------------------------------------------- forced alignment, long form (csrc/align_long.hip)
+ALIGN_LONG_LIMITS = {"clips": 64, "frames": 1048576, "tokens": 262144, "classes": 65536,      # TA_ALIGN_LONG_MAX_* of include/ta355.h
+                     "col_block": 2048}
+
+
+def ctc_align_long(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, *, col_block=0, frame_block=0, frames=None,
+                   trellis_off=None, trellis_numel=0, trellis=None, workspace=None):
+    """ta_ctc_align_long_f32: ``ctc_align`` (same arguments, same returns, same bytes) beyond its envelope, as a tiled wavefront of
+    launches.  ``col_block`` (a multiple of 64 up to 2048) and ``frame_block`` (>= 1) set the tile, 0 = the library's default; the
+    results do not depend on them.  ``workspace``: a uint8 device tensor of at least ``ta_ctc_align_long_workspace_bytes`` bytes to
+    use instead of a new one (its contents do not matter).  The unchecked device-side tables are the caller's responsibility as in
+    ``ctc_align``."""
+    if not (emission.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("ctc_align_long needs the emissions on a HIP device: there is no CPU path for the trellis")
+    assert emission.dim() == 2 and emission.dtype == F32 and (emission.stride(1) == 1 or emission.numel() == 0), \
+        "emission: f32 [frames, C], unit column stride"
+    C_ = emission.shape[1]
+    ld = emission.stride(0) if emission.shape[0] > 1 else C_
+    N = cu_frames.numel() - 1
+    for name, v, lim in (("clips", N, "clips"), ("frames per clip", max_frames, "frames"), ("tokens per clip", max_tokens, "tokens"),
+                         ("classes", C_, "classes")):
+        if v > ALIGN_LONG_LIMITS[lim]:
+            raise ValueError(f"ctc_align_long: {v} {name} is beyond the kernel's limit of {ALIGN_LONG_LIMITS[lim]}")
+    col_block, frame_block = int(col_block), int(frame_block)
+    if col_block < 0 or col_block % 64 or col_block > ALIGN_LONG_LIMITS["col_block"]:
+        raise ValueError(f"ctc_align_long: col_block {col_block} must be a multiple of 64 up to {ALIGN_LONG_LIMITS['col_block']} "
+                         "(0 = the default)")
+    if frame_block < 0:
+        raise ValueError(f"ctc_align_long: frame_block {frame_block} must be at least 1 (0 = the default)")
+    if not 0 <= blank_id < C_:
+        raise ValueError(f"ctc_align_long: blank_id {blank_id} is outside [0, {C_})")
+    if ld < C_:
+        raise ValueError("ctc_align_long: emission rows overlap")
+    dev = emission.device
+    for t in (cu_frames, tokens, cu_tokens):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == dev
+    if cu_tokens.numel() != N + 1 or N < 0:
+        raise ValueError(f"ctc_align_long: cu_frames holds {N + 1} entries but cu_tokens {cu_tokens.numel()}")
+    if frames is None:
+        frames = torch.full((tokens.numel(),), -1, device=dev, dtype=torch.int32)
+    assert frames.dtype == torch.int32 and frames.is_contiguous() and frames.numel() == tokens.numel() and frames.device == dev
+    score = torch.empty(N, device=dev, dtype=F32)
+    status = torch.empty(N, device=dev, dtype=torch.int32)
+    if trellis_off is None:
+        trellis = None
+    else:
+        assert trellis_off.dtype == torch.int64 and trellis_off.numel() == N and trellis_off.device == dev
+        if trellis is None:
+            trellis = torch.empty(int(trellis_numel), device=dev, dtype=F32)
+        assert trellis.dtype == F32 and trellis.is_contiguous() and trellis.numel() == int(trellis_numel) and trellis.device == dev
+    L = lib()
+    ws_bytes = L.ta_ctc_align_long_workspace_bytes(N, int(max_frames), int(max_tokens), col_block, frame_block)
+    if workspace is None:
+        workspace = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= ws_bytes and workspace.device == dev
+    check(L.ta_ctc_align_long_f32(ptr(emission), ld, C_, ptr(cu_frames), ptr(tokens), ptr(cu_tokens), N, int(max_frames),
+                                  int(max_tokens), int(blank_id), col_block, frame_block, ptr(frames), ptr(score), ptr(status),
+                                  ptr(workspace), ws_bytes, ptr(trellis), ptr(trellis_off), stream()), "ta_ctc_align_long_f32")
+    return frames, score, status, trellis
+
+
 # ----------------------------------------------------------------------------- decoding scores (csrc/generate.hip)
 MAX_TOP_LOGPROBS = 8      # the per-lane candidate list of token_scores_kernel
 

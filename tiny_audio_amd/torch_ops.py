@@ -7,6 +7,7 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment        RIRAugmentation / NoiseAugmentation.__call__   tiny_audio/augmentation.py:71-223
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
+    ta355::ctc_align_long      the same, for a whole recording against its whole transcript   tiny_audio/asr_pipeline.py:117-131
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
     ta355::ecapa_embeddings    SpeechBrain ECAPA-TDNN encode_batch, one call per window   tiny_audio/diarization.py:457-517
     ta355::spk_affinity        SpectralCluster.get_sim_mat / p_pruning / get_laplacian   tiny_audio/diarization.py:49-89
@@ -151,6 +152,29 @@ def ctc_align(emission: Tensor, cu_frames: Tensor, tokens: Tensor, cu_tokens: Te
 
 @ctc_align.register_fake
 def _(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, trellis_off, trellis_numel):
+    N = cu_frames.shape[0] - 1
+    return (tokens.new_empty(tokens.shape), emission.new_empty((N,)), tokens.new_empty((N,)),
+            emission.new_empty((trellis_numel if trellis_off is not None else 0,)))
+
+
+@torch.library.custom_op("ta355::ctc_align_long", mutates_args=("workspace",))
+def ctc_align_long(emission: Tensor, cu_frames: Tensor, tokens: Tensor, cu_tokens: Tensor, blank_id: int, max_frames: int,
+                   max_tokens: int, col_block: int, frame_block: int, trellis_off: Optional[Tensor], trellis_numel: int,
+                   workspace: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``ctc_align`` beyond its envelope (``ops.ctc_align_long``, csrc/align_long.hip): the same inputs and the same four outputs,
+    byte for byte, for up to 64 clips of up to 1 048 576 frames and 262 144 tokens, as a tiled wavefront of launches.  ``col_block``
+    (a multiple of 64) x ``frame_block`` is the tile, 0 = the default; ``workspace``: u8 scratch of
+    ``ta_ctc_align_long_workspace_bytes`` bytes whose contents do not matter (None: allocated here).  No autograd."""
+    from . import ops
+    frames, score, status, trellis = ops.ctc_align_long(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens,
+                                                        col_block=col_block, frame_block=frame_block, trellis_off=trellis_off,
+                                                        trellis_numel=trellis_numel, workspace=workspace)
+    return frames, score, status, trellis if trellis is not None else torch.empty(0, device=emission.device, dtype=F32)
+
+
+@ctc_align_long.register_fake
+def _(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, col_block, frame_block, trellis_off, trellis_numel,
+      workspace):
     N = cu_frames.shape[0] - 1
     return (tokens.new_empty(tokens.shape), emission.new_empty((N,)), tokens.new_empty((N,)),
             emission.new_empty((trellis_numel if trellis_off is not None else 0,)))
@@ -667,4 +691,4 @@ lm_forward_loss.register_autograd(_lm_bwd, setup_context=_lm_setup)
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "whisper_encoder_forward", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
-             "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext")
+             "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long")

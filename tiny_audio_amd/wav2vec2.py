@@ -69,6 +69,37 @@ def frames_of(num_samples: int) -> int:
     return T
 
 
+FRAME_HOP = 320                                  # samples between two emission frames: the product of CONV_STRIDE
+SAMPLE_RATE = 16000
+
+
+def long_windows(n_samples: int, window: int, context: int) -> list[tuple[int, int, int, int]]:
+    """The window table of ``emissions_long``, in samples: -> [(s0, s1, f0, f1)], window i being the slice ``wave[s0:s1]`` that is
+    run through the model and whose frames with GLOBAL index in [f0, f1) are kept.  Pure host arithmetic.
+
+    * Global frame f reads samples [320 f, 320 f + 400); a recording has T = (n_samples - 400) // 320 + 1 of them.
+    * ``window`` is rounded down to a multiple of 320 (at least 320), so window i owns the samples from i * window on and the frames
+      [i * window / 320, (i + 1) * window / 320) that start inside it, cut at T: the spans tile [0, T) exactly once.
+    * The slice is the window's own frames' samples extended by ``context`` (rounded down to a multiple of 320) on both sides where
+      audio exists.  s0 is a multiple of 320, so the slice's frame grid is the global one: its local frame f - s0 / 320 is global f.
+    * A last window with fewer than 400 samples of its own holds no whole frame: it is merged into the window before it, whose right
+      context reaches over its samples as far as ``context`` allows.
+    * A recording of at most one window gives the one entry (0, n_samples, 0, T): the whole recording, no context arithmetic.
+    A recording shorter than 400 samples has no frame and gives no window."""
+    n, T = int(n_samples), frames_of(int(n_samples))
+    if T <= 0:
+        return []
+    wf = max(int(window) // FRAME_HOP, 1)
+    ctx = max(int(context), 0) // FRAME_HOP * FRAME_HOP
+    if T <= wf:
+        return [(0, n, 0, T)]
+    out = []
+    for f0 in range(0, T, wf):
+        f1 = min(f0 + wf, T)
+        out.append((max(0, f0 * FRAME_HOP - ctx), min(n, (f1 - 1) * FRAME_HOP + MIN_SAMPLES + ctx), f0, f1))
+    return out
+
+
 def fold_weight_norm(g, v) -> torch.Tensor:
     """``weight_norm(conv, dim=2)``: w[:, :, tap] = g[tap] * v[:, :, tap] / ||v[:, :, tap]||_F  (g is [1, 1, k])."""
     g, v = torch.as_tensor(g).to(torch.float64), torch.as_tensor(v).to(torch.float64)
@@ -362,6 +393,38 @@ class Wav2Vec2CtcMI355X(torch.nn.Module):
             return torch.empty((0, self.config.n_classes), device=self.device_, dtype=F32), []
         wav, lens = self._pad(waveforms, lengths)
         return torch.ops.ta355.wav2vec2_emissions(wav, lens, torch_ops.register_module(self)), [frames_of(n) for n in lens]
+
+    @torch.no_grad()
+    def emissions_long(self, wave, window_s: float = 30.0, context_s: float = 2.0, batch_windows: int = 16):
+        """One 16 kHz recording of any length -> emissions f32 [T, n_classes] on the device, T = (len - 400) // 320 + 1, for
+        ``ForcedAligner.align_long``.  GroupNorm and attention are global over a clip, so an hour in one ``forward`` is not sensible:
+        the recording is cut by ``long_windows`` into windows of ``window_s`` seconds that start on the global frame grid, each is
+        extended by ``context_s`` seconds on both sides where audio exists and run through ``forward`` as one clip of a ragged batch
+        (``batch_windows`` windows per call), and only the frames of a window's own span are kept.  This is the usual windowed
+        approximation of the full-context model, not its value.  A recording no longer than one window is one ``forward`` call."""
+        w = torch.as_tensor(np.ascontiguousarray(wave)) if isinstance(wave, np.ndarray) else wave
+        if w.dim() == 2 and w.shape[0] == 1:
+            w = w[0]
+        if w.dim() != 1:
+            raise ValueError(f"emissions_long takes one 1-D recording, got {tuple(w.shape)}")
+        if w.shape[0] < MIN_SAMPLES:
+            raise ValueError(f"a clip of {w.shape[0]} samples is shorter than the {MIN_SAMPLES} samples one wav2vec2 frame needs")
+        if window_s <= 0 or context_s < 0 or batch_windows < 1:
+            raise ValueError("emissions_long: window_s > 0, context_s >= 0 and batch_windows >= 1")
+        table = long_windows(w.shape[0], int(round(window_s * SAMPLE_RATE)), int(round(context_s * SAMPLE_RATE)))
+        if len(table) == 1:
+            return self.forward([w])[0]
+        w = w.to(device=self.device_, dtype=F32)
+        out = torch.empty((table[-1][3], self.config.n_classes), device=self.device_, dtype=F32)
+        for i in range(0, len(table), int(batch_windows)):
+            group = table[i:i + int(batch_windows)]
+            em, Ts = self.forward([w[s0:s1] for s0, s1, _, _ in group])
+            row = 0
+            for (s0, _, f0, f1), t in zip(group, Ts):
+                lo = row + f0 - s0 // FRAME_HOP
+                out[f0:f1] = em[lo:lo + f1 - f0]
+                row += t
+        return out
 
     def _forward_impl(self, wav, lens, out=None):
         """wav f32 [B, Ls] on the device, lens: Python ints -> emissions [sum T, n_classes] (written into ``out`` when given: a
