@@ -448,6 +448,61 @@ int ta_greedy_advance(const long* amax, const long* eos_ids, int n_eos, long pad
 int ta_token_scores_f32(const float* logits, long ld, int V, int B, const long* chosen, const int* finished, const int* step_dev,
                         int max_new, int top_k, float* logprob, float* entropy, long* top_ids, float* top_logprobs, hipStream_t st);
 
+/* ---- beam search (csrc/beam.hip): HF GenerationMixin._beam_search (TF:generation/utils.py) for do_sample=False, around the unchanged
+ * ta_lm_prefill / ta_lm_decode_step.  Beams are rows: R = B * K rows, row = b * K + k; 1 <= K <= 8 beams, n_eos <= 3 eos ids,
+ * M = max(2, 1 + n_eos) * K <= 32 candidates per clip and step (anything else: TA_ERR_ARG, nothing launched).  A step is
+ * ta_lm_decode_step on R rows -> ta_beam_logprobs_f32 -> the ta_logits_* processors on R rows (context: the replicated prompt ids
+ * followed by run_seq) -> ta_beam_topk_f32 -> ta_beam_advance -> ta_kv_beam_reorder; every argument is step-invariant (the step, the
+ * slot and all flags are device memory), so the step is hipGraph-capturable like the greedy one.  All state-machine arithmetic is the
+ * f32 add / compare / IEEE divide / select HF performs, in HF's order.
+ *
+ * ta_beam_logprobs_f32: `log_probs = nn.functional.log_softmax(logits, dim=-1)` of _beam_search, in place on rows [R, ld] f32 over
+ * the first V columns (columns >= V untouched): (x - m) - log(sum e^(x - m)), -inf stays -inf, a row without a finite entry is left
+ * alone.  R <= 64 rows of V >= 16384 columns are split over 8 workgroups per row through a scratch the library owns (its own, not
+ * ta_token_scores_f32's); as there, such calls on two streams at once must be serialised by the caller. */
+int ta_beam_logprobs_f32(float* logits, long ld, int V, int R, hipStream_t st);
+/* ta_beam_topk_f32: _get_top_k_continuations (torch.topk of `log_probs + running_beam_scores[:, :, None]` reshaped [B, K * V]).
+ * cand_score f32 [B, M] = the M largest of fl32(rows[b * K + k][v] + score[b * K + k]), descending; cand_flat i32 [B, M] = their
+ * flat indices k * V + v (parent beam = flat / V, token = flat % V).  Ties: lowest flat index first (-inf entries included: a clip
+ * with fewer than M finite values is completed by its lowest -inf indices).  ws: ta_beam_topk_workspace_bytes(B, K, V, M) bytes. */
+long ta_beam_topk_workspace_bytes(int B, int K, int V, int M);
+int ta_beam_topk_f32(const float* rows, long ld, int V, const float* score, int B, int K, int M, float* cand_score, int* cand_flat,
+                     void* ws, long ws_bytes, hipStream_t st);
+/* ta_beam_advance: the rest of one _beam_search iteration for step t = *step_dev, one workgroup per clip:
+ *   stopping criteria                       hit[c] = token[c] is an eos id, or t + 1 == max_new
+ *   _get_running_beams_for_next_iteration   the K best of cand_score + hit * -1e9 -> run_score f32 [R], parent i32 [R] (the beam each
+ *                                           new row continues), next_ids i64 [R], run_seq i64 [R, max_new] (permuted through LDS:
+ *                                           K * max_new <= 12288) with the new token at column t
+ *   _update_finished_beams                  only the first K candidates may finish; cand_score / len_div[t] (len_div f32 [max_new],
+ *                                           len_div[n - 1] = float32(float(n) ** length_penalty) from the host), then + -1e9 for "pool
+ *                                           full and early_stopping is True", for "heuristic satisfied", for "did not just finish", in
+ *                                           that order; merged behind the pool, the K best kept: pool_seq i64 [B, K, max_new] (padded
+ *                                           with pad_id), pool_score f32 [B, K], pool_len i32 [B, K], pool_fin i32 [B, K] (is_sent_finished)
+ *   _check_early_stop_heuristic             heur i32 [B] (is_early_stop_heuristic_unsatisfied); heur_max_len != 0 when early_stopping
+ *                                           is "never" and length_penalty > 0 (the divisor is then len_div[max_new - 1], else len_div[t])
+ *   _beam_search_has_unfinished_sequences   clip_done i32 [B], sticky; *n_unfinished = clips not done.  HF stops the whole batch on
+ *                                           batch-wide any / all; a done clip keeps stepping here and its pool no longer changes.
+ * early_stopping: 0 False, 1 True, 2 "never".  Initial state: run_score = 0, -1e9, ... per clip, pool_score = -1e9, pool_fin = 0,
+ * heur = 1, clip_done = 0.  Also advances *step_dev, *slot_dev, pos [R] and kmask [R, Lmax] as ta_greedy_advance does.  The five tr_*
+ * pointers (all or none) receive at index t of [max_new, ...] buffers: the candidates [B, M], run_seq / run_score as they stood
+ * BEFORE the step ([R, max_new] / [R]) and parent [R]. */
+int ta_beam_advance(const float* cand_score, const int* cand_flat, int B, int K, int M, int V, const long* eos_ids, int n_eos,
+                    long pad_id, int max_new, const float* len_div, int early_stopping, int heur_max_len, long* run_seq,
+                    float* run_score, int* parent, long* next_ids, long* pool_seq, float* pool_score, int* pool_len,
+                    int* pool_fin, int* heur, int* clip_done, int* step_dev, int* slot_dev, int* pos, int* kmask, int Lmax,
+                    int* n_unfinished, float* tr_cand_score, int* tr_cand_flat, long* tr_run_seq, float* tr_run_score,
+                    int* tr_parent, hipStream_t st);
+/* The cache of a beam run, bf16 [layers, R, kv_heads, Lmax, head_dim] (head_dim a multiple of 8), moved in 16-byte pieces.
+ * ta_kv_beam_expand (_expand_inputs_for_generation): slots [0, L) of clip b of the B-row prefill caches [layers, B, kv_heads, Lsrc,
+ * head_dim] -> rows b * K .. b * K + K - 1.  ta_kv_beam_reorder (the `reorder_cache(beam_idx)` of _beam_search): the generated slots
+ * [L, *slot_dev) of the K rows of every clip permuted in place by parent [R] (row j takes row parent[j]'s), both caches, every layer;
+ * a lane loads its piece of all K rows before it stores any, so no scratch copy is needed.  Prompt slots are never touched; clips
+ * whose parent is the identity, and K == 1, move nothing.  Lmax >= L + max_new; the grid covers max_new slots. */
+int ta_kv_beam_expand(const void* ksrc, const void* vsrc, void* kdst, void* vdst, int layers, int B, int K, int kv_heads, int L,
+                      int Lsrc, int Lmax, int head_dim, hipStream_t st);
+int ta_kv_beam_reorder(void* kcache, void* vcache, int layers, int B, int K, int kv_heads, int L, int Lmax, int head_dim, int max_new,
+                       const int* parent, const int* slot_dev, hipStream_t st);
+
 /* loss.backward() through the LM (replaces autograd over Qwen3ForCausalLM, tiny_audio/asr_modeling.py:517-533).
  * d_audio f32 [n_audio_rows, D] (zeroed, then rows referenced by src_row written; NULL = not wanted, e.g. frozen
  * projector); d_embeds optional [B*L, D]; lora_grads: host array [n_layers] (required iff w->lora_rank > 0, zeroed and

@@ -4,7 +4,9 @@ B clips of 10 s, prompt = 3 + 125 <audio> + 24 tokens, N new tokens; reports pro
 ``gen_bench.py [B [N]] [--scores] [--top-logprobs K]``: the same loop with the decoding scores on (token log-probability and entropy,
 K alternatives per step).  Decoding options: ``--bad-words`` (256 two-token entries), ``--suppress`` (64 suppressed ids), ``--min-p P`` and
 ``--typical-p P`` (both switch sampling on: HF's warpers act under do_sample only); ``--options-sweep`` measures none, each of the four alone
-and all of them in one process, one JSON line each."""
+and all of them in one process, one JSON line each.
+``--num-beams K [--length-penalty P]``: beam search (``generate_beams``) on B clips x K beams, and in the same process greedy decoding at
+B * K rows, so that the difference of the two per-step figures is the beam machinery (log-softmax, top-k, bookkeeping, cache reorder)."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,6 +16,7 @@ from tiny_audio_amd.asr_modeling import ASRModel
 
 argv, scores, top_lp = [], False, 0
 bad_words, suppress, min_p, typical_p, sweep = False, False, None, None, False
+num_beams, length_penalty = 0, 1.0
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--scores":
@@ -28,11 +31,15 @@ for a in it:
         min_p = float(next(it))
     elif a == "--typical-p":
         typical_p = float(next(it))
+    elif a == "--num-beams":
+        num_beams = int(next(it))
+    elif a == "--length-penalty":
+        length_penalty = float(next(it))
     elif a == "--options-sweep":
         sweep = True
     else:
         argv.append(a)
-B = int(argv[0]) if len(argv) > 0 else 32
+B = int(argv[0]) if len(argv) > 0 else (8 if num_beams else 32)
 N = int(argv[1]) if len(argv) > 1 else 64
 cfg = ASRConfig()
 m = ASRModel(cfg, device="cuda", init="random", seed=0)
@@ -59,16 +66,32 @@ def option_kwargs(bad_words, suppress, min_p, typical_p):
     return o
 
 
-def measure(options):
+def measure(options, gen=None, kw=kw):
+    gen = gen or m.generate
     res = {}
     for n in (1, N):
-        m.generate(**kw, **options, max_new_tokens=n); torch.cuda.synchronize()
+        gen(**kw, **options, max_new_tokens=n); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(3):
-            m.generate(**kw, **options, max_new_tokens=n)
+            gen(**kw, **options, max_new_tokens=n)
         torch.cuda.synchronize()
         res[n] = (time.perf_counter() - t0) / 3
     return res
+
+
+if num_beams:
+    K = num_beams
+    r = measure(dict(num_beams=K, length_penalty=length_penalty), m.generate_beams)
+    rows = B * K                      # greedy at the same number of rows: what the decode step itself costs
+    kw_g = dict(kw, input_ids=ids[:1].expand(rows, -1).contiguous(), input_features=feats[:1].expand(rows, -1, -1).contiguous(),
+                audio_attention_mask=amask[:1].expand(rows, -1).contiguous(), attention_mask=torch.ones(rows, ids.shape[1], dtype=torch.int64))
+    g = measure({}, kw=kw_g)
+    beam_ms, greedy_ms = (r[N] - r[1]) / (N - 1) * 1e3, (g[N] - g[1]) / (N - 1) * 1e3
+    print(json.dumps({"B": B, "num_beams": K, "rows": rows, "length_penalty": length_penalty, "new_tokens": N,
+                      "prompt_pass_ms": round(r[1] * 1e3, 2), "per_step_ms": round(beam_ms, 3),
+                      "greedy_rows": rows, "greedy_prompt_pass_ms": round(g[1] * 1e3, 2), "greedy_per_token_ms": round(greedy_ms, 3),
+                      "beam_machinery_ms_per_step": round(beam_ms - greedy_ms, 3)}))
+    sys.exit(0)
 
 
 if sweep:

@@ -76,19 +76,22 @@ class GenerationOutput(dict):
     distribution it was chosen from: HF's ``compute_transition_scores(..., normalize_logits=True)``), ``token_entropy`` f32
     [B, n_new] (nats), and with ``top_logprobs`` = k > 0 ``top_token_ids`` int64 [B, n_new, k] / ``top_logprobs`` f32 [B, n_new, k]
     (descending; slots beyond the finite entries are -1 / -inf).  Positions after a clip's first eos hold 0 / 0 / -1 / -inf.
-    HF's ``scores`` (the full [B, V] row of every step) is deliberately not kept, so that name is not used."""
+    HF's ``scores`` (the full [B, V] row of every step) is deliberately not kept, so that name is not used.
+    ``ASRModel.generate_beams`` returns ``sequences`` int64 [B * num_return_sequences, n_new] with ``sequences_scores`` f32
+    [B * num_return_sequences] (HF's name: the length-penalised sum of log-probabilities of every returned hypothesis)."""
 
-    _items = ("sequences", "token_logprobs", "token_entropy", "top_token_ids", "top_logprobs")
+    _items = ("sequences", "token_logprobs", "token_entropy", "top_token_ids", "top_logprobs", "sequences_scores")
 
-    def __init__(self, sequences=None, token_logprobs=None, token_entropy=None, top_token_ids=None, top_logprobs=None):
+    def __init__(self, sequences=None, token_logprobs=None, token_entropy=None, top_token_ids=None, top_logprobs=None,
+                 sequences_scores=None):
         super().__init__()
         if isinstance(sequences, Mapping):            # rebuilt from a mapping, as library code does with ModelOutput
             src = sequences
             unknown = [k for k in src if k not in self._items]
             if unknown:
                 raise KeyError(f"GenerationOutput has no item {unknown[0]!r}")
-            sequences, token_logprobs, token_entropy, top_token_ids, top_logprobs = (src.get(k) for k in self._items)
-        for k, v in zip(self._items, (sequences, token_logprobs, token_entropy, top_token_ids, top_logprobs)):
+            sequences, token_logprobs, token_entropy, top_token_ids, top_logprobs, sequences_scores = (src.get(k) for k in self._items)
+        for k, v in zip(self._items, (sequences, token_logprobs, token_entropy, top_token_ids, top_logprobs, sequences_scores)):
             if v is not None:
                 dict.__setitem__(self, k, v)
 
@@ -574,24 +577,28 @@ class ASRModel(nn.Module):
         lens = self._compute_encoder_output_lengths(audio_attention_mask)
         return int(self.projector.get_output_length(int(lens.max().item())))
 
-    def _prepare_generation(self, input_ids, input_features, audio_attention_mask, attention_mask, system_prompt, kw):
-        """Everything ``generate`` and ``generate_streaming`` share (tiny_audio/asr_modeling.py:580-640, :669-716):
+    def _prepare_generation(self, input_ids, input_features, audio_attention_mask, attention_mask, system_prompt, kw, beams=False):
+        """Everything ``generate``, ``generate_streaming`` and ``generate_beams`` share (tiny_audio/asr_modeling.py:580-640, :669-716):
         generation settings, audio -> encoder -> projector, the chat prompt with one <audio> placeholder per projected
-        frame, and the placeholder -> audio-row index.  -> kwargs of ``Qwen3MI355X.greedy_decode_iter``."""
+        frame, and the placeholder -> audio-row index.  -> kwargs of ``Qwen3MI355X.greedy_decode_iter``; with ``beams`` (the caller
+        has taken the beam settings out of ``kw``) those of ``Qwen3MI355X.beam_decode``, which takes no ``sampling``."""
         if input_features is None:
             raise ValueError("input_features required for generation")
         if audio_attention_mask is None:
             raise ValueError("audio_attention_mask required for generation")
         self._apply_stream_modes()
         max_new = int(self._generation_setting("max_new_tokens", 128, kw))
-        if int(self._generation_setting("num_beams", 1, kw)) != 1:
-            raise NotImplementedError("num_beams 1 only (the reference's generation config, asr_config.py:103-111); beam search is not built")
+        if not beams and int(self._generation_setting("num_beams", 1, kw)) != 1:
+            raise NotImplementedError("generate() is greedy search or sampling (num_beams 1, the reference's generation config, "
+                                      "asr_config.py:103-111); beam search is ASRModel.generate_beams(...)")
         # do_sample / temperature / top_k / top_p (asr_config.py:78-81; round 4): HF's warpers on the device, one multinomial draw per
         # clip and step from a Philox stream keyed by ``seed`` (a generate() keyword here).  Without one every call draws a FRESH key
         # from torch's global generator, so repeated calls on the same audio give different samples and torch.manual_seed() makes a
         # run reproducible -- the behaviour of HF's sampling, which advances the global RNG (ADVICE r4)
         sampling = None
         if bool(self._generation_setting("do_sample", False, kw)):
+            if beams:
+                raise ValueError("do_sample=True with beams: beam sampling is not built")
             temp = self._generation_setting("temperature", None, kw)
             top_k = self._generation_setting("top_k", None, kw)
             top_p = self._generation_setting("top_p", None, kw)
@@ -607,7 +614,8 @@ class ASRModel(nn.Module):
         # the reference's other two knobs (asr_config.py:84-86): HF logits processors on the device, in front of the argmax
         rep = float(self._generation_setting("repetition_penalty", 1.0, kw))
         ngram = int(self._generation_setting("no_repeat_ngram_size", 0, kw))
-        kw.pop("length_penalty", None)                                  # beam-search only: no effect on greedy search
+        if not beams:
+            kw.pop("length_penalty", None)                              # beam-search only: no effect on greedy search
         eos_ids = kw.pop("eos_token_id", None)
         if eos_ids is None:       # <|im_end|> and <|endoftext|> (asr_modeling.py:163-167); the latter is Qwen's pad token
             eos_ids = [self.config.eos_token_id, self.config.pad_token_id]
@@ -635,7 +643,7 @@ class ASRModel(nn.Module):
         src_row = ops.audio_index(ids, counts, N, self.audio_token_id)
         return dict(input_ids=ids, src_row=src_row, audio=y.reshape(B * N, -1), attention_mask=attention_mask,
                     max_new_tokens=max_new, eos_ids=eos_ids, pad_id=pad_id, repetition_penalty=rep, no_repeat_ngram_size=ngram,
-                    min_new_tokens=min_new, sampling=sampling, **options)
+                    min_new_tokens=min_new, **({} if beams else {"sampling": sampling}), **options)
 
     def _decoding_options(self, kw, eos_ids, min_new, do_sample):
         """HF's remaining single-hypothesis options, each read from the call's keywords, then from ``self.config``
@@ -713,6 +721,55 @@ class ASRModel(nn.Module):
         finally:
             self.train(was_training)
 
+    @torch.no_grad()
+    def generate_beams(self, input_ids: Optional[torch.Tensor] = None, input_features: Optional[torch.Tensor] = None,
+                       audio_attention_mask: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+                       system_prompt: Optional[str] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
+                       early_stopping=None, num_return_sequences: int = 1, return_beam_trace: bool = False, **generate_kwargs):
+        """Beam search: what the reference gets from ``language_model.generate(num_beams=K, ...)`` (``num_beams`` / ``length_penalty``
+        of asr_config.py:42,85 and any ``**generate_kwargs``; HF ``GenerationMixin._beam_search``, do_sample False) -- the n-best
+        transcripts of every clip with their scores.  ``generate`` keeps raising for ``num_beams > 1`` (its callers rely on one row per
+        clip); this is the entry point.
+
+        ``num_beams`` (1..8), ``length_penalty`` and ``early_stopping`` (False, True or "never") are read from the call, then from
+        ``self.config``; defaults 1, 1.0, False.  Every logits-processor option of ``generate`` works here (HF applies them to the
+        log-probabilities of every beam).  -> ``GenerationOutput(sequences int64 [B * num_return_sequences, n_new], sequences_scores
+        f32 [B * num_return_sequences])``: per clip its best ``num_return_sequences <= num_beams`` finished hypotheses, best first,
+        padded with ``pad_token_id`` and cropped to the longest.  ``return_beam_trace=True`` -> ``(that output, trace)`` with the
+        trace dict of ``Qwen3MI355X.beam_decode`` (every step's candidates, running beams and parents, the final pool and cache).
+        ``use_graph=False`` (a keyword) runs every step eagerly instead of replaying the captured one."""
+        kw = dict(generate_kwargs)
+        K = int(self._generation_setting("num_beams", 1, {"num_beams": num_beams}))
+        lp = float(self._generation_setting("length_penalty", 1.0, {"length_penalty": length_penalty}))
+        es = self._generation_setting("early_stopping", False, {"early_stopping": early_stopping})
+        nrs = int(num_return_sequences)
+        if not 1 <= K <= ops.MAX_BEAMS:
+            raise ValueError(f"num_beams must be within [1, {ops.MAX_BEAMS}] (the per-clip candidate lists of csrc/beam.hip); got {K}")
+        if not 1 <= nrs <= K:
+            raise ValueError(f"`num_return_sequences` ({nrs}) has to be smaller or equal to `num_beams` ({K})")
+        if es not in (False, True, "never"):
+            raise ValueError(f"`early_stopping` must be a boolean or 'never', but is {es!r}")
+        if kw.pop("return_token_scores", False) or kw.pop("top_logprobs", 0):
+            raise ValueError("return_token_scores / top_logprobs are per-token scores of one hypothesis per clip: generate() only; "
+                             "generate_beams returns sequences_scores")
+        for name in ("num_beam_groups", "constraints", "force_words_ids"):
+            v = kw.pop(name, None)
+            if v is not None and v != 1:
+                raise ValueError(f"{name}: group and constrained beam search are not built")
+        was_training = self.training
+        self.eval()
+        try:
+            args = self._prepare_generation(input_ids, input_features, audio_attention_mask, attention_mask, system_prompt, kw, beams=True)
+            if len(args["eos_ids"]) > ops.MAX_BEAM_EOS:
+                raise ValueError(f"beam search takes at most {ops.MAX_BEAM_EOS} eos ids; got {args['eos_ids']}")
+            use_graph = bool(kw.pop("use_graph", True))
+            out = self.language_model.beam_decode(**args, num_beams=K, length_penalty=lp, early_stopping=es, num_return_sequences=nrs,
+                                                  use_graph=use_graph, return_trace=bool(return_beam_trace))
+            res = GenerationOutput(sequences=out[0], sequences_scores=out[1])
+            return (res, out[2]) if return_beam_trace else res
+        finally:
+            self.train(was_training)
+
     def generate_streaming(self, input_features: torch.Tensor, audio_attention_mask: torch.Tensor,
                            system_prompt: Optional[str] = None, input_ids: Optional[torch.Tensor] = None,
                            return_token_ids: bool = False, return_token_scores: bool = False, **generate_kwargs) -> Iterator:
@@ -732,6 +789,8 @@ class ASRModel(nn.Module):
             raise ValueError("generate_streaming handles one clip at a time (TextIteratorStreamer: batch size 1 only)")
         if not return_token_ids and self.tokenizer is None:
             raise ValueError("generate_streaming needs a tokenizer to produce text (or return_token_ids=True)")
+        if int(self._generation_setting("num_beams", 1, {"num_beams": generate_kwargs.get("num_beams")})) != 1:
+            raise ValueError("generate_streaming does not take num_beams > 1 (HF: a streamer cannot follow beam search); use generate_beams")
         was_training = self.training
         self.eval()
         try:

@@ -813,6 +813,193 @@ class Qwen3MI355X(torch.nn.Module):
             return
         yield out_seq[:, :n_new]
 
+    # ------------------------------------------------------------------ beam search (csrc/beam.hip)
+    @torch.no_grad()
+    def beam_decode(self, input_ids, src_row, audio, attention_mask=None, max_new_tokens=128, eos_ids=(), pad_id=0, num_beams=1,
+                    length_penalty=1.0, early_stopping=False, num_return_sequences=1, sync_every=8, use_graph=True,
+                    repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, sequence_bias=None, bad_words=None,
+                    forced_eos_ids=None, exponential_decay_length_penalty=None, suppress_tokens=None, begin_suppress_tokens=None,
+                    return_trace=False):
+        """HF beam search (``GenerationMixin._beam_search``, do_sample False) with beams as rows: the prompt pass runs once on the B
+        clips, ``ta_kv_beam_expand`` copies every clip's cache rows to its K = ``num_beams`` rows, and every step is the unchanged
+        ``ta_lm_decode_step`` on R = B * K rows followed by ``ta_beam_logprobs_f32``, the greedy loop's logits processors on the
+        log-probabilities (context: the replicated prompt ids and the running sequences), ``ta_beam_topk_f32``, ``ta_beam_advance`` and
+        ``ta_kv_beam_reorder``.  As in the greedy loop all per-step state is device memory: the first step runs eagerly, the second is
+        captured into a hipGraph and replayed, and the host polls the number of clips that are not done every ``sync_every`` steps.
+
+        -> (sequences int64 [B * num_return_sequences, n_new], sequences_scores f32 [B * num_return_sequences]): the best finished
+        sequences of every clip in descending score order, padded with ``pad_id``, cropped to the longest.  ``early_stopping``: False,
+        True or "never", HF's three heuristics.  With ``return_trace`` a third item, a dict: per executed step ``cand_score`` /
+        ``cand_flat`` [steps, B, M], ``running_sequences`` [steps, B, K, max_new] and ``running_scores`` [steps, B, K] as they stood
+        BEFORE the step, ``parent`` [steps, B, K]; and the final ``pool`` (sequences, scores, lengths, finished), the final running
+        state and the R-row ``cache``.  The trace buffers are written by ``ta_beam_advance`` at ``*step_dev``; without the switch
+        nothing extra is allocated or launched."""
+        if self._w is None:
+            raise _lib.Ta355Error("LM weights not loaded")
+        L_ = _lib.lib()
+        c, dev = self.config, self.device_
+        B, L = input_ids.shape
+        K, max_new, eos_ids = int(num_beams), int(max_new_tokens), [int(e) for e in eos_ids]
+        n_eos, nrs = len(eos_ids), int(num_return_sequences)
+        if not 1 <= K <= 8:
+            raise ValueError(f"num_beams must be within [1, 8]; got {num_beams}")
+        if n_eos > 3:
+            raise ValueError(f"beam search takes at most 3 eos ids (max(2, 1 + n_eos) * num_beams candidates, 32 at the most); got {n_eos}")
+        if not 1 <= nrs <= K:
+            raise ValueError(f"num_return_sequences ({nrs}) has to be within [1, num_beams = {K}]")
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f"early_stopping must be False, True or 'never'; got {early_stopping!r}")
+        es = 2 if early_stopping == "never" else int(bool(early_stopping))
+        lp = float(length_penalty)
+        i32, i64 = torch.int32, torch.int64
+        if max_new <= 0:
+            out = torch.empty((B * nrs, 0), dtype=i64, device=dev), torch.full((B * nrs,), -1.0e9, dtype=F32, device=dev)
+            return (*out, {}) if return_trace else out
+        Lmax = L + max_new
+        if Lmax > c.max_position_embeddings:
+            raise ValueError(f"prompt ({L}) + max_new_tokens ({max_new}) exceeds max_position_embeddings")
+        if K * max_new > 12288:
+            raise ValueError(f"num_beams * max_new_tokens = {K * max_new} exceeds 12288 (the running sequences are staged in LDS)")
+        M, R, V, vp = max(2, 1 + n_eos) * K, B * K, c.vocab_size, self.vocab_pad
+        att = torch.ones((B, L), dtype=i32, device=dev) if attention_mask is None else attention_mask.to(device=dev, dtype=i32)
+        pos_full = (att.cumsum(-1) - 1).clamp(min=0).to(i32).contiguous()
+        idx = torch.arange(L, device=dev, dtype=i32)[None, :].expand(B, L)
+        last_rows = (torch.arange(B, device=dev, dtype=i32) * L + (idx * att).max(dim=-1).values.to(i32)).contiguous()
+        # per row: every beam of a clip starts from the clip's prompt (HF _expand_inputs_for_generation)
+        kmask = torch.zeros((R, Lmax), dtype=i32, device=dev)
+        kmask[:, :L] = att.repeat_interleave(K, 0)
+        pos = att.sum(-1).to(i32).repeat_interleave(K).contiguous()
+        ids = input_ids.to(device=dev, dtype=i64).contiguous()
+        ids_r = ids.repeat_interleave(K, 0).contiguous()
+        nl, hkv, hd = c.num_hidden_layers, c.num_key_value_heads, c.head_dim
+        kc0, vc0 = (torch.empty((nl, B, hkv, L, hd), dtype=BF16, device=dev) for _ in range(2))      # the prompt pass's B-row staging cache
+        kc, vc = (torch.empty((nl, R, hkv, Lmax, hd), dtype=BF16, device=dev) for _ in range(2))
+        lora_img = None
+        if self.train_base:
+            self._bind_ft()
+        if self.lora_rank:
+            self._bind_lora()
+            lora_img = torch.empty(L_.ta_lm_lora_image_bytes(C.byref(self._w)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(L_.ta_lm_prefill_workspace_bytes(C.byref(self._w), B, L),
+                             L_.ta_lm_decode_workspace_bytes(C.byref(self._w), R)), dtype=torch.uint8, device=dev)
+        tk_ws = torch.empty(max(L_.ta_beam_topk_workspace_bytes(B, K, V, M), 8), dtype=torch.uint8, device=dev)
+        logits = torch.empty((R, vp), dtype=F32, device=dev)
+        pre_logits = torch.empty((B, vp), dtype=F32, device=dev)
+        run_seq = torch.full((R, max_new), int(pad_id), dtype=i64, device=dev)
+        run_score = torch.tensor([0.0] + [-1.0e9] * (K - 1), dtype=F32, device=dev).repeat(B).contiguous()      # HF: only beam 0 is live at first
+        parent, next_ids = torch.zeros(R, dtype=i32, device=dev), torch.zeros(R, dtype=i64, device=dev)
+        pool_seq = torch.full((B, K, max_new), int(pad_id), dtype=i64, device=dev)
+        pool_score = torch.full((B, K), -1.0e9, dtype=F32, device=dev)
+        pool_len, pool_fin = torch.zeros((B, K), dtype=i32, device=dev), torch.zeros((B, K), dtype=i32, device=dev)
+        heur, clip_done = torch.ones(B, dtype=i32, device=dev), torch.zeros(B, dtype=i32, device=dev)
+        cand_score, cand_flat = torch.empty((B, M), dtype=F32, device=dev), torch.empty((B, M), dtype=i32, device=dev)
+        step_dev = torch.zeros(1, dtype=i32, device=dev)
+        slot_dev = torch.full((1,), L, dtype=i32, device=dev)
+        alive = torch.full((1,), B, dtype=i32, device=dev)
+        eos = torch.tensor(eos_ids or [-1], dtype=i64, device=dev)
+        len_div = ops.beam_length_divisors(lp, max_new).to(dev)
+        a = None if audio is None else audio.detach().to(F32).contiguous()
+        tr = None
+        if return_trace:
+            tr = dict(cand_score=torch.zeros((max_new, B, M), dtype=F32, device=dev), cand_flat=torch.zeros((max_new, B, M), dtype=i32, device=dev),
+                      run_seq=torch.full((max_new, R, max_new), int(pad_id), dtype=i64, device=dev),
+                      run_score=torch.zeros((max_new, R), dtype=F32, device=dev), parent=torch.zeros((max_new, R), dtype=i32, device=dev))
+        tp = lambda k: None if tr is None else ptr(tr[k])  # noqa: E731
+
+        # the logits processors of greedy_decode_iter, on R rows of log-probabilities (HF runs them behind log_softmax)
+        rep, ngram, min_new = float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens or 0)
+        tab_bias = ops.build_sequence_table(sequence_bias or [], V, dev, "sequence_bias")
+        tab_bad = ops.build_sequence_table(bad_words or [], V, dev, "bad_words_ids")
+        ids_of = lambda v, what: torch.tensor(ops.id_list(v, V, what), dtype=i64, device=dev) if v else None  # noqa: E731
+        forced, sup = ids_of(forced_eos_ids, "forced_eos_token_id"), ids_of(suppress_tokens, "suppress_tokens")
+        bsup = ids_of(begin_suppress_tokens, "begin_suppress_tokens")
+        decay_start, decay_mult = 0, None
+        if exponential_decay_length_penalty is not None and n_eos:
+            if min_new > int(exponential_decay_length_penalty[0]):
+                raise ValueError(f"min_new_tokens ({min_new}) > exponential_decay_length_penalty start ({exponential_decay_length_penalty[0]}): "
+                                 "HF forms -inf + inf = NaN on the eos scores in that window; refused")
+            decay_start, decay_mult = ops.decay_multipliers(exponential_decay_length_penalty, max_new)
+            decay_mult = decay_mult.to(dev)
+        step_rules = forced is not None or decay_mult is not None or sup is not None or bsup is not None
+        n_of = lambda t: 0 if t is None else t.numel()  # noqa: E731
+
+        def seq_bias(tab):
+            _lib.check(L_.ta_logits_sequence_bias(ptr(logits), vp, V, ptr(ids_r), L, ptr(run_seq), max_new, ptr(step_dev), R,
+                                                  ptr(tab["tokens"]), ptr(tab["offsets"]), ptr(tab["bias"]), ptr(tab["groups"]),
+                                                  tab["n_seq"], tab["n_groups"], tab["n_tokens"], stream()), "ta_logits_sequence_bias")
+
+        def select():
+            _lib.check(L_.ta_beam_logprobs_f32(ptr(logits), vp, V, R, stream()), "ta_beam_logprobs_f32")
+            if tab_bias is not None:
+                seq_bias(tab_bias)
+            if rep != 1.0 or ngram > 0:
+                _lib.check(L_.ta_logits_process(ptr(logits), vp, V, ptr(ids_r), L, ptr(run_seq), max_new, ptr(step_dev), R, rep, ngram,
+                                                stream()), "ta_logits_process")
+            if tab_bad is not None:
+                seq_bias(tab_bad)
+            if min_new > 0 and n_eos:
+                _lib.check(L_.ta_logits_suppress_until(ptr(logits), vp, V, ptr(eos), n_eos, min_new, ptr(step_dev), R, stream()),
+                           "ta_logits_suppress_until")
+            if step_rules:
+                _lib.check(L_.ta_logits_step_rules(ptr(logits), vp, V, R, ptr(step_dev), max_new, ptr(forced), n_of(forced), ptr(eos),
+                                                   n_eos if decay_mult is not None else 0, decay_start, ptr(decay_mult), ptr(sup), n_of(sup),
+                                                   ptr(bsup), n_of(bsup), stream()), "ta_logits_step_rules")
+            _lib.check(L_.ta_beam_topk_f32(ptr(logits), vp, V, ptr(run_score), B, K, M, ptr(cand_score), ptr(cand_flat), ptr(tk_ws),
+                                           tk_ws.numel(), stream()), "ta_beam_topk_f32")
+            _lib.check(L_.ta_beam_advance(ptr(cand_score), ptr(cand_flat), B, K, M, V, ptr(eos), n_eos, int(pad_id), max_new, ptr(len_div),
+                                          es, int(es == 2 and lp > 0.0), ptr(run_seq), ptr(run_score), ptr(parent), ptr(next_ids),
+                                          ptr(pool_seq), ptr(pool_score), ptr(pool_len), ptr(pool_fin), ptr(heur), ptr(clip_done),
+                                          ptr(step_dev), ptr(slot_dev), ptr(pos), ptr(kmask), Lmax, ptr(alive), tp("cand_score"),
+                                          tp("cand_flat"), tp("run_seq"), tp("run_score"), tp("parent"), stream()), "ta_beam_advance")
+            if K > 1:
+                _lib.check(L_.ta_kv_beam_reorder(ptr(kc), ptr(vc), nl, B, K, hkv, L, Lmax, hd, max_new, ptr(parent), ptr(slot_dev),
+                                                 stream()), "ta_kv_beam_reorder")
+
+        _lib.check(L_.ta_lm_prefill(C.byref(self._w), ptr(ids), ptr(src_row), ptr(a), ptr(att.contiguous()), ptr(pos_full), B, L,
+                                    ptr(kc0), ptr(vc0), L, ptr(last_rows), ptr(pre_logits), ptr(lora_img), ptr(ws), ws.numel(),
+                                    stream()), "ta_lm_prefill")
+        _lib.check(L_.ta_kv_beam_expand(ptr(kc0), ptr(vc0), ptr(kc), ptr(vc), nl, B, K, hkv, L, L, Lmax, hd, stream()), "ta_kv_beam_expand")
+        logits.view(B, K, vp).copy_(pre_logits[:, None, :])             # the prompt's logits row feeds the clip's K rows (all but beam 0 carry -1e9)
+        del kc0, vc0
+        select()
+
+        def step():
+            _lib.check(L_.ta_lm_decode_step(C.byref(self._w), ptr(next_ids), ptr(pos), ptr(kmask), ptr(slot_dev), R, ptr(kc),
+                                            ptr(vc), Lmax, ptr(logits), ptr(lora_img), ptr(ws), ws.numel(), stream()),
+                       "ta_lm_decode_step")
+            select()
+
+        graph = None
+        want_graph = use_graph and dev.type == "cuda" and not _lib.DRY_RUN and max_new > 3
+        n_steps = 1
+        for t in range(1, max_new):
+            if t % sync_every == 0 and int(alive.item()) == 0:
+                break
+            if graph is not None:
+                graph.replay()
+            elif want_graph and t == 2:
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    step()
+                graph.replay()                      # capture records, it does not run
+            else:
+                step()
+            n_steps += 1
+        lens = pool_len[:, :nrs]
+        n_new = int(lens.max().item()) if lens.numel() else 0
+        seqs = pool_seq[:, :nrs, :n_new].reshape(B * nrs, n_new).contiguous()
+        scores = pool_score[:, :nrs].reshape(B * nrs).contiguous()
+        if not return_trace:
+            return seqs, scores
+        trace = dict(n_steps=n_steps, cand_score=tr["cand_score"][:n_steps], cand_flat=tr["cand_flat"][:n_steps],
+                     running_sequences=tr["run_seq"][:n_steps].reshape(n_steps, B, K, max_new),
+                     running_scores=tr["run_score"][:n_steps].reshape(n_steps, B, K), parent=tr["parent"][:n_steps].reshape(n_steps, B, K),
+                     pool=dict(sequences=pool_seq, scores=pool_score, lengths=pool_len, finished=pool_fin),
+                     final_running_sequences=run_seq.reshape(B, K, max_new), final_running_scores=run_score.reshape(B, K),
+                     heuristic_unsatisfied=heur, clip_done=clip_done, cache=(kc, vc), prompt_len=L, n_candidates=M)
+        return seqs, scores, trace
+
 
 def _lora_drop_desc(d):
     """(p, seed, offset) -> ta_lora_dropout, or None when dropout is off (None or p == 0: the plain entry points run)."""

@@ -903,6 +903,138 @@ def logits_warp_ext(logits, V, min_p=None, typical_p=None, epsilon_cutoff=None, 
     return logits
 
 
+# ----------------------------------------------------------------------------- beam search (csrc/beam.hip)
+MAX_BEAMS = 8             # BM_MAXK / BM_MAXM / BM_MAXEOS of csrc/beam.hip
+MAX_BEAM_CANDIDATES = 32
+MAX_BEAM_EOS = 3
+BEAM_STATE = ("run_seq", "run_score", "parent", "next_ids", "pool_seq", "pool_score", "pool_len", "pool_fin", "heur", "clip_done",
+              "step_dev", "slot_dev", "pos", "kmask", "n_unfinished")      # ta_beam_advance's in/out tensors, in argument order
+
+
+def beam_length_divisors(length_penalty, max_new):
+    """f32 [max_new] with d[n - 1] = float32(float(n) ** length_penalty): the divisors HF's _update_finished_beams and
+    _check_early_stop_heuristic form as Python floats (``(cur_len + 1 - decoder_prompt_len) ** length_penalty``), by the same ``pow``."""
+    d = torch.ones(max(int(max_new), 1), dtype=torch.float64)
+    for n in range(1, int(max_new) + 1):
+        try:
+            d[n - 1] = float(n) ** float(length_penalty)
+        except OverflowError:
+            d[n - 1] = float("inf")
+    return d.to(F32)
+
+
+def beam_candidates(num_beams, n_eos):
+    """M = max(2, 1 + n_eos) * num_beams (``beams_to_keep`` of HF's _beam_search); ValueError outside the library's envelope."""
+    K, n_eos = int(num_beams), int(n_eos)
+    if not 1 <= K <= MAX_BEAMS:
+        raise ValueError(f"num_beams = {K} is outside [1, {MAX_BEAMS}]")
+    if not 0 <= n_eos <= MAX_BEAM_EOS:
+        raise ValueError(f"{n_eos} eos ids: beam search takes at most {MAX_BEAM_EOS}")
+    return max(2, 1 + n_eos) * K
+
+
+def beam_logprobs(logits, V):
+    """ta_beam_logprobs_f32: log_softmax over the first ``V`` columns of f32 ``logits`` [R, ld], IN PLACE (-inf stays -inf, columns
+    >= V untouched).  -> logits."""
+    R, V, ld = _logits_rows(logits, V, "beam_logprobs")
+    check(lib().ta_beam_logprobs_f32(ptr(logits), ld, V, R, stream()), "ta_beam_logprobs_f32")
+    return logits
+
+
+def beam_topk(rows, V, score, M):
+    """ta_beam_topk_f32: ``rows`` f32 [B * K, ld] (V valid columns), ``score`` f32 [B, K] -> (cand_score f32 [B, M], cand_flat i32
+    [B, M]): per clip the M largest of float32(rows[b * K + k, v] + score[b, k]), descending, lowest flat index k * V + v on ties."""
+    R, V, ld = _logits_rows(rows, V, "beam_topk")
+    if score.dim() != 2 or score.dtype != F32 or not score.is_contiguous() or score.device != rows.device or score.numel() != R:
+        raise ValueError(f"beam_topk: score must be a contiguous f32 [B, K] with B * K = {R} on the rows' device")
+    B, K, M = score.shape[0], score.shape[1], int(M)
+    if not 1 <= K <= MAX_BEAMS or not 1 <= M <= min(MAX_BEAM_CANDIDATES, K * V):
+        raise ValueError(f"beam_topk: K = {K} must be within [1, {MAX_BEAMS}] and M = {M} within [1, {min(MAX_BEAM_CANDIDATES, K * V)}]")
+    dev = rows.device
+    cs, cf = torch.empty((B, M), device=dev, dtype=F32), torch.empty((B, M), device=dev, dtype=torch.int32)
+    nb = lib().ta_beam_topk_workspace_bytes(B, K, V, M)
+    ws = torch.empty(max(nb, 8), device=dev, dtype=torch.uint8)
+    check(lib().ta_beam_topk_f32(ptr(rows), ld, V, ptr(score), B, K, M, ptr(cs), ptr(cf), ptr(ws), ws.numel(), stream()), "ta_beam_topk_f32")
+    return cs, cf
+
+
+def beam_advance(cand_score, cand_flat, V, eos_ids, pad_id, len_div, early_stopping, length_penalty, state, trace=None):
+    """ta_beam_advance: one step of HF's beam bookkeeping on device state.  ``cand_score`` f32 / ``cand_flat`` i32 [B, M] from
+    ``beam_topk``; ``len_div`` = ``beam_length_divisors(length_penalty, max_new)`` on the device; ``early_stopping`` False / True /
+    "never"; ``state``: dict of the ``BEAM_STATE`` tensors (updated IN PLACE; shapes in include/ta355.h); ``trace``: None or a dict with
+    cand_score, cand_flat, run_seq, run_score, parent buffers [max_new, ...].  -> state."""
+    if cand_score.dim() != 2 or cand_score.dtype != F32 or cand_flat.dtype != torch.int32 or cand_flat.shape != cand_score.shape:
+        raise ValueError("beam_advance: cand_score f32 [B, M] and cand_flat i32 [B, M] are required")
+    missing = [k for k in BEAM_STATE if k not in state]
+    if missing:
+        raise ValueError(f"beam_advance: state lacks {missing}")
+    B, M = cand_score.shape
+    R, max_new = state["run_seq"].shape
+    K = R // max(B, 1)
+    eos_ids = [int(e) for e in eos_ids]
+    if K * B != R or beam_candidates(K, len(eos_ids)) != M:
+        raise ValueError(f"beam_advance: {R} rows, {B} clips and {len(eos_ids)} eos ids do not give M = {M} candidates")
+    if early_stopping not in (False, True, "never"):
+        raise ValueError(f"early_stopping must be False, True or 'never'; got {early_stopping!r}")
+    if K * max_new > 12288:
+        raise ValueError(f"beam_advance: num_beams * max_new = {K * max_new} exceeds 12288")
+    if len_div.dtype != F32 or len_div.numel() != max_new:
+        raise ValueError(f"beam_advance: len_div must be f32 [{max_new}]")
+    for k, dt in (("run_seq", torch.int64), ("next_ids", torch.int64), ("pool_seq", torch.int64), ("run_score", F32), ("pool_score", F32)):
+        if state[k].dtype != dt or not state[k].is_contiguous():
+            raise ValueError(f"beam_advance: state[{k!r}] must be a contiguous {dt} tensor")
+    for k in BEAM_STATE:
+        if k not in ("run_seq", "next_ids", "pool_seq", "run_score", "pool_score") and (state[k].dtype != torch.int32 or not state[k].is_contiguous()):
+            raise ValueError(f"beam_advance: state[{k!r}] must be a contiguous int32 tensor")
+    if state["kmask"].dim() != 2 or state["kmask"].shape[0] != R or state["pos"].numel() != R or state["pool_seq"].numel() != R * max_new:
+        raise ValueError("beam_advance: pos [R], kmask [R, Lmax] and pool_seq [B, K, max_new] are required")
+    es = 2 if early_stopping == "never" else int(bool(early_stopping))
+    dev = cand_score.device
+    eos = torch.tensor(eos_ids or [-1], dtype=torch.int64, device=dev)
+    tr = [None] * 5 if trace is None else [ptr(trace[k]) for k in ("cand_score", "cand_flat", "run_seq", "run_score", "parent")]
+    s = state
+    check(lib().ta_beam_advance(ptr(cand_score.contiguous()), ptr(cand_flat.contiguous()), B, K, M, int(V), ptr(eos), len(eos_ids), int(pad_id),
+                                max_new, ptr(len_div), es, int(es == 2 and float(length_penalty) > 0.0), ptr(s["run_seq"]), ptr(s["run_score"]),
+                                ptr(s["parent"]), ptr(s["next_ids"]), ptr(s["pool_seq"]), ptr(s["pool_score"]), ptr(s["pool_len"]),
+                                ptr(s["pool_fin"]), ptr(s["heur"]), ptr(s["clip_done"]), ptr(s["step_dev"]), ptr(s["slot_dev"]), ptr(s["pos"]),
+                                ptr(s["kmask"]), s["kmask"].shape[1], ptr(s["n_unfinished"]), *tr, stream()), "ta_beam_advance")
+    return state
+
+
+def _beam_cache(t, what):
+    if t.dim() != 5 or t.dtype != BF16 or not t.is_contiguous() or t.shape[4] % 8:
+        raise ValueError(f"{what}: caches must be contiguous bf16 [layers, rows, kv_heads, slots, head_dim] with head_dim a multiple of 8")
+    return t.shape
+
+
+def kv_beam_expand(ksrc, vsrc, num_beams, Lmax, L=None):
+    """ta_kv_beam_expand: the B-row prompt caches [layers, B, kv_heads, Lsrc, head_dim] -> new caches [layers, B * K, kv_heads, Lmax,
+    head_dim] whose rows b * K .. b * K + K - 1 hold slots [0, L) of clip b (L defaults to Lsrc; the other slots are uninitialised)."""
+    nl, B, hkv, Ls, hd = _beam_cache(ksrc, "kv_beam_expand")
+    K, L = int(num_beams), int(Ls if L is None else L)
+    if vsrc.shape != ksrc.shape or vsrc.dtype != BF16 or not vsrc.is_contiguous() or not 1 <= K <= MAX_BEAMS or not 0 <= L <= min(Ls, int(Lmax)):
+        raise ValueError("kv_beam_expand: the two caches must agree, 1 <= num_beams <= 8 and L <= min(Lsrc, Lmax)")
+    kd, vd = (torch.empty((nl, B * K, hkv, int(Lmax), hd), dtype=BF16, device=ksrc.device) for _ in range(2))
+    check(lib().ta_kv_beam_expand(ptr(ksrc), ptr(vsrc), ptr(kd), ptr(vd), nl, B, K, hkv, L, Ls, int(Lmax), hd, stream()), "ta_kv_beam_expand")
+    return kd, vd
+
+
+def kv_beam_reorder(kcache, vcache, num_beams, L, max_new, parent, slot_dev):
+    """ta_kv_beam_reorder, IN PLACE: slots [L, *slot_dev) of row b * K + j of both caches take those of row b * K + parent[b * K + j]
+    (``parent`` i32 [R], ``slot_dev`` i32 [1], both on the device).  -> (kcache, vcache)."""
+    nl, R, hkv, Lmax, hd = _beam_cache(kcache, "kv_beam_reorder")
+    K, L, max_new = int(num_beams), int(L), int(max_new)
+    if vcache.shape != kcache.shape or vcache.dtype != BF16 or not vcache.is_contiguous() or not 1 <= K <= MAX_BEAMS or R % K:
+        raise ValueError("kv_beam_reorder: the two caches must agree and hold a multiple of num_beams (1..8) rows")
+    if L < 0 or max_new < 0 or L + max_new > Lmax:
+        raise ValueError(f"kv_beam_reorder: L + max_new = {L + max_new} exceeds the cache's {Lmax} slots")
+    if parent.dtype != torch.int32 or parent.numel() != R or not parent.is_contiguous() or slot_dev.dtype != torch.int32 or slot_dev.numel() != 1:
+        raise ValueError(f"kv_beam_reorder: parent must be a contiguous int32 [{R}] and slot_dev an int32 [1]")
+    check(lib().ta_kv_beam_reorder(ptr(kcache), ptr(vcache), nl, R // K, K, hkv, L, Lmax, hd, max_new, ptr(parent), ptr(slot_dev), stream()),
+          "ta_kv_beam_reorder")
+    return kcache, vcache
+
+
 # ----------------------------------------------------------------------------- wav2vec2 acoustic model (csrc/wav2vec2.hip)
 def w2v_conv0_gn_gelu(wav, lens, w, gn_w, gn_b, eps=1e-5, out=None, out_rpb=None):
     """ta_w2v_conv0_gn_gelu: conv layer 0 (k 10, stride 5) + per-channel GroupNorm over each clip's own frames + exact GELU.

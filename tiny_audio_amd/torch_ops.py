@@ -17,6 +17,8 @@ reference has no FFI; its seams are nn.Module boundaries,
                                asks HF for no scores (tiny_audio/asr_modeling.py:631-637)
     ta355::logits_sequence_bias, logits_step_rules, logits_warp_ext   HF's remaining single-hypothesis logits processors, which the
                                reference reaches through **generate_kwargs (tiny_audio/asr_modeling.py:625-637); in place
+    ta355::beam_logprobs, beam_topk, beam_advance, kv_beam_expand, kv_beam_reorder   one iteration of HF's _beam_search
+                               (TF:generation/utils.py), which the reference reaches with num_beams > 1 (tiny_audio/asr_config.py:42)
     ta355::encoder_forward     model.audio_tower(input_features=...)      tiny_audio/asr_modeling.py:448-450
     ta355::encoder_forward_ragged   the same seam, every clip at its own length (opt-in; what the reference computes for a
                                clip encoded alone, tiny_audio/asr_modeling.py:198-200)
@@ -224,6 +226,60 @@ def logits_warp_ext(logits: Tensor, V: int, min_p: float, typical_p: float, epsi
     """MinP, Typical, Epsilon and Eta warpers on f32 logits [B, ld], IN PLACE, in HF's order (off: 0, 1, 0, 0)."""
     from . import ops
     ops.logits_warp_ext(logits, V, min_p, typical_p, epsilon_cutoff, eta_cutoff)
+
+
+# ============================================================================ beam search
+@torch.library.custom_op("ta355::beam_logprobs", mutates_args=("logits",))
+def beam_logprobs(logits: Tensor, V: int) -> None:
+    """log_softmax over the first V columns of f32 logits [R, ld], IN PLACE (``ops.beam_logprobs``; HF _beam_search's first operation on a
+    step's logits).  No autograd."""
+    from . import ops
+    ops.beam_logprobs(logits, V)
+
+
+@torch.library.custom_op("ta355::beam_topk", mutates_args=())
+def beam_topk(rows: Tensor, V: int, score: Tensor, M: int) -> Tuple[Tensor, Tensor]:
+    """HF _get_top_k_continuations: f32 rows [B * K, ld] and running scores f32 [B, K] -> (cand_score f32 [B, M], cand_flat i32 [B, M]),
+    descending, lowest flat index k * V + v on ties (``ops.beam_topk``)."""
+    from . import ops
+    return ops.beam_topk(rows, V, score, M)
+
+
+@beam_topk.register_fake
+def _(rows, V, score, M):
+    return rows.new_empty((score.shape[0], M)), rows.new_empty((score.shape[0], M), dtype=torch.int32)
+
+
+@torch.library.custom_op("ta355::beam_advance", mutates_args=("state",))
+def beam_advance(cand_score: Tensor, cand_flat: Tensor, V: int, eos_ids: Sequence[int], pad_id: int, len_div: Tensor, early_stopping: int,
+                 length_penalty: float, state: List[Tensor]) -> None:
+    """One step of HF's beam bookkeeping (``ops.beam_advance``) on the 15 state tensors of ``ops.BEAM_STATE``, in that order, IN PLACE.
+    ``early_stopping``: 0 False, 1 True, 2 "never"."""
+    from . import ops
+    ops.beam_advance(cand_score, cand_flat, V, list(eos_ids), pad_id, len_div, "never" if early_stopping == 2 else bool(early_stopping),
+                     length_penalty, dict(zip(ops.BEAM_STATE, state)))
+
+
+@torch.library.custom_op("ta355::kv_beam_expand", mutates_args=())
+def kv_beam_expand(ksrc: Tensor, vsrc: Tensor, num_beams: int, Lmax: int) -> Tuple[Tensor, Tensor]:
+    """The B-row prompt caches bf16 [layers, B, kv_heads, L, head_dim] -> caches [layers, B * num_beams, kv_heads, Lmax, head_dim] with
+    every clip's slots [0, L) in its num_beams rows (``ops.kv_beam_expand``)."""
+    from . import ops
+    return ops.kv_beam_expand(ksrc, vsrc, num_beams, Lmax)
+
+
+@kv_beam_expand.register_fake
+def _(ksrc, vsrc, num_beams, Lmax):
+    nl, B, h, _, d = ksrc.shape
+    return ksrc.new_empty((nl, B * num_beams, h, Lmax, d)), ksrc.new_empty((nl, B * num_beams, h, Lmax, d))
+
+
+@torch.library.custom_op("ta355::kv_beam_reorder", mutates_args=("kcache", "vcache"))
+def kv_beam_reorder(kcache: Tensor, vcache: Tensor, num_beams: int, L: int, max_new: int, parent: Tensor, slot_dev: Tensor) -> None:
+    """Slots [L, *slot_dev) of the num_beams rows of every clip permuted by ``parent`` i32 [R], IN PLACE, both caches, every layer
+    (``ops.kv_beam_reorder``; HF's reorder_cache)."""
+    from . import ops
+    ops.kv_beam_reorder(kcache, vcache, num_beams, L, max_new, parent, slot_dev)
 
 
 # ============================================================================ frozen encoder
@@ -691,4 +747,5 @@ lm_forward_loss.register_autograd(_lm_bwd, setup_context=_lm_setup)
 OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backward", "moe_projector", "moe_projector_backward",
              "lm_forward_loss", "lm_backward", "whisper_encoder_forward", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
-             "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long")
+             "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long", "beam_logprobs", "beam_topk",
+             "beam_advance", "kv_beam_expand", "kv_beam_reorder")
