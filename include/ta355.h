@@ -567,6 +567,18 @@ int ta_lm_backward_seg(const ta_lm_weights* w, const int* src_row, const int* km
                        const int* label_rows, int n_label_rows, float* d_audio, long n_audio_rows, float* d_embeds,
                        const ta_lm_lora_grads* lora_grads, const ta_lm_wgrads* wgrads, const long* ids, const void* tape, void* ws,
                        long ws_bytes, const ta_lora_dropout* drop, hipStream_t st);
+/* The LM forward with loss options (ta_ce_options, below at ta_cross_entropy_opt; replaces TF:trainer_pt_utils.py LabelSmoother over
+ * TF:loss/loss_utils.py fixed_cross_entropy): ta_lm_forward_loss_seg plus `ce`.  One entry point serves the three call shapes: seg NULL
+ * and drop NULL is the plain forward, seg NULL the _ex one.  `loss` accumulates loss_scale * sum of the objective (summed in row order
+ * from ce->obj [n_label_rows]), nll_rows stays the plain NLL, and the tape's dlogits are the objective's: every ta_lm_backward* entry
+ * point consumes them unchanged.  ce NULL is exactly ta_lm_forward_loss_seg.  eps > 0 or zc > 0 with ce->obj NULL is TA_ERR_ARG: the
+ * training step's loss is never summed with float atomics. */
+struct ta_ce_options;
+int ta_lm_forward_loss_opt(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                           const int* kmask, const int* pos, const int* seg, int B, int L, const int* label_rows,
+                           const long* label_targets, int n_label_rows, float loss_scale, float* loss,
+                           float* nll_rows, void* logits_out, void* tape, void* ws, long ws_bytes,
+                           const ta_lora_dropout* drop, const struct ta_ce_options* ce, hipStream_t st);
 /* The attention entry points of the LM over packed rows (causal, head_dim 128; seg NULL = the plain call). */
 int ta_attention_fwd_seg(const void* Q, const void* K, const void* VT, void* O, float* LSE, const int* kmask, const int* seg,
                          int B, int Hq, int Hkv, int L, int Lp, float scale, hipStream_t st);
@@ -780,6 +792,25 @@ int ta_debug_occupy(int workgroups, double micros, void* buf, long bytes, hipStr
 int ta_cross_entropy(const void* logits, int logits_bf16, long ldl, const int* rows, const long* targets, int n, int V,
                      float scale, float* nll, float* loss_accum, void* dlogits_bf16, long ldd, hipStream_t st);
 int ta_label_rows(const long* labels, int B, int L, int* rows, long* targets, int* n_out, hipStream_t st);
+/* ---- LM loss options, fused into the cross-entropy pass (TF:trainer_pt_utils.py LabelSmoother, i.e. TrainingArguments.
+ * label_smoothing_factor, and torch.nn.functional.cross_entropy(label_smoothing=) inside TF:loss/loss_utils.py fixed_cross_entropy;
+ * z-loss: coef * logsumexp^2 per target row, PaLM).  Per row r with a valid target t, over the V true columns:
+ *     nll_r = lse_r - z_rt                                                        (what `nll` keeps holding)
+ *     obj_r = (1 - eps) nll_r + eps (lse_r - mean_v z_rv) + zc lse_r^2            (what the loss sums, times scale)
+ *     dlogits_rv = scale (p_rv (1 + 2 zc lse_r) - (1 - eps) [v == t] - eps / V),  p_rv = exp(z_rv - lse_r)
+ * Rows with an invalid target keep nll = obj = 0 and a zero dlogits row, columns >= V exact zeros.  The mean is accumulated as
+ * sum_v (z_rv - z_r0), so it is as invariant to a shift of the row as lse - z_t.  0 <= eps < 1 and zc >= 0, else TA_ERR_ARG. */
+typedef struct ta_ce_options {
+  float eps;                        /* label smoothing; 0 = off */
+  float zc;                         /* z-loss coefficient; 0 = off */
+  float* obj;                       /* [n] per-row objective, or NULL.  With it the loss is summed from it in row order (the same
+                                     * bits on every run); without it every row adds itself to loss_accum atomically. */
+} ta_ce_options;
+/* ta_cross_entropy with options (replaces TF:trainer_pt_utils.py LabelSmoother over TF:loss/loss_utils.py fixed_cross_entropy).
+ * opt NULL, or eps == zc == 0 with obj NULL, is exactly ta_cross_entropy (the plain entry point is this with NULL). */
+int ta_cross_entropy_opt(const void* logits, int logits_bf16, long ldl, const int* rows, const long* targets, int n, int V,
+                         float scale, float* nll, float* loss_accum, void* dlogits_bf16, long ldd, const ta_ce_options* opt,
+                         hipStream_t st);
 
 /* optimizer: clip_grad_norm_(max_norm) + AdamW on fp32 masters (configs/training/production.yaml:5-9) */
 /* accum[0] += sum(g^2), DETERMINISTICALLY (two launches: per-block partials into scratch, then one block adds them in index order):

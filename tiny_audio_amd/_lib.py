@@ -124,6 +124,11 @@ class LoraDropout(C.Structure):
     _fields_ = [("p", C.c_float), ("seed", C.c_ulonglong), ("offset", C.c_ulonglong)]
 
 
+class CeOptions(C.Structure):
+    """ta_ce_options (include/ta355.h): label smoothing, z-loss coefficient, the per-row objective buffer."""
+    _fields_ = [("eps", C.c_float), ("zc", C.c_float), ("obj", C.c_void_p)]
+
+
 class LmLayerWgrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dwqkv", "dwo", "dwgu", "dwd", "dln_in", "dln_post", "dqn", "dkn")]
 

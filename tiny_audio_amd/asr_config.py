@@ -200,7 +200,8 @@ class ASRConfig:
                  router_aux_loss_coef: float = 0.01, use_lora: bool = False, lora_rank: int = 8, lora_alpha: int = 32,
                  lora_dropout: float = 0.0, lora_target_modules: Optional[list] = None, freeze_projector: bool = False,
                  freeze_language_model: bool = True, max_new_tokens: int = 128, audio_config=None, text_config=None,
-                 audio_token_id: int = 151669, pad_token_id: int = 151643, eos_token_id: int = 151645, **kwargs):
+                 audio_token_id: int = 151669, pad_token_id: int = 151643, eos_token_id: int = 151645,
+                 label_smoothing: float = 0.0, lm_z_loss_coef: float = 0.0, **kwargs):
         self.audio_model_id = audio_model_id
         self.text_model_id = text_model_id
         self.attn_implementation = attn_implementation
@@ -225,6 +226,14 @@ class ASRConfig:
         self.freeze_projector = freeze_projector
         self.freeze_language_model = freeze_language_model
         self.max_new_tokens = max_new_tokens
+        # LM loss options (not in the reference's config: HF has label_smoothing_factor on TrainingArguments, where a stock Trainer
+        # smooths on the full logits): label smoothing and the coefficient of logsumexp^2, both inside the cross-entropy launch
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1); got {label_smoothing}")
+        if not float(lm_z_loss_coef) >= 0.0:
+            raise ValueError(f"lm_z_loss_coef must be >= 0; got {lm_z_loss_coef}")
+        self.label_smoothing = float(label_smoothing)
+        self.lm_z_loss_coef = float(lm_z_loss_coef)
         if isinstance(audio_config, (EncoderConfig, WhisperEncoderConfig)):
             self.audio_config = audio_config
         elif is_whisper(audio_model_id, audio_config):

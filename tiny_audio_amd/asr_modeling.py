@@ -20,7 +20,7 @@ from . import _lib, ops
 from .asr_config import ASRConfig, WhisperEncoderConfig, compute_encoder_output_length
 from .encoder import GlmAsrEncoderMI355X
 from .whisper_encoder import WhisperEncoderMI355X
-from .language_model import NO_NORM_FULL_FT, FrozenLMLoss, Qwen3MI355X
+from .language_model import NO_NORM_FULL_FT, FrozenLMLoss, Qwen3MI355X, check_loss_options
 from .ops import F32
 from .projectors import PROJECTOR_CLASSES
 
@@ -410,7 +410,8 @@ class ASRModel(nn.Module):
                 labels: Optional[torch.Tensor] = None, audio_token_counts: Optional[torch.Tensor] = None,
                 num_items_in_batch=None, return_logits: bool = True, frame_keep=None, after_encoder=None,
                 position_ids: Optional[torch.Tensor] = None, past_key_values=None, inputs_embeds=None,
-                use_cache: Optional[bool] = None, cache_position=None, segment_ids: Optional[torch.Tensor] = None, **kwargs):
+                use_cache: Optional[bool] = None, cache_position=None, segment_ids: Optional[torch.Tensor] = None,
+                z_loss_coef: Optional[float] = None, **kwargs):
         """Training/eval forward (tiny_audio/asr_modeling.py:481-533).
 
         ``segment_ids`` [R, L] (sequence packing, ``DataCollator(pack_to=...)``; not in the reference): a row holds several clips'
@@ -433,6 +434,13 @@ class ASRModel(nn.Module):
         a NAMED parameter containing "label" would enter HF Trainer's ``label_names`` -- find_labels scans the signature -- and
         Trainer.predict would then treat every batch as unlabelled) lets a
         collator that already knows the label positions on the host avoid one device->host sync.
+
+        ``label_smoothing`` (through ``**kwargs`` for the same reason) and ``z_loss_coef``: the LM loss options for this call;
+        ``None`` takes ``config.label_smoothing`` / ``config.lm_z_loss_coef`` (default 0).  As in HF they apply whenever labels are
+        given, in ``eval()`` too: ``loss`` / ``loss_ce`` are then loss_scale * sum of
+        (1 - eps) nll + eps (lse - mean(logits)) + z_loss_coef lse^2 over the label tokens (LabelSmoother /
+        cross_entropy(label_smoothing=eps), plus the z-loss), computed with its gradient inside the cross-entropy launch; ``nll``
+        stays the plain per-token NLL.
         """
         dev = self.device_
         if inputs_embeds is not None or past_key_values is not None or use_cache or cache_position is not None:
@@ -442,6 +450,9 @@ class ASRModel(nn.Module):
                                       "runs from input_ids (+ input_features) without a KV cache; use generate() for decoding")
         if input_ids is None:
             raise ValueError("input_ids is required")
+        eps, zc = kwargs.pop("label_smoothing", None), z_loss_coef
+        eps, zc = check_loss_options(getattr(self.config, "label_smoothing", 0.0) if eps is None else eps,
+                                     getattr(self.config, "lm_z_loss_coef", 0.0) if zc is None else zc)
         self._apply_stream_modes()
         ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
         B, L = ids.shape
@@ -505,12 +516,15 @@ class ASRModel(nn.Module):
                 rows, targets, n = ops.label_rows(labels.to(device=dev, dtype=torch.int64).contiguous())
                 n_lab = int(n.item())                                                      # one host sync
         scale = 1.0 / float(num_items_in_batch if num_items_in_batch is not None else max(n_lab, 1))
+        if labels is None:                                    # (validated above; without labels there is no loss to apply them to)
+            eps, zc = 0.0, 0.0
         if audio is None:
             audio = torch.zeros((1, self.config.llm_dim), device=dev, dtype=F32)
         loss, nll, logits = FrozenLMLoss.apply(audio, self.language_model, ids, src_row, kmask, rows, targets, n_lab,
                                                scale, bool(return_logits),
                                                *(self.language_model.lora_parameters() or self.language_model.ft_parameters()), pos=pos,
-                                               **({} if seg is None else {"seg": seg}))
+                                               **({} if seg is None else {"seg": seg}),
+                                               **({"label_smoothing": eps, "z_loss": zc} if (eps > 0.0 or zc > 0.0) else {}))
         V = self.config.text_config.vocab_size
         logits = logits.reshape(B, L, -1)[:, :, :V] if return_logits else None
         aux, loss_ce = None, loss

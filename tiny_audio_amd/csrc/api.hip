@@ -630,7 +630,10 @@ static int lm_forward_loss_impl(const ta_lm_weights* w, const long* ids, const i
                                 const int* kmask, const int* pos, const int* seg, int B, int L, const int* label_rows,
                                 const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
                                 void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
-                                hipStream_t st) {
+                                const ta_ce_options* ce, hipStream_t st) {
+  // options without the per-row objective buffer would sum the loss with one float atomic per row: not the same bits on every run
+  if (ce && (!(ce->eps >= 0.f) || !(ce->eps < 1.f) || !(ce->zc >= 0.f) || ((ce->eps > 0.f || ce->zc > 0.f) && !ce->obj)))
+    return TA_ERR_ARG;
   LoraDropDev dd;
   const LoraDropDev* dp = nullptr;
   RC(lm_lora_drop(w, drop, &dd, &dp));
@@ -660,8 +663,9 @@ static int lm_forward_loss_impl(const ta_lm_weights* w, const long* ids, const i
     // The labelled logits are bf16 -- what the reference's bf16 lm_head produces before `logits.float()`
     // (TF:loss/loss_utils.py:55) -- which halves the bytes of the head epilogue and of the CE pass (0.25 ms per step).
     RC(gemm(s.hl, w->embed_bf16, s.logits, n_lab, w->vocab_pad, d.D, nullptr, nullptr, 0, 1, st));
-    RC(ta_cross_entropy(s.logits, 1, w->vocab_pad, nullptr, label_targets, n_lab, w->vocab, loss_scale, nll_rows, loss,
-                        t.dlogits, w->vocab_pad, st));
+    // ce NULL (every entry point but _opt): the kernel without options
+    RC(ta_cross_entropy_opt(s.logits, 1, w->vocab_pad, nullptr, label_targets, n_lab, w->vocab, loss_scale, nll_rows, loss,
+                            t.dlogits, w->vocab_pad, ce, st));
   }
   return TA_OK;
 }
@@ -671,7 +675,7 @@ extern "C" int ta_lm_forward_loss(const ta_lm_weights* w, const long* ids, const
                                   const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
                                   void* logits_out, void* tape, void* ws, long ws_bytes, hipStream_t st) {
   return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, nullptr, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
-                              nll_rows, logits_out, tape, ws, ws_bytes, nullptr, st);
+                              nll_rows, logits_out, tape, ws, ws_bytes, nullptr, nullptr, st);
 }
 extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
                                      const int* kmask, const int* pos, int B, int L, const int* label_rows,
@@ -679,7 +683,7 @@ extern "C" int ta_lm_forward_loss_ex(const ta_lm_weights* w, const long* ids, co
                                      void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
                                      hipStream_t st) {
   return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, nullptr, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
-                              nll_rows, logits_out, tape, ws, ws_bytes, drop, st);
+                              nll_rows, logits_out, tape, ws, ws_bytes, drop, nullptr, st);
 }
 // Sequence packing: rows that hold several clips back to back (include/ta355.h).  `seg` is the table ta_segment_table wrote for these
 // rows; everything but attention is row-local, so it reaches the attention launches only.  NULL = ta_lm_forward_loss_ex.
@@ -689,7 +693,17 @@ extern "C" int ta_lm_forward_loss_seg(const ta_lm_weights* w, const long* ids, c
                                       void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
                                       hipStream_t st) {
   return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, seg, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
-                              nll_rows, logits_out, tape, ws, ws_bytes, drop, st);
+                              nll_rows, logits_out, tape, ws, ws_bytes, drop, nullptr, st);
+}
+// LM loss options (include/ta355.h ta_ce_options): the _seg call with the options the cross-entropy launch takes; the backward is unchanged,
+// it consumes the dlogits this forward leaves on the tape
+extern "C" int ta_lm_forward_loss_opt(const ta_lm_weights* w, const long* ids, const int* src_row, const float* audio,
+                                      const int* kmask, const int* pos, const int* seg, int B, int L, const int* label_rows,
+                                      const long* label_targets, int n_lab, float loss_scale, float* loss, float* nll_rows,
+                                      void* logits_out, void* tape, void* ws, long ws_bytes, const ta_lora_dropout* drop,
+                                      const ta_ce_options* ce, hipStream_t st) {
+  return lm_forward_loss_impl(w, ids, src_row, audio, kmask, pos, seg, B, L, label_rows, label_targets, n_lab, loss_scale, loss,
+                              nll_rows, logits_out, tape, ws, ws_bytes, drop, ce, st);
 }
 
 // ---------------------------------------------------------------------------- greedy decoding: prompt pass

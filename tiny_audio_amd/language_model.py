@@ -521,13 +521,18 @@ class Qwen3MI355X(torch.nn.Module):
 
     # ------------------------------------------------------------------ raw forward / backward (no autograd)
     def forward_loss(self, input_ids, src_row, audio, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-                     want_logits=False, pos=None, lora_dropout=None, seg=None):
+                     want_logits=False, pos=None, lora_dropout=None, seg=None, label_smoothing=0.0, z_loss=0.0):
         """Returns (loss[1] f32, nll[n] f32, logits or None, ctx) -- ctx feeds ``backward_from_ctx``.
+        ``label_smoothing`` (HF label_smoothing_factor, 0 <= eps < 1) and ``z_loss`` (coefficient of logsumexp^2 per target row,
+        >= 0): the loss options of include/ta355.h ``ta_ce_options``, computed inside the cross-entropy launch.  With either set,
+        ``loss`` is the objective and ctx["obj"] its per-row terms; ``nll`` stays the plain NLL, and the backward needs nothing new
+        (the tape's dlogits are the objective's).  Both 0: the call without options.
         ``lora_dropout``: (p, seed, offset) of ``next_lora_dropout()`` or None; kept in ctx for the backward.
         ``seg``: int32 [2, B*L], the table of ``ops.segment_table`` for packed rows (several clips per row, block-diagonal
         attention), or None; kept in ctx for the backward too."""
         if self._w is None:
             raise _lib.Ta355Error("LM weights not loaded")
+        eps, zc = check_loss_options(label_smoothing, z_loss)
         L_ = _lib.lib()
         B, L = input_ids.shape
         dev = self.device_
@@ -542,14 +547,20 @@ class Qwen3MI355X(torch.nn.Module):
         logits = torch.empty((B * L, self.vocab_pad), device=dev, dtype=BF16) if want_logits else None
         if seg is not None and (seg.dtype != torch.int32 or seg.numel() != 2 * B * L or not seg.is_contiguous()):
             raise ValueError(f"seg must be a contiguous int32 [2, {B * L}] segment table; got {seg.dtype} {tuple(seg.shape)}")
+        obj, ce = None, None
+        if eps > 0.0 or zc > 0.0:
+            obj = torch.zeros(max(n_label_rows, 1), device=dev, dtype=F32)
+            ce = _lib.CeOptions(eps=eps, zc=zc, obj=obj.data_ptr())
         _lm_call("forward", (C.byref(self._w), ptr(input_ids), ptr(src_row), ptr(audio), ptr(kmask), ptr(pos)), seg,
                  (B, L, ptr(label_rows), ptr(label_targets), n_label_rows, loss_scale, ptr(loss), ptr(nll), ptr(logits), ptr(tape),
-                  ptr(ws), ws.numel()), _lora_drop_desc(lora_dropout))
+                  ptr(ws), ws.numel()), _lora_drop_desc(lora_dropout), ce)
         # ``modes``: the tape's residual-stream rows are in the storage dtype this handle carries NOW; the backward must read them as
         # that even if the owner flips ``res_f32`` in between
         ctx = dict(tape=tape, ws=ws, B=B, L=L, src_row=src_row, kmask=kmask, pos=pos, label_rows=label_rows,
                    n_label_rows=n_label_rows, ids=input_ids, lora_dropout=lora_dropout, seg=seg,
                    modes=(bool(self._w.res_f32), bool(self._w.dx_f32)))
+        if obj is not None:
+            ctx["obj"] = obj
         return loss, nll, logits, ctx
 
     def backward_from_ctx(self, ctx, n_audio_rows, want_d_embeds=False, want_d_audio=True):
@@ -1008,17 +1019,30 @@ def _lora_drop_desc(d):
     return _lib.LoraDropout(p=float(d[0]), seed=int(d[1]) & 0xFFFFFFFFFFFFFFFF, offset=int(d[2]) & 0xFFFFFFFFFFFFFFFF)
 
 
+def check_loss_options(label_smoothing, z_loss):
+    """(label_smoothing, z_loss) as floats; ValueError outside 0 <= label_smoothing < 1, z_loss >= 0 (the library's TA_ERR_ARG)."""
+    eps, zc = float(label_smoothing or 0.0), float(z_loss or 0.0)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1); got {label_smoothing}")
+    if not zc >= 0.0:
+        raise ValueError(f"z_loss must be >= 0; got {z_loss}")
+    return eps, zc
+
+
 _LM_ENTRY = {"forward": ("ta_lm_forward_loss", "ta_lm_forward_loss_ex", "ta_lm_forward_loss_seg"),
              "backward": ("ta_lm_backward", "ta_lm_backward_ex", "ta_lm_backward_seg")}
 
 
-def _lm_call(direction, head, seg, tail, drop):
+def _lm_call(direction, head, seg, tail, drop, ce=None):
     """Run the LM entry point of ``direction`` that (seg, drop) select: the plain one with neither, _ex with a dropout descriptor only,
     _seg with a segment table (its descriptor may be NULL).  All three take ``head`` (... pos), then the table, then ``tail``
-    (B ... ws_bytes), then the descriptor, then the stream."""
+    (B ... ws_bytes), then the descriptor, then the stream.  ``ce`` (forward only): a ta_ce_options selects ta_lm_forward_loss_opt,
+    the _seg arguments (table and descriptor may be NULL) followed by the options."""
     plain, ex, packed = _LM_ENTRY[direction]
     d = None if drop is None else C.byref(drop)
-    if seg is not None:
+    if ce is not None:
+        name, args = "ta_lm_forward_loss_opt", (*head, ptr(seg), *tail, d, C.byref(ce), stream())
+    elif seg is not None:
         name, args = packed, (*head, ptr(seg), *tail, d, stream())
     elif drop is not None:
         name, args = ex, (*head, *tail, d, stream())
@@ -1035,6 +1059,8 @@ class FrozenLMLoss:
     One operator pair (``lm_forward_loss`` / ``lm_backward``) serves every configuration: ``seg`` (the table of
     ``ops.segment_table``) selects packed rows, and the (p, seed, offset) of ``lm.next_lora_dropout()`` selects LoRA dropout, p = 0
     being "off".  The autograd node keeps both, and the two residual-stream modes the forward ran in, for ITS backward.
+    ``label_smoothing`` / ``z_loss`` (``forward_loss``) change the loss and the dlogits the forward leaves on the tape; the backward
+    is the same call.
 
     accumulate_into_grad (full decoder fine-tuning under ASRTrainer): the kernels add the LM's weight gradients straight
     into the trainer's flat buffer, so d(loss) cannot be applied to them afterwards.  ASRTrainer is the only caller that
@@ -1043,13 +1069,16 @@ class FrozenLMLoss:
 
     @staticmethod
     def apply(audio_embeds, lm, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale,
-              want_logits, *trainable, pos=None, seg=None):
+              want_logits, *trainable, pos=None, seg=None, label_smoothing=0.0, z_loss=0.0):
         from . import torch_ops
         # training forwards of a p > 0 model only: a fresh Philox offset each; lora_p = 0 is "no dropout"
         drop = lm.next_lora_dropout() or (0.0, 0, 0)
+        # the loss options trail the operator's arguments; left out at 0, the call dispatches as it did before they existed
+        eps, zc = check_loss_options(label_smoothing, z_loss)
+        opts = (eps, zc) if (eps > 0.0 or zc > 0.0) else ()
         loss, nll, logits, _tape, _ws = torch.ops.ta355.lm_forward_loss(
             audio_embeds, list(trainable), torch_ops.register_module(lm), input_ids, src_row, kmask, label_rows, label_targets,
-            int(n_label_rows), float(loss_scale), bool(want_logits), pos, seg, *drop)
+            int(n_label_rows), float(loss_scale), bool(want_logits), pos, seg, *drop, *opts)
         # a fresh tensor: the outputs of a multi-output custom op may not be modified in place, and HF Trainer does
         # `loss *= ...` on what the model returns (TF:trainer.py compute_loss)
         return loss.clone(), nll, logits

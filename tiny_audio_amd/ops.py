@@ -436,6 +436,25 @@ def cross_entropy(logits, targets, V, scale, rows=None, want_dlogits=True, ldd=N
     return loss, nll, dl
 
 
+def cross_entropy_opt(logits, targets, V, scale, label_smoothing=0.0, z_loss=0.0, rows=None, want_dlogits=True, ldd=None):
+    """``cross_entropy`` with the loss options of include/ta355.h ta_ce_options -> (loss, nll, dlogits, obj): loss and dlogits are the
+    objective's, obj its per-row terms, nll stays the plain NLL (both options 0: obj == nll)."""
+    eps, zc = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps < 1.0 or not zc >= 0.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1) and z_loss must be >= 0; got {label_smoothing}, {z_loss}")
+    n = targets.shape[0]
+    ldl = logits.shape[1]
+    ldd = ldd or ldl
+    nll = torch.empty(n, device=logits.device, dtype=F32)
+    obj = torch.empty(n, device=logits.device, dtype=F32)
+    loss = torch.zeros(1, device=logits.device, dtype=F32)
+    dl = torch.empty((n, ldd), device=logits.device, dtype=BF16) if want_dlogits else None
+    ce = _lib.CeOptions(eps=eps, zc=zc, obj=obj.data_ptr())
+    check(lib().ta_cross_entropy_opt(ptr(logits), int(logits.dtype == BF16), ldl, ptr(rows), ptr(targets), n, V, scale,
+                                     ptr(nll), ptr(loss), ptr(dl), ldd, C.byref(ce), stream()), "ta_cross_entropy_opt")
+    return loss, nll, dl, obj
+
+
 def bernoulli_keep(n, keep_prob, seed, device):
     keep = torch.empty(n, device=device, dtype=F32)
     check(lib().ta_bernoulli_keep(ptr(keep), n, keep_prob, seed, stream()), "ta_bernoulli_keep")

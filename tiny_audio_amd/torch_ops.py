@@ -645,26 +645,31 @@ moe_projector.register_autograd(_moe_bwd, setup_context=_moe_setup)
 def lm_forward_loss(audio: Tensor, trainable: Sequence[Tensor], handle: int, input_ids: Tensor, src_row: Optional[Tensor],
                     kmask: Optional[Tensor], label_rows: Optional[Tensor], label_targets: Optional[Tensor], n_label_rows: int,
                     loss_scale: float, want_logits: bool, pos: Optional[Tensor], seg: Optional[Tensor] = None, lora_p: float = 0.0,
-                    lora_seed: int = 0, lora_offset: int = 0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+                    lora_seed: int = 0, lora_offset: int = 0, label_smoothing: float = 0.0,
+                    z_loss: float = 0.0) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """-> (loss f32 [], per-row nll f32 [max(n, 1)], logits bf16 [B*L, vocab_pad] or empty, tape, workspace).
     ``audio`` f32 [rows, D]: the projector's output rows that replace the <audio> positions (``src_row`` from
     ta_audio_index); ``trainable``: the LoRA masters or, with a trainable base LM, its fp32 masters (autograd inputs);
     ``pos`` int32 [B*L]: RoPE position of every token row (the reference's ``position_ids``; None = arange(L) per clip);
     ``seg`` int32 [2, B*L]: the table of ops.segment_table for packed rows (block-diagonal attention inside every row; None = one
     clip per row); ``lora_p``, ``lora_seed``, ``lora_offset``: LoRA dropout (peft lora_dropout p > 0, training forwards), the triple
-    that names the Philox masks (include/ta355.h ta_lora_dropout); lora_p == 0 is "no dropout".  The autograd node keeps the table,
+    that names the Philox masks (include/ta355.h ta_lora_dropout); lora_p == 0 is "no dropout"; ``label_smoothing``, ``z_loss``: the
+    loss options of the cross-entropy launch (include/ta355.h ta_ce_options; both 0 = the call without options): ``loss`` is then the
+    objective, the per-row nll stays plain, and the backward is unchanged.  The autograd node keeps the table,
     the triple and the module's two stream modes and hands them to ITS backward, so gradient accumulation and backwards run out
     of order regenerate the right masks and read the tape as it was recorded."""
     lm = module_of(handle)
     a = audio.detach().to(F32).contiguous()
     loss, nll, logits, c = lm.forward_loss(input_ids, src_row, a, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits,
-                                           pos=pos, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg)
+                                           pos=pos, lora_dropout=(lora_p, lora_seed, lora_offset) if lora_p > 0 else None, seg=seg,
+                                           **({"label_smoothing": label_smoothing, "z_loss": z_loss}
+                                              if (label_smoothing > 0 or z_loss > 0) else {}))
     return loss.reshape(()), nll, (logits if logits is not None else _empty(a.device)), c["tape"], c["ws"]
 
 
 @lm_forward_loss.register_fake
 def _(audio, trainable, handle, input_ids, src_row, kmask, label_rows, label_targets, n_label_rows, loss_scale, want_logits, pos,
-      seg=None, lora_p=0.0, lora_seed=0, lora_offset=0):
+      seg=None, lora_p=0.0, lora_seed=0, lora_offset=0, label_smoothing=0.0, z_loss=0.0):
     lm = module_of(handle)
     B, L = input_ids.shape
     logits = audio.new_empty((B * L, lm.vocab_pad), dtype=BF16) if want_logits else audio.new_empty((0,))
@@ -709,7 +714,7 @@ def _(tape, ws, handle, input_ids, src_row, kmask, label_rows, n_label_rows, n_a
 def _lm_setup(ctx, inputs, output):
     (audio, trainable, handle, input_ids, src_row, kmask, label_rows, _targets, n_label_rows, _scale, _want, pos, seg, *drop) = inputs
     ctx.handle, ctx.n_label_rows, ctx.n_audio, ctx.n_train = handle, n_label_rows, audio.shape[0], len(trainable)
-    ctx.drop = tuple(drop)
+    ctx.drop = tuple(drop[:3])                                # (behind the triple: the loss options, which the backward does not take)
     ctx.module = module_of(handle)
     # this runs on the forward's thread, directly behind the forward: the stream modes its tape was recorded in
     ctx.modes = (ctx.module.res_f32, ctx.module.dx_f32)

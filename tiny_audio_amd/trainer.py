@@ -37,6 +37,7 @@ class TrainingArguments:
     lr_scheduler_type: str = "constant"          # "constant" | "cosine" | "polynomial"
     lr_scheduler_kwargs: dict = field(default_factory=dict)
     gradient_accumulation_steps: int = 1
+    label_smoothing_factor: float = 0.0          # HF's name; > 0 overrides config.label_smoothing in every training forward
 
 
 def lr_multiplier(step: int, args: TrainingArguments) -> float:
@@ -286,8 +287,12 @@ class ASRTrainer:
         after_encoder = self._apply_pending if self._pending is not None else None
         if self._pending is None and self._micro == 0 and self._need_zero:
             self._zero()
+        # label smoothing: handed to the forward, which computes it inside the cross-entropy launch (HF Trainer pops the labels and runs
+        # LabelSmoother on the full logits instead); loss_ce, and so the loss slot of the flat buffer, is then the objective
+        smooth = float(getattr(self.args, "label_smoothing_factor", 0.0) or 0.0)
         out = self.model(**batch, num_items_in_batch=1.0, return_logits=return_logits,
-                         **({"after_encoder": after_encoder} if after_encoder else {}))
+                         **({"after_encoder": after_encoder} if after_encoder else {}),
+                         **({"label_smoothing": smooth} if smooth > 0.0 else {}))
         self.last_logits = out.logits           # None unless return_logits (the reference's outputs.logits [B, L, V])
         ce = getattr(out, "loss_ce", None)
         aux = out.aux_loss if (ce is not None and out.aux_loss is not None and out.aux_loss.numel() > 0) else None
