@@ -1171,6 +1171,57 @@ int ta_spk_panel_update_f32(float* B, long ldb, int b, const float* A, long lda,
 /* Y [N, m] = V [N, c] Z [c, m], m <= TA_SPK_MAX_P (Ritz vectors; a block times the inverse of its Cholesky factor).  Y != V. */
 int ta_spk_panel_combine_f32(const float* V, long ldv, int c, const float* Z, long ldz, int m, float* Y, long ldy, int N, hipStream_t st);
 
+/* ---- long-form segmentation: where to cut a whole recording into encoder windows, at pauses and never beyond the window, and the cut
+ * itself (tiny_audio_amd/csrc/segment.hip; driven by tiny_audio_amd/longform.py).  The reference has no counterpart: its
+ * ASRPipeline.postprocess keeps the first chunk only (tiny_audio/asr_pipeline.py:243-245).  Contract: DESIGN.md section 3, "Long-form
+ * transcription", defined by tests/segment_ref.py.  R recordings in one flat f32 buffer `wav`, recording r at samples
+ * offsets[r] .. offsets[r + 1] (device long[R + 1]); n = its length, T = ceil(n / TA_CUT_HOP); its grid has the positions p = 0 .. T,
+ * p standing for sample TA_CUT_HOP p and T for sample n.  max_n bounds every n (it sizes the workspaces and the rows: ld >= max_T + 1
+ * with max_T = ceil(max_n / TA_CUT_HOP)); a recording with n < 1 or n > max_n is refused: its rows are not written and its n_seg is -1.
+ * Limits (TA_ERR_ARG beyond them): R <= TA_CUT_MAX_RECORDINGS, max_T <= TA_CUT_MAX_POSITIONS (2.9 h), 0 <= h <= TA_CUT_MAX_SMOOTH,
+ * 1 <= min_len, 2 min_len <= max_len <= TA_CUT_MAX_LEN, max_T / min_len <= TA_CUT_MAX_BLOCKS, cut_penalty finite and >= 0.
+ *
+ * ta_wave_cut_cost_f32: cost [R, ld] f32, for p = 0 .. T of every recording
+ *   pw[p]   = (1 / 400) sum_{i = -200}^{199} x[160 p + i]^2                 samples outside [0, n) count as 0
+ *   s[p]    = (1 / (2 h + 1)) sum_{q = p - h}^{p + h} pw[q]                 positions outside [0, T] count as 0; the divisor is fixed
+ *   cost[p] = s[p] + cut_penalty * (1 / n) sum x^2
+ * in f32, every term non-negative, in the fixed order written beside the kernels: no atomics, no workgroup waits for another, two runs
+ * give the same bits, zeros cost exactly 0.  |cost - exact| <= gamma_K cost with K = TA_CUT_COST_K(h), gamma_K = K u / (1 - K u),
+ * u = 2^-24: K is the longest chain of additions + 3, which is 2 h + 25 through s[p] and 65 through the mean power at the cap
+ * (a blocked reduction: 128 positions per workgroup, then one workgroup per recording).
+ * ws: ta_wave_cut_cost_workspace_bytes(R, max_n) bytes, no initial contents required (0 for arguments that would be refused).
+ *
+ * ta_cut_plan_f32: the cheapest set of cuts with every window between min_len and max_len positions, one workgroup per recording:
+ *   dp[0] = 0;  dp[p] = (p < T ? cost[p] : 0) + min{dp[s] : max(0, p - max_len) <= s <= p - min_len}    for p = 1 .. T, one f32 add
+ *   back[p] = the LOWEST s that attains the minimum; dp[p] = +inf and back[p] = -1 where the range is empty (back[0] = -1)
+ * back int32 [R, ld] is written for p = 0 .. T.  cuts int32 [R, ldc] receives cuts[0] = 0 < ... < cuts[n_seg] = T, the walk of back[]
+ * from T; n_seg int32 [R]; dp_T f32 [R] = dp[T].  ldc >= max_T / min_len + 2.  T < min_len: the single window {0, T}, n_seg = 1,
+ * dp_T = 0 (back[] still holds the recurrence's -1).  With 2 min_len <= max_len a plan exists for every T >= min_len; n_seg = -1 is
+ * left only where the walk breaks (non-finite costs).  The workgroup runs ceil(T / min_len) blocks of min_len positions one after the
+ * other, two barriers each (13 ns per position at min_len = 1000; a small min_len makes a long recording one long kernel, hence
+ * TA_CUT_MAX_BLOCKS: at the cap of positions min_len must be at least 8).
+ *
+ * ta_wave_windows_f32: out f32 [W, Ls] row w = wav[start[w] .. start[w] + len[w]) then zeros, lens long [W] = len[w] clamped to
+ * [0, Ls]: the input contract of ta_logmel_f32.  start long [W] indexes the flat buffer of `total` samples, len int32 [W]; samples
+ * outside [0, total) are never read (they come out as 0).  16-byte stores when Ls is a multiple of 4 and out is 16-byte aligned;
+ * 16-byte loads where a source quad is aligned, 4-byte loads otherwise.  W <= TA_WAVE_WINDOWS_MAX. */
+#define TA_CUT_HOP 160
+#define TA_CUT_POWER_WINDOW 400
+#define TA_CUT_MAX_POSITIONS 1048576
+#define TA_CUT_MAX_LEN 3000
+#define TA_CUT_MAX_SMOOTH 64
+#define TA_CUT_MAX_RECORDINGS 64
+#define TA_CUT_MAX_BLOCKS 131072
+#define TA_CUT_COST_K(h) (2 * (h) + 25 > 65 ? 2 * (h) + 25 : 65)
+#define TA_WAVE_WINDOWS_MAX 65535
+long ta_wave_cut_cost_workspace_bytes(int R, long max_n);
+int ta_wave_cut_cost_f32(const float* wav, const long* offsets, int R, long max_n, int h, float cut_penalty, float* cost, long ld,
+                         void* ws, long ws_bytes, hipStream_t st);
+int ta_cut_plan_f32(const float* cost, long ld, const long* offsets, int R, long max_n, int min_len, int max_len, int* back, int* cuts,
+                    long ldc, int* n_seg, float* dp_T, hipStream_t st);
+int ta_wave_windows_f32(const float* wav, long total, const long* start, const int* len, int W, int Ls, float* out, long* lens,
+                        hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -784,6 +784,36 @@ class ASRModel(nn.Module):
         finally:
             self.train(was_training)
 
+    @torch.no_grad()
+    def transcribe_long(self, audio, sample_rate: int = 16000, *, max_window_s: float = 28.0, min_window_s: float = 10.0,
+                        batch_size: int = 32, return_timestamps: bool = False, acoustic_model=None,
+                        system_prompt: Optional[str] = None, **generate_kwargs):
+        """A whole 16 kHz recording -> ``{"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}`` (``audio``: a 1-D array or
+        tensor; a list of them returns a list of results).  The reference keeps a long recording's first chunk only
+        (tiny_audio/asr_pipeline.py:243-245); this transcribes all of it, up to 2.9 h per recording (``tiny_audio_amd/longform.py``).
+
+        The recordings are uploaded once.  On the device every 10 ms position is priced as a cut (smoothed short-time power) and the
+        cheapest cuts that keep every window within ``min_window_s`` .. ``max_window_s`` are chosen: cuts fall into pauses and never
+        beyond the encoder's window (``longform.plan_windows`` returns the plan alone).  The windows are ordered by length, longest
+        first (ties in time order), grouped ``batch_size`` at a time, gathered on the device into the feature extractor's padded batch
+        and decoded by ``generate``; every window gets its OWN chat prompt with its own ``<audio>`` placeholder count, left-padded
+        (with ``input_ids=None`` ``generate`` would build one prompt from the batch maximum).  Every ``generate`` keyword passes
+        through (decoding options, ``repetition_penalty``, sampling, ``max_new_tokens``).  Tokens become text through
+        ``eval_text.postprocess_tokens``; ``chunks`` are in time order and ``text`` joins the non-empty ones with one space.
+
+        ``return_timestamps=True`` adds ``"words"`` [{'word', 'start', 'end'}]: ``ForcedAligner.align_audio_batch`` with
+        ``acoustic_model`` (a ``wav2vec2.Wav2Vec2CtcMI355X``, required) on the same windows in the same groups, shifted by each
+        window's start; a window shorter than one acoustic frame (400 samples) or with no text has no words."""
+        from .longform import transcribe_long
+        was_training = self.training
+        self.eval()
+        try:
+            return transcribe_long(self, audio, sample_rate, max_window_s=max_window_s, min_window_s=min_window_s, batch_size=batch_size,
+                                   return_timestamps=return_timestamps, acoustic_model=acoustic_model, system_prompt=system_prompt,
+                                   **generate_kwargs)
+        finally:
+            self.train(was_training)
+
     def generate_streaming(self, input_features: torch.Tensor, audio_attention_mask: torch.Tensor,
                            system_prompt: Optional[str] = None, input_ids: Optional[torch.Tensor] = None,
                            return_token_ids: bool = False, return_token_scores: bool = False, **generate_kwargs) -> Iterator:

@@ -697,6 +697,107 @@ def ctc_align_long(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames,
     return frames, score, status, trellis
 
 
+# ----------------------------------------------------------------------------- long-form segmentation (csrc/segment.hip)
+SEGMENT_LIMITS = {"recordings": 64, "positions": 1048576, "max_len": 3000, "smooth": 64, "windows": 65535, "blocks": 131072}     # TA_CUT_* of include/ta355.h
+CUT_HOP = 160
+
+
+def cut_cost_K(smooth_positions: int) -> int:
+    """TA_CUT_COST_K(h): the kernel's longest chain of additions + 3 (its error bound is gamma_K * cost)."""
+    return max(2 * int(smooth_positions) + 25, 65)
+
+
+def _segment_batch(wav, offsets, max_samples, what):
+    if not (wav.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error(f"{what} needs the recordings on a HIP device: there is no CPU path")
+    assert wav.dim() == 1 and wav.dtype == F32 and wav.is_contiguous(), "wav: one flat contiguous f32 buffer"
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.is_contiguous() and offsets.device == wav.device
+    R, max_samples = offsets.numel() - 1, int(max_samples)
+    if R < 0 or R > SEGMENT_LIMITS["recordings"]:
+        raise ValueError(f"{what}: {R} recordings, the kernels take at most {SEGMENT_LIMITS['recordings']} per call")
+    if max_samples < 1:
+        raise ValueError(f"{what}: max_samples must be at least 1")
+    max_T = -(-max_samples // CUT_HOP)
+    if max_T > SEGMENT_LIMITS["positions"]:
+        raise ValueError(f"{what}: {max_samples} samples are {max_T} positions, beyond the kernel's limit of "
+                         f"{SEGMENT_LIMITS['positions']} ({SEGMENT_LIMITS['positions'] * CUT_HOP / 16000 / 3600:.1f} h at 16 kHz)")
+    return R, max_samples, max_T
+
+
+def wave_cut_cost(wav, offsets, max_samples, smooth_positions=10, cut_penalty=0.05):
+    """ta_wave_cut_cost_f32: ``wav`` flat f32 (device), ``offsets`` int64 [R + 1] (device; recording r is wav[offsets[r]:offsets[r + 1]]),
+    ``max_samples`` >= every recording's length (known on the host: it sizes the rows) -> cost f32 [R, max_T + 1], row r filled for the
+    positions 0 .. T_r = ceil(n_r / 160); the rest of a row, and the row of a recording longer than ``max_samples``, keeps its NaN."""
+    R, max_samples, max_T = _segment_batch(wav, offsets, max_samples, "wave_cut_cost")
+    h = int(smooth_positions)
+    if not 0 <= h <= SEGMENT_LIMITS["smooth"]:
+        raise ValueError(f"wave_cut_cost: smooth_positions must be within [0, {SEGMENT_LIMITS['smooth']}]; got {smooth_positions}")
+    cut_penalty = float(cut_penalty)
+    if not (0.0 <= cut_penalty < float("inf")):
+        raise ValueError(f"wave_cut_cost: cut_penalty must be finite and >= 0; got {cut_penalty}")
+    cost = torch.full((R, max_T + 1), float("nan"), device=wav.device, dtype=F32)
+    if R == 0:
+        return cost
+    L = lib()
+    ws_bytes = L.ta_wave_cut_cost_workspace_bytes(R, max_samples)
+    ws = torch.empty(max(ws_bytes, 8), device=wav.device, dtype=torch.uint8)
+    check(L.ta_wave_cut_cost_f32(ptr(wav), ptr(offsets), R, max_samples, h, cut_penalty, ptr(cost), max_T + 1, ptr(ws), ws_bytes, stream()),
+          "ta_wave_cut_cost_f32")
+    return cost
+
+
+def cut_plan(cost, offsets, max_samples, min_len, max_len):
+    """ta_cut_plan_f32 on ``wave_cut_cost``'s rows: windows of ``min_len`` .. ``max_len`` positions at the least total cost ->
+    (cuts int32 [R, max_T // min_len + 2], n_seg int32 [R], dp_T f32 [R], back int32 [R, max_T + 1]); recording r is cut at the
+    positions cuts[r, 0] = 0 < ... < cuts[r, n_seg[r]] = T_r.  Entries the kernel does not write hold -1."""
+    assert cost.dim() == 2 and cost.dtype == F32 and cost.is_contiguous()
+    flat = torch.empty(0, device=cost.device, dtype=F32)
+    R, max_samples, max_T = _segment_batch(flat, offsets, max_samples, "cut_plan")
+    min_len, max_len = int(min_len), int(max_len)
+    if min_len < 1 or 2 * min_len > max_len or max_len > SEGMENT_LIMITS["max_len"]:
+        raise ValueError(f"cut_plan: 1 <= min_len, 2 * min_len <= max_len <= {SEGMENT_LIMITS['max_len']} must hold; "
+                         f"got min_len={min_len}, max_len={max_len}")
+    if cost.shape[0] != R or cost.shape[1] < max_T + 1:
+        raise ValueError(f"cut_plan: cost is {tuple(cost.shape)}, {R} recordings of up to {max_T + 1} positions need [{R}, >= {max_T + 1}]")
+    if max_T // min_len > SEGMENT_LIMITS["blocks"]:
+        raise ValueError(f"cut_plan: {max_T} positions in blocks of min_len={min_len} are more than {SEGMENT_LIMITS['blocks']} sequential "
+                         "steps of one workgroup: raise min_len")
+    dev, i32 = cost.device, torch.int32
+    ldc = max_T // min_len + 2
+    back = torch.full((R, cost.shape[1]), -1, device=dev, dtype=i32)
+    cuts = torch.full((R, ldc), -1, device=dev, dtype=i32)
+    n_seg = torch.full((R,), -1, device=dev, dtype=i32)
+    dp_T = torch.full((R,), float("inf"), device=dev, dtype=F32)
+    if R:
+        check(lib().ta_cut_plan_f32(ptr(cost), cost.shape[1], ptr(offsets), R, max_samples, min_len, max_len, ptr(back), ptr(cuts), ldc,
+                                    ptr(n_seg), ptr(dp_T), stream()), "ta_cut_plan_f32")
+    return cuts, n_seg, dp_T, back
+
+
+def wave_windows(wav, start, length, Ls, out=None):
+    """ta_wave_windows_f32: ``wav`` flat f32, ``start`` int64 [W] (indices into ``wav``), ``length`` int32 [W], all on the device ->
+    (out f32 [W, Ls]: window w's samples then zeros, lens int64 [W] = the lengths clamped to [0, Ls]): what ``ta_logmel_f32`` takes."""
+    if not (wav.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("wave_windows needs the recordings on a HIP device: there is no CPU path")
+    assert wav.dim() == 1 and wav.dtype == F32 and wav.is_contiguous(), "wav: one flat contiguous f32 buffer"
+    dev = wav.device
+    assert start.dtype == torch.int64 and start.dim() == 1 and start.is_contiguous() and start.device == dev
+    assert length.dtype == torch.int32 and length.shape == start.shape and length.is_contiguous() and length.device == dev
+    W, Ls = start.numel(), int(Ls)
+    if W > SEGMENT_LIMITS["windows"]:
+        raise ValueError(f"wave_windows: {W} windows, the kernel takes at most {SEGMENT_LIMITS['windows']} per call")
+    if Ls < 1:
+        raise ValueError(f"wave_windows: Ls must be at least 1; got {Ls}")
+    if out is None:
+        out = torch.empty((W, Ls), device=dev, dtype=F32)
+    assert out.dtype == F32 and out.shape == (W, Ls) and out.is_contiguous() and out.device == dev
+    lens = torch.empty(W, device=dev, dtype=torch.int64)
+    if W:
+        check(lib().ta_wave_windows_f32(ptr(wav), wav.numel(), ptr(start), ptr(length), W, Ls, ptr(out), ptr(lens), stream()),
+              "ta_wave_windows_f32")
+    return out, lens
+
+
 # ----------------------------------------------------------------------------- decoding scores (csrc/generate.hip)
 MAX_TOP_LOGPROBS = 8      # the per-lane candidate list of token_scores_kernel
 

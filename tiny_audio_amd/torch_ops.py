@@ -8,6 +8,8 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
     ta355::ctc_align_long      the same, for a whole recording against its whole transcript   tiny_audio/asr_pipeline.py:117-131
+    ta355::wave_cut_cost, cut_plan, wave_windows   long-form transcription: where to cut a recording and the cut itself; the reference
+                               keeps the first chunk only   tiny_audio/asr_pipeline.py:243-245
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
     ta355::ecapa_embeddings    SpeechBrain ECAPA-TDNN encode_batch, one call per window   tiny_audio/diarization.py:457-517
     ta355::spk_affinity        SpectralCluster.get_sim_mat / p_pruning / get_laplacian   tiny_audio/diarization.py:49-89
@@ -180,6 +182,51 @@ def _(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, 
     N = cu_frames.shape[0] - 1
     return (tokens.new_empty(tokens.shape), emission.new_empty((N,)), tokens.new_empty((N,)),
             emission.new_empty((trellis_numel if trellis_off is not None else 0,)))
+
+
+# ============================================================================ long-form segmentation
+@torch.library.custom_op("ta355::wave_cut_cost", mutates_args=())
+def wave_cut_cost(wav: Tensor, offsets: Tensor, max_samples: int, smooth_positions: int, cut_penalty: float) -> Tensor:
+    """wav flat f32, offsets i64 [R + 1] -> cost f32 [R, ceil(max_samples / 160) + 1]: the cost of cutting recording r at each of its
+    positions 0 .. T_r (smoothed short-time power + ``cut_penalty`` x its mean power; ``ops.wave_cut_cost``), NaN beyond T_r.  No
+    autograd: the waveform is data."""
+    from . import ops
+    return ops.wave_cut_cost(wav, offsets, max_samples, smooth_positions, cut_penalty)
+
+
+@wave_cut_cost.register_fake
+def _(wav, offsets, max_samples, smooth_positions, cut_penalty):
+    return wav.new_empty((offsets.shape[0] - 1, -(-max_samples // 160) + 1))
+
+
+@torch.library.custom_op("ta355::cut_plan", mutates_args=())
+def cut_plan(cost: Tensor, offsets: Tensor, max_samples: int, min_len: int, max_len: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The cheapest cuts with every window within [min_len, max_len] positions (``ops.cut_plan``) -> (cuts i32 [R, max_T // min_len + 2],
+    n_seg i32 [R], dp_T f32 [R], back i32 [R, cost.shape[1]]).  No autograd: the plan is integers."""
+    from . import ops
+    return ops.cut_plan(cost, offsets, max_samples, min_len, max_len)
+
+
+@cut_plan.register_fake
+def _(cost, offsets, max_samples, min_len, max_len):
+    R = offsets.shape[0] - 1
+    i32 = torch.int32
+    return (cost.new_empty((R, -(-max_samples // 160) // min_len + 2), dtype=i32), cost.new_empty((R,), dtype=i32), cost.new_empty((R,)),
+            cost.new_empty((R, cost.shape[1]), dtype=i32))
+
+
+@torch.library.custom_op("ta355::wave_windows", mutates_args=())
+def wave_windows(wav: Tensor, start: Tensor, length: Tensor, Ls: int) -> Tuple[Tensor, Tensor]:
+    """wav flat f32, start i64 [W], length i32 [W] -> (f32 [W, Ls]: the windows, zero padded; their lengths i64 [W]): the inputs of
+    ``logmel`` (``ops.wave_windows``)."""
+    from . import ops
+    return ops.wave_windows(wav, start, length, Ls)
+
+
+@wave_windows.register_fake
+def _(wav, start, length, Ls):
+    W = start.shape[0]
+    return wav.new_empty((W, Ls)), start.new_empty((W,))
 
 
 # ============================================================================ decoding scores
@@ -753,4 +800,4 @@ OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backwa
              "lm_forward_loss", "lm_backward", "whisper_encoder_forward", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
              "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long", "beam_logprobs", "beam_topk",
-             "beam_advance", "kv_beam_expand", "kv_beam_reorder")
+             "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows")
