@@ -968,6 +968,52 @@ int ta_ctc_align_long_f32(const float* emission, long ld, int C, const int* cu_f
                           int max_T, int max_J, int blank_id, int col_block, int frame_block, int* frames, float* score, int* status,
                           void* ws, long ws_bytes, float* trellis_out, const long* trellis_off, hipStream_t st);
 
+/* ---- text alignment on the device: word / character error counts (WER, CER) and the LCS word matching of the reference's timestamp
+ * evaluator (tiny_audio_amd/csrc/text_align.hip).  Replaces the O(n m) host loops behind jiwer.wer in the reference's evaluator
+ * (scripts/eval/evaluators/base.py:114,150) and align_words_to_reference (scripts/eval/evaluators/alignment.py:12-79).  Contract:
+ * DESIGN.md section 3, "Text alignment", defined by tests/text_align_ref.py.  N pairs in one call, ragged:
+ *   ref: int32 symbol ids, pair p owns ref[cu_ref[p] .. cu_ref[p + 1]) (n_p of them); hyp / cu_hyp the same (m_p); cu_* are
+ *   int32[N + 1].  Only equality of ids is used; any int32 value is legal.
+ * mode TA_TEXT_ALIGN_EDIT: D[0][j] = j, D[i][0] = i, D[i][j] = min(D[i-1][j-1] + (r_i != h_j), D[i-1][j] + 1, D[i][j-1] + 1); the
+ *   path from (n, m) steps diagonally if i, j > 0 and D[i][j] == D[i-1][j-1] + (r_i != h_j) (a hit if the symbols are equal, else a
+ *   substitution), else up if i > 0 and D[i][j] == D[i-1][j] + 1 (a deletion), else left (an insertion).
+ * mode TA_TEXT_ALIGN_LCS: L[i][j] = L[i-1][j-1] + 1 if r_i == h_j else max(L[i-1][j], L[i][j-1]); the path from (n, m), while
+ *   i, j > 0, records a pair and steps diagonally if r_i == h_j, else steps up if L[i-1][j] > L[i][j-1], else left.
+ * Outputs per pair (all int32; cells are int32):
+ *   status[p] = 0 ok, 2 refused: n_p or m_p negative or beyond max_n / max_m, or (want_path) decision bits that do not fit ws;
+ *               a refused pair gets dist -1 and nothing else of it is written;
+ *   dist[p]   = D[n][m], or L[n][m];
+ *   counts[p][4] = hits, substitutions, deletions, insertions (lcs: pairs, 0, n - pairs, m - pairs)            -- want_path only
+ *   map[cu_ref[p] + i] = the hypothesis index of reference position i's diagonal step, -1 if deleted / unmatched -- want_path only
+ * want_path = 0 writes status and dist only, needs no decision bits, and counts / map may be NULL.
+ * Tiling: a tile is col_block hypothesis columns (64, 128, 256 or 512) by row_block reference rows (a multiple of 64), one wave per
+ * tile.  col_block = row_block = 0 chooses: the short kernel (one workgroup per pair: fill and walk in one launch) when
+ * max_m <= TA_TEXT_ALIGN_SHORT_MAX_M, else the long kernel with the default tile.  Any non-zero value asks for the long kernel (the
+ * other one, if 0, takes its default): launch k runs every tile (cb, rb) with cb + rb == k of every pair, a tile's entering row and
+ * the column to its left reach it through the workspace from the launch before, so ceil(max_m / col_block) +
+ * ceil(max_n / row_block) - 1 tile launches on `st`, one before them (the per-pair checks) and, with want_path, one after (the walk,
+ * one wave per pair).  No kernel waits for another workgroup.  Neither the kernel nor the tile changes an output byte.
+ * ws: ta_text_align_workspace_bytes(cu_ref_host, cu_hyp_host, N, max_n, max_m, want_path, col_block, row_block) bytes (-1 for a
+ * tiling that would be refused), no initial contents required.  The two cu_* arrays are HOST copies: the decision bits are sized
+ * from the batch's actual pairs, sum over p of m_p * ceil(n_p / 64) * 16 bytes (two bits a cell; 268 MB for 32 768 x 32 768),
+ * after a fixed part of 12 bytes a pair and, for the long kernel, the carries: max_m + max_n + ceil(max_n / row_block) ints a pair.
+ * With want_path = 0 (or NULL cu_*) the fixed part is all.
+ * Limits (TA_ERR_ARG beyond them): N <= TA_TEXT_ALIGN_MAX_PAIRS, max_n and max_m <= TA_TEXT_ALIGN_MAX_LEN (the transcript size
+ * ta_ctc_align_long_f32 takes); mode and want_path 0 or 1. */
+#define TA_TEXT_ALIGN_EDIT 0
+#define TA_TEXT_ALIGN_LCS 1
+#define TA_TEXT_ALIGN_MAX_LEN 262144
+#define TA_TEXT_ALIGN_MAX_PAIRS 65536
+#define TA_TEXT_ALIGN_MAX_COL_BLOCK 512    /* 64 lanes x 8 columns in registers */
+#define TA_TEXT_ALIGN_SHORT_MAX_M 512      /* the short kernel: the hypothesis side fits one tile */
+#define TA_TEXT_ALIGN_COL_BLOCK 256        /* the default tile of the long kernel (profiles/text_align.md) */
+#define TA_TEXT_ALIGN_ROW_BLOCK 256
+long ta_text_align_workspace_bytes(const int* cu_ref_host, const int* cu_hyp_host, int N, int max_n, int max_m, int want_path,
+                                   int col_block, int row_block);
+int ta_text_align_i32(const int* ref, const int* cu_ref, const int* hyp, const int* cu_hyp, int N, int max_n, int max_m, int mode,
+                      int want_path, int col_block, int row_block, int* dist, int* counts, int* map, int* status, void* ws,
+                      long ws_bytes, hipStream_t st);
+
 /* ---- frozen wav2vec2-base CTC acoustic model: the front half of forced alignment (tiny_audio_amd/csrc/wav2vec2.hip).  Replaces the
  * torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax the reference runs through PyTorch in ForcedAligner.align
  * (tiny_audio/alignment.py:206-211).  Arithmetic of Wav2Vec2ForCTC.forward (TF:models/wav2vec2/modeling_wav2vec2.py:1667-1700; feature encoder :382-419, projection :422-434,

@@ -140,12 +140,16 @@ def _edit_distance(ref: Sequence[str], hyp: Sequence[str]) -> int:
     return prev[-1]
 
 
-def word_error_rate(references, hypotheses, normalize: Optional[Callable[[str], str]] = None) -> float:
-    """Corpus WER: sum of word edit distances / sum of reference lengths (strings or lists of strings)."""
+def word_error_rate(references, hypotheses, normalize: Optional[Callable[[str], str]] = None, device=None) -> float:
+    """Corpus WER: sum of word edit distances / sum of reference lengths (strings or lists of strings).  ``device`` (e.g. "cuda"):
+    compute the distances on that device (``text_align.error_counts``) -- the same two integers divided; None: the host loop."""
     if isinstance(references, str):
         references, hypotheses = [references], [hypotheses]
     if len(references) != len(hypotheses):
         raise ValueError("references and hypotheses differ in length")
+    if device is not None:
+        from .text_align import error_counts
+        return error_counts(references, hypotheses, unit="word", normalize=normalize, device=device)["wer"]
     norm = normalize or (lambda s: s)
     edits = total = 0
     for r, h in zip(references, hypotheses):

@@ -697,6 +697,79 @@ def ctc_align_long(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames,
     return frames, score, status, trellis
 
 
+# ----------------------------------------------------------------------------- text alignment (csrc/text_align.hip)
+TEXT_ALIGN_LIMITS = {"pairs": 65536, "length": 262144, "col_block": 512, "short_m": 512}      # TA_TEXT_ALIGN_* of include/ta355.h
+TEXT_ALIGN_EDIT, TEXT_ALIGN_LCS = 0, 1
+TEXT_ALIGN_MAX_WORKSPACE = 8 << 30
+
+
+def text_align_workspace_bytes(cu_ref_host, cu_hyp_host, max_n, max_m, want_path, col_block=0, row_block=0, pairs=None):
+    """ta_text_align_workspace_bytes from HOST copies of the cumulative lengths (int32 CPU tensors), or, with None for both and the
+    number of ``pairs``, its fixed part alone: all that a call without ``want_path`` needs."""
+    for t in (cu_ref_host, cu_hyp_host):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and not t.is_cuda)
+    N = int(pairs) if cu_ref_host is None else cu_ref_host.numel() - 1
+    return lib().ta_text_align_workspace_bytes(ptr(cu_ref_host), ptr(cu_hyp_host), N, int(max_n), int(max_m), int(bool(want_path)),
+                                               int(col_block), int(row_block))
+
+
+def text_align(ref, cu_ref, hyp, cu_hyp, max_n, max_m, mode, want_path, *, col_block=0, row_block=0, map=None, workspace=None,
+               max_workspace_bytes=TEXT_ALIGN_MAX_WORKSPACE):
+    """ta_text_align_i32: N ragged pairs of int32 symbol ids in one call.  ``ref`` int32 [sum n_p], ``hyp`` int32 [sum m_p],
+    ``cu_ref`` / ``cu_hyp`` int32 [N + 1], all on the device; ``max_n`` / ``max_m`` bound every pair.  ``mode``: 0 edit distance, 1 LCS.
+    -> (dist int32 [N], counts int32 [N, 4] = hits, substitutions, deletions, insertions, map int32 [sum n_p], status int32 [N]).
+    Without ``want_path`` only dist and status are written (counts stays zero, map is None).  ``map`` (given, or a new tensor of -1)
+    is written for accepted pairs only.  ``col_block`` / ``row_block``: the long kernel's tile, 0 = the default; both 0 lets pairs
+    whose hypotheses fit one tile run in the short kernel; no output byte depends on them.  ``workspace``: a uint8 device tensor to
+    use instead of a new one; without it a path request reads the cumulative lengths back to size the decision bits from the actual
+    pairs (one synchronisation) and is refused beyond ``max_workspace_bytes``.  A pair beyond the maxima gets status 2."""
+    if not (ref.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("text_align needs the symbols on a HIP device: there is no CPU path for the tables")
+    dev = ref.device
+    for t in (ref, cu_ref, hyp, cu_hyp):
+        assert t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == dev, "int32, flat, contiguous, one device"
+    N = cu_ref.numel() - 1
+    if N < 0 or cu_hyp.numel() != N + 1:
+        raise ValueError(f"text_align: cu_ref holds {N + 1} entries but cu_hyp {cu_hyp.numel()}")
+    max_n, max_m, col_block, row_block, want_path = int(max_n), int(max_m), int(col_block), int(row_block), bool(want_path)
+    if N > TEXT_ALIGN_LIMITS["pairs"]:
+        raise ValueError(f"text_align: {N} pairs is beyond the kernel's limit of {TEXT_ALIGN_LIMITS['pairs']}")
+    for name, v in (("reference", max_n), ("hypothesis", max_m)):
+        if not 0 <= v <= TEXT_ALIGN_LIMITS["length"]:
+            raise ValueError(f"text_align: a {name} length of {v} is outside the kernel's limit of {TEXT_ALIGN_LIMITS['length']}")
+    if ref.numel() == 0:                 # nothing to point at: a pair that claims symbols all the same is refused, not read
+        max_n = 0
+    if hyp.numel() == 0:
+        max_m = 0
+    if mode not in (TEXT_ALIGN_EDIT, TEXT_ALIGN_LCS):
+        raise ValueError(f"text_align: mode {mode} is neither 0 (edit) nor 1 (lcs)")
+    if col_block not in (0, 64, 128, 256, 512):
+        raise ValueError(f"text_align: col_block {col_block} must be 64, 128, 256 or 512 (0 = the default)")
+    if row_block < 0 or row_block % 64 or row_block > TEXT_ALIGN_LIMITS["length"]:
+        raise ValueError(f"text_align: row_block {row_block} must be a multiple of 64 (0 = the default)")
+    if want_path:
+        if map is None:
+            map = torch.full((ref.numel(),), -1, device=dev, dtype=torch.int32)
+        assert map.dtype == torch.int32 and map.is_contiguous() and map.numel() == ref.numel() and map.device == dev
+    else:
+        map = None
+    if workspace is None:
+        host = (cu_ref.cpu(), cu_hyp.cpu()) if want_path and N > 0 else (None, None)
+        ws_bytes = text_align_workspace_bytes(*host, max_n, max_m, want_path, col_block, row_block, pairs=N)
+        if want_path and ws_bytes > int(max_workspace_bytes):
+            raise ValueError(f"text_align: the paths of this batch need a workspace of {ws_bytes} bytes, beyond max_workspace_bytes = "
+                             f"{int(max_workspace_bytes)}; ask for distances only, or split the batch")
+        workspace = torch.empty(max(ws_bytes, 16), device=dev, dtype=torch.uint8)
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev
+    dist = torch.zeros(N, device=dev, dtype=torch.int32)
+    counts = torch.zeros((N, 4), device=dev, dtype=torch.int32)
+    status = torch.zeros(N, device=dev, dtype=torch.int32)
+    check(lib().ta_text_align_i32(ptr(ref), ptr(cu_ref), ptr(hyp), ptr(cu_hyp), N, max_n, max_m, int(mode), int(want_path), col_block,
+                                  row_block, ptr(dist), ptr(counts), ptr(map), ptr(status), ptr(workspace), workspace.numel(),
+                                  stream()), "ta_text_align_i32")
+    return dist, counts, map, status
+
+
 # ----------------------------------------------------------------------------- long-form segmentation (csrc/segment.hip)
 SEGMENT_LIMITS = {"recordings": 64, "positions": 1048576, "max_len": 3000, "smooth": 64, "windows": 65535, "blocks": 131072}     # TA_CUT_* of include/ta355.h
 CUT_HOP = 160

@@ -8,6 +8,8 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_augment_chain  the same seam, every member of the production chain   tiny_audio/augmentation.py:153-216
     ta355::ctc_align           ForcedAligner._get_trellis / ._backtrack   tiny_audio/alignment.py:47-152
     ta355::ctc_align_long      the same, for a whole recording against its whole transcript   tiny_audio/asr_pipeline.py:117-131
+    ta355::text_align          jiwer.wer's edit distance and align_words_to_reference's LCS table
+                               scripts/eval/evaluators/base.py:114,150, scripts/eval/evaluators/alignment.py:12-79
     ta355::wave_cut_cost, cut_plan, wave_windows   long-form transcription: where to cut a recording and the cut itself; the reference
                                keeps the first chunk only   tiny_audio/asr_pipeline.py:243-245
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
@@ -182,6 +184,29 @@ def _(emission, cu_frames, tokens, cu_tokens, blank_id, max_frames, max_tokens, 
     N = cu_frames.shape[0] - 1
     return (tokens.new_empty(tokens.shape), emission.new_empty((N,)), tokens.new_empty((N,)),
             emission.new_empty((trellis_numel if trellis_off is not None else 0,)))
+
+
+# ============================================================================ text alignment
+@torch.library.custom_op("ta355::text_align", mutates_args=("workspace",))
+def text_align(ref: Tensor, cu_ref: Tensor, hyp: Tensor, cu_hyp: Tensor, max_n: int, max_m: int, mode: int, want_path: bool,
+               col_block: int, row_block: int, workspace: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """N ragged pairs of int32 symbol ids (``ops.text_align``, csrc/text_align.hip): ref i32 [sum n_p], hyp i32 [sum m_p], cu_ref /
+    cu_hyp i32 [N + 1]; mode 0 = edit distance (WER / CER counts), 1 = LCS (the reference evaluator's word matching) ->
+    (dist i32 [N]; counts i32 [N, 4]: hits, substitutions, deletions, insertions; map i32 [sum n_p]: the hypothesis index matched to
+    every reference position, -1 for none; status i32 [N]: 0 ok, 2 refused).  Without ``want_path`` counts is zero and map is empty.
+    ``col_block`` x ``row_block``: the long kernel's tile, 0 = the default; ``workspace``: u8 scratch of
+    ``ta_text_align_workspace_bytes`` bytes whose contents do not matter (None: sized from the pairs and allocated here).  No
+    autograd: everything is integers."""
+    from . import ops
+    dist, counts, map_, status = ops.text_align(ref, cu_ref, hyp, cu_hyp, max_n, max_m, mode, want_path, col_block=col_block,
+                                                row_block=row_block, workspace=workspace)
+    return dist, counts, map_ if map_ is not None else torch.empty(0, device=ref.device, dtype=torch.int32), status
+
+
+@text_align.register_fake
+def _(ref, cu_ref, hyp, cu_hyp, max_n, max_m, mode, want_path, col_block, row_block, workspace):
+    N = cu_ref.shape[0] - 1
+    return (ref.new_empty((N,)), ref.new_empty((N, 4)), ref.new_empty(ref.shape if want_path else (0,)), ref.new_empty((N,)))
 
 
 # ============================================================================ long-form segmentation
@@ -800,4 +825,4 @@ OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backwa
              "lm_forward_loss", "lm_backward", "whisper_encoder_forward", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
              "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long", "beam_logprobs", "beam_topk",
-             "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows")
+             "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows", "text_align")
