@@ -448,6 +448,46 @@ int ta_greedy_advance(const long* amax, const long* eos_ids, int n_eos, long pad
 int ta_token_scores_f32(const float* logits, long ld, int V, int B, const long* chosen, const int* finished, const int* step_dev,
                         int max_new, int top_k, float* logprob, float* entropy, long* top_ids, float* top_logprobs, hipStream_t st);
 
+/* ---- candidate scoring (csrc/attention_extend.hip, api.hip): log-probability of GIVEN texts under the model, the clips' prompt cache
+ * shared by their candidates.  For clip b with prompt P_b and candidate c = (c_0 .. c_{n-1}), n >= 1:
+ *     lp_t = log_softmax(z(P_b, c_<t))[c_t] over the V true columns, in f32;   score = sum_t lp_t in the order t = 0 .. n-1
+ * i.e. minus HF's summed cross-entropy over those label positions (the `labels` path of tiny_audio/asr_modeling.py:481-533 ->
+ * TF:loss/loss_utils.py ForCausalLMLoss), which re-encodes the prompt per text and returns one batch mean; and what closed-set
+ * evaluation otherwise approximates by generating free text and string-matching the choices (scripts/eval/evaluators/mcq.py:89-132).
+ *
+ * ta_attention_extend: causal GQA attention (head_dim 128) of R rows x T given positions appended to a cache -- the pass between the
+ * prompt pass ("q rows = k rows, no cache") and the decode step ("one q row against the cache"); it takes the place of the attention of
+ * TF:models/qwen3/modeling_qwen3.py:185-208 when past_key_values holds the prompt and T new tokens arrive at once.  Query t of row r
+ * sees (1) the prompt slots s < Lp of clip clip_of[r] with pmask[clip_of[r], s] != 0 (pmask int [B, Lp]), read in place from ONE
+ * layer of the cache Kc / Vc bf16 [B, Hkv, Lmax, 128] -- never copied per row -- and (2) the row's own slots j <= t, j < len[r], of
+ * Kn / Vn bf16 [R, Hkv, T, 128].  Q bf16 [R, Hq, T, 128]: Q / Kn / Vn are what ta_lm_qkv_post_fwd writes for B = R, L = T.  O bf16
+ * [R*T, Hq*128] token-major like ta_attention_fwd's; LSE f32 [R, Hq, T] or NULL.  Query rows t >= len[r], and queries without any
+ * visible key, get O exactly 0 (LSE 1e30).  Masked slots must hold finite values and contribute exactly nothing.  No workspace.
+ * TA_ERR_ARG before any launch unless 1 <= T <= TA_EXTEND_MAX_T, 1 <= R <= TA_EXTEND_MAX_R, Hq / Hkv in {1, 2, 4}, 1 <= Lp <= Lmax,
+ * B >= 1 and every pointer but LSE non-NULL. */
+#define TA_EXTEND_MAX_T 256
+#define TA_EXTEND_MAX_R 1024
+int ta_attention_extend(const void* Q, const void* Kn, const void* Vn, const void* Kc, const void* Vc, const int* pmask,
+                        const int* clip_of, const int* len, void* O, float* LSE, int B, int R, int Hq, int Hkv, int T, int Lp,
+                        int Lmax, float scale, hipStream_t st);
+/* ta_lm_score: the scores of R candidates of B clips after ONE ta_lm_prefill of those clips made with Lmax = L = Lp, whose kcache /
+ * vcache [n_layers, B, kv_heads, Lp, 128], kmask (here pmask [B, Lp]), logits [B, vocab_pad] and lora_img it takes unchanged.
+ * ids i64 [R, T] (entries behind a row's end are ignored), len int [R] on the device and the same values in len_host (host memory:
+ * the number of label rows sizes the launches), clip_of int [R], pos0 int [B] = RoPE position of a clip's first new token (its number
+ * of valid prompt tokens; token t sits at pos0 + t, where the decode step would place it).  The decoder layers run over the R*T rows
+ * as in the prompt pass, with ta_attention_extend for the attention; token 0 is read off the prefill's logits (log-sum-exp once per
+ * clip), tokens 1 .. n-1 go through the final norm, the head (f32 logits) and ta_cross_entropy in chunks of TA_SCORE_CE_ROWS label
+ * rows.  Raw logits: no processor, no temperature.  token_logprobs f32 [R, T] (exact 0 at t >= len[r]); score f32 [R] = the row's sum
+ * in index order (no atomics: the same bits on every run).  TA_ERR_ARG before any HIP call: a NULL among the above (lora_img only
+ * with adapters), R / T beyond ta_attention_extend's limits, R*T > TA_SCORE_MAX_ROWS, B < 1, Lp < 1, Lp + T > max_pos, a len_host
+ * entry outside [1, T], a model outside ta_lm_prefill's envelope, or ws_bytes < ta_lm_score_workspace_bytes(w, B, R, T). */
+#define TA_SCORE_MAX_ROWS 65536
+#define TA_SCORE_CE_ROWS 256
+long ta_lm_score_workspace_bytes(const ta_lm_weights* w, int B, int R, int T);
+int ta_lm_score(const ta_lm_weights* w, const long* ids, const int* len, const int* len_host, const int* clip_of, const int* pos0,
+                int B, int R, int T, const void* kcache, const void* vcache, int Lp, const int* pmask, const float* logits,
+                const void* lora_img, float* token_logprobs, float* score, void* ws, long ws_bytes, hipStream_t st);
+
 /* ---- beam search (csrc/beam.hip): HF GenerationMixin._beam_search (TF:generation/utils.py) for do_sample=False, around the unchanged
  * ta_lm_prefill / ta_lm_decode_step.  Beams are rows: R = B * K rows, row = b * K + k; 1 <= K <= 8 beams, n_eos <= 3 eos ids,
  * M = max(2, 1 + n_eos) * K <= 32 candidates per clip and step (anything else: TA_ERR_ARG, nothing launched).  A step is

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(HERE)
 HEADER = os.path.join(ROOT, "include", "ta355.h")
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "libta355.so")
-SOURCES = ["gemm.hip", "gemm_tn.hip", "norm.hip", "attention.hip", "attention_enc.hip", "qkv_post.hip", "elementwise.hip", "loss.hip",
+SOURCES = ["gemm.hip", "gemm_tn.hip", "norm.hip", "attention.hip", "attention_extend.hip", "attention_enc.hip", "qkv_post.hip", "elementwise.hip", "loss.hip",
            "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "beam.hip", "decode_fused.hip", "augment.hip", "align.hip", "align_long.hip", "text_align.hip", "wav2vec2.hip", "ecapa.hip", "cluster.hip", "segment.hip", "api.hip"]
 
 

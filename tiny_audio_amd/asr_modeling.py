@@ -112,6 +112,54 @@ class GenerationOutput(dict):
         return (GenerationOutput, tuple(dict.get(self, k) for k in self._items))
 
 
+class ScoreOutput(dict):
+    """What ``ASRModel.score`` returns; a dict in the style of ``GenerationOutput`` (the fields that are not None, in order, with
+    attribute, key, index and slice access): ``scores`` f32 [R] (sum of the candidate's token log-probabilities), ``candidate_clip``
+    int64 [R] and ``n_tokens`` int64 [R], rows clip-major in the order the candidates were given; with ``return_token_scores`` also
+    ``token_ids`` int64 [R, T] and ``token_logprobs`` f32 [R, T] (exact 0 behind a candidate's end).  ``per_clip()`` regroups them."""
+
+    _items = ("scores", "candidate_clip", "n_tokens", "token_ids", "token_logprobs")
+
+    def __init__(self, scores=None, candidate_clip=None, n_tokens=None, token_ids=None, token_logprobs=None, n_clips=None):
+        super().__init__()
+        for k, v in zip(self._items, (scores, candidate_clip, n_tokens, token_ids, token_logprobs)):
+            if v is not None:
+                dict.__setitem__(self, k, v)
+        self.n_clips = n_clips
+
+    def __getattr__(self, k):                     # reached only when the normal lookup fails: an item, or an absent item
+        if k in ScoreOutput._items:
+            return dict.get(self, k)
+        raise AttributeError(k)
+
+    def __getitem__(self, k):
+        if isinstance(k, (int, slice)):
+            return tuple(self.values())[k]
+        return dict.__getitem__(self, k)
+
+    def to_tuple(self):
+        return tuple(self.values())
+
+    def __reduce__(self):
+        return (ScoreOutput, tuple(dict.get(self, k) for k in self._items) + (self.n_clips,))
+
+    def per_clip(self):
+        """One list per clip, in the order given: a dict(score, n_tokens[, token_ids, token_logprobs cut to the candidate's length])
+        per candidate; an empty list for a clip without candidates."""
+        clip = self["candidate_clip"].tolist()
+        n = self["n_tokens"].tolist()
+        s = self["scores"].detach().cpu().tolist()
+        B = self.n_clips if self.n_clips is not None else (max(clip) + 1 if clip else 0)
+        out = [[] for _ in range(B)]
+        for r, b in enumerate(clip):
+            item = dict(score=s[r], n_tokens=n[r])
+            if "token_logprobs" in self:
+                item["token_ids"] = self["token_ids"][r, :n[r]].tolist()
+                item["token_logprobs"] = self["token_logprobs"][r, :n[r]].detach().cpu().tolist()
+            out[b].append(item)
+        return out
+
+
 def _is_cjk(ch: str) -> bool:
     """CJK ideograph blocks (a streamer releases such characters one by one: they carry no spaces)."""
     cp = ord(ch)
@@ -783,6 +831,43 @@ class ASRModel(nn.Module):
             return (res, out[2]) if return_beam_trace else res
         finally:
             self.train(was_training)
+
+    @torch.no_grad()
+    def score(self, input_features: Optional[torch.Tensor] = None, audio_attention_mask: Optional[torch.Tensor] = None, candidates=None, *,
+              input_ids: Optional[torch.Tensor] = None, attention_mask: Optional[torch.Tensor] = None,
+              system_prompt: Optional[str] = None, append_eos: bool = True, return_token_scores: bool = False):
+        """How probable is each given text under the model, given the audio: for clip b and candidate c = (c_0 .. c_{n-1}) the sum over
+        t of log_softmax(z(P_b, c_<t))[c_t] -- minus the summed cross-entropy the reference's ``forward(labels=...)`` computes for those
+        label positions (tiny_audio/asr_modeling.py:481-533), with P_b exactly the prompt ``generate`` builds (system prompt, user turn
+        with the audio placeholders, assistant header) and raw logits (no processor, no temperature).  The audio and the prompt are
+        encoded once per clip; the candidates of a clip share its KV cache.
+
+        ``candidates``: one list per clip; an entry is a ``str`` (tokenised with ``add_special_tokens=False``) or a list of token ids;
+        the lists are ragged and a clip may have none.  ``append_eos`` appends ``config.eos_token_id`` (``<|im_end|>``: what training
+        labels end with).  ValueError: a candidate empty after tokenisation, ids outside the vocabulary, prompt + candidate beyond
+        ``max_position_embeddings``.  -> ``ScoreOutput``."""
+        from . import scoring
+        if candidates is None:
+            raise ValueError("candidates required: one list of texts or token-id lists per clip")
+        B = int(input_features.shape[0]) if input_features is not None else len(candidates)
+        if len(candidates) != B:
+            raise ValueError(f"{len(candidates)} candidate lists for {B} clips")
+        V = int(self.language_model.config.vocab_size)
+        tab = scoring.build_candidate_table(candidates, self.tokenizer, self.config.eos_token_id, append_eos, vocab_size=V)
+        was_training = self.training
+        self.eval()
+        try:
+            args = self._prepare_generation(input_ids, input_features, audio_attention_mask, attention_mask, system_prompt, {})
+            L, T = args["input_ids"].shape[1], tab["token_ids"].shape[1]
+            if L + T > self.language_model.config.max_position_embeddings:
+                raise ValueError(f"prompt ({L}) + candidate tokens ({T}) exceeds max_position_embeddings")
+            lp, scores = self.language_model.score_candidates(args["input_ids"], args["src_row"], args["audio"], args["attention_mask"],
+                                                              tab["token_ids"], tab["n_tokens"], tab["candidate_clip"], tab["chunks"])
+        finally:
+            self.train(was_training)
+        return ScoreOutput(scores=scores, candidate_clip=tab["candidate_clip"], n_tokens=tab["n_tokens"],
+                           token_ids=tab["token_ids"] if return_token_scores else None,
+                           token_logprobs=lp if return_token_scores else None, n_clips=B)
 
     @torch.no_grad()
     def transcribe_long(self, audio, sample_rate: int = 16000, *, max_window_s: float = 28.0, min_window_s: float = 10.0,

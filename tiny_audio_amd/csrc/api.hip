@@ -496,10 +496,14 @@ extern "C" long ta_lm_workspace_bytes(const ta_lm_weights* w, int B, int L, int 
 // Llama: Lw.qn_w == Lw.kn_w == NULL) and with per-layer NoPE (w->nope_layers): same layer, two switches on the q / k post-processing.  Training keeps one
 // tape entry per layer; inference (`alias`) reuses entry 0 for every layer.  `ext`: adapter images held outside the
 // tape (generation keeps them across decode steps); kcache/vcache: see ta_lm_prefill.
+// `xt` (candidate scoring, ta_lm_score; NULL = off, and then nothing here changes): the B rows are candidates of L given tokens behind
+// the prompt cache of their clips -- the layer takes the un-fused ta_lm_qkv_post_fwd path and ta_attention_extend in place of the causal
+// attention; `ext` then holds the images the prompt pass packed, which are not packed again.
+struct LmExtend { const bf16_t *kc, *vc; const int *pmask, *clip_of, *len; int clips, Lp; };
 static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int L, const int* kmask, const int* pos,
                              LmLayerTape* store, bool alias, float* x_final, LmWs& s, const ta_i_lora_layer_imgs* ext,
                              bf16_t* kcache, bf16_t* vcache, int Lmax, hipStream_t st, const LoraDropDev* drop = nullptr,
-                             const int* seg = nullptr) {
+                             const int* seg = nullptr, const LmExtend* xt = nullptr) {
   const int M = (int)d.M;
   const float scale = 1.0f / sqrtf((float)d.hd);
   const bool lora = w->lora_rank > 0;
@@ -516,7 +520,7 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
     return TA_OK;
   };
   auto take_ext = [&]() { const ta_gemm_opts o = kx; kx = opts_none(); return o; };
-  if (lora) {
+  if (lora && !xt) {
     // bf16 images of every layer's adapters (kept in the tape / the caller's image buffer for backward and decoding).
     // The masters of consecutive layers are usually one tensor [L, ...] and the images are carved with a constant
     // per-layer stride: then each of the 8 image kinds is ONE launch over all layers instead of one per layer.
@@ -582,8 +586,11 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
     if (lgm & 1) RC(lora_fwd(xn, d.D, p.i_qkv, p.xa_qkv, 3, 8 * l + 0));
     RC(gemm_opt(xn, Lw.wqkv, p.qkv0, M, d.NQKV, d.D, nullptr, nullptr, 0, 1, take_ext(), st));
     // short causal sequences: QK-norm + RoPE + head split ride in the attention kernel's staging; longer ones take two kernels
-    const bool fused_fwd = lm_attn_fused(d, L);
-    if (fused_fwd && seg)                            // packed rows: the segment-aware instantiation of the same kernel
+    const bool fused_fwd = !xt && lm_attn_fused(d, L);
+    if (xt)                                          // no transposed images: the extend kernel reads V transposed out of its row tiles
+      RC(ta_lm_qkv_post_fwd(p.qkv0, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, p.q, p.k, p.v, nullptr, nullptr, nullptr,
+                            p.rq, p.rk, B, d.nq, d.nkv, L, d.Lp, w->eps, st));
+    else if (fused_fwd && seg)                           // packed rows: the segment-aware instantiation of the same kernel
       RC(ta_attention_fwd_qkv_seg(p.qkv0, Lw.qn_w, Lw.kn_w, lm_rope_cos(w, l), lm_rope_sin(w, l), pos, p.q, p.k, (kcache || w->train_base) ? p.v : nullptr, p.rq, p.rk, p.ao, p.lse, kmask,
                                   seg, B, d.nq, d.nkv, L, scale, w->eps, st));
     else if (fused_fwd)
@@ -600,7 +607,11 @@ static int lm_layers_forward(const ta_lm_weights* w, const LmDims& d, int B, int
           hipMemcpy2DAsync(vcache + (size_t)l * rows * Lmax * d.hd, pitch, p.v, row, row, rows, hipMemcpyDeviceToDevice, st) != hipSuccess)
         return TA_ERR_LAUNCH;
     }
-    if (!fused_fwd && seg) RC(ta_attention_fwd_seg(p.q, p.k, p.vt, p.ao, p.lse, kmask, seg, B, d.nq, d.nkv, L, d.Lp, scale, st));
+    if (xt) {
+      const size_t layer = (size_t)xt->clips * d.nkv * xt->Lp * d.hd;          // one layer of the prompt cache (Lmax = Lp)
+      RC(ta_attention_extend(p.q, p.k, p.v, xt->kc + l * layer, xt->vc + l * layer, xt->pmask, xt->clip_of, xt->len, p.ao, nullptr,
+                             xt->clips, B, d.nq, d.nkv, L, xt->Lp, xt->Lp, scale, st));
+    } else if (!fused_fwd && seg) RC(ta_attention_fwd_seg(p.q, p.k, p.vt, p.ao, p.lse, kmask, seg, B, d.nq, d.nkv, L, d.Lp, scale, st));
     else if (!fused_fwd) RC(ta_attention_fwd(p.q, p.k, p.vt, p.ao, p.lse, kmask, B, d.nq, d.nkv, L, d.Lp, d.hd, 1, scale, st));
     if (lgm & 2) RC(lora_fwd(p.ao, d.nq * d.hd, p.i_o, p.xa_o, 1, 8 * l + 3));
     RC(res_gemm(p.ao, Lw.wo, p.x1, d.nq * d.hd, p.x_in));
@@ -749,6 +760,91 @@ extern "C" int ta_lm_prefill(const ta_lm_weights* w, const long* ids, const int*
   else RC(ta_rmsnorm_fwd(p.t.x_final, w->norm_w, p.t.hn, nullptr, p.t.r_f, M, d.D, w->eps, 0, st));
   RC(ta_gather_rows_bf16(p.t.hn, last_rows, p.s.hl, B, d.D, st));
   RC(gemm(p.s.hl, w->embed_bf16, logits, B, w->vocab_pad, d.D, nullptr, nullptr, 0, 0, st));
+  return TA_OK;
+}
+
+// ---------------------------------------------------------------------------- candidate scoring (include/ta355.h ta_lm_score)
+namespace {
+// the prompt pass's carve over [R, T] rows with the head sized for one chunk of label rows, then the scoring tables
+struct ScoreWs {
+  PrefillWs p;
+  long *ids_clean, *label_targets;
+  int *pos, *off, *label_rows;
+  float *nll, *lse;
+  int chunk;
+  size_t bytes;
+};
+ScoreWs score_ws(const ta_lm_weights* w, int B, int R, int T, void* base) {
+  ScoreWs q;
+  const long rows = (long)R * T, labs = std::max((long)R * (T - 1), 1L);
+  q.chunk = (int)std::min((long)TA_SCORE_CE_ROWS, labs);            // the f32 logits buffer never exceeds TA_SCORE_CE_ROWS * vocab_pad
+  q.p.w1 = *w; q.p.w1.n_layers = 1;
+  q.p.t = lm_tape(&q.p.w1, R, T, 1, base, q.p.layer);
+  q.p.tape_bytes = q.p.t.bytes;
+  q.p.s = lm_ws(w, R, T, q.chunk, base ? (char*)base + q.p.tape_bytes : nullptr);
+  q.p.bytes = q.p.tape_bytes + q.p.s.bytes;
+  Carver c(base ? (char*)base + q.p.bytes : nullptr);
+  q.ids_clean = c.take<long>((size_t)rows);
+  q.pos = c.take<int>((size_t)rows);
+  q.off = c.take<int>((size_t)R + 1);
+  q.label_rows = c.take<int>((size_t)labs);
+  q.label_targets = c.take<long>((size_t)labs);
+  q.nll = c.take<float>((size_t)labs);
+  q.lse = c.take<float>((size_t)B);
+  q.bytes = q.p.bytes + c.total();
+  return q;
+}
+bool score_shape_ok(const ta_lm_weights* w, int B, int R, int T) {
+  return w && B >= 1 && R >= 1 && R <= TA_EXTEND_MAX_R && T >= 1 && T <= TA_EXTEND_MAX_T && (long)R * T <= TA_SCORE_MAX_ROWS &&
+         w->n_layers <= MAX_LM_LAYERS && w->n_layers >= 1;
+}
+}  // namespace
+extern "C" long ta_lm_score_workspace_bytes(const ta_lm_weights* w, int B, int R, int T) {
+  if (!score_shape_ok(w, B, R, T)) return -1;
+  return (long)score_ws(w, B, R, T, nullptr).bytes;
+}
+extern "C" int ta_lm_score(const ta_lm_weights* w, const long* ids, const int* len, const int* len_host, const int* clip_of,
+                           const int* pos0, int B, int R, int T, const void* kcache, const void* vcache, int Lp, const int* pmask,
+                           const float* logits, const void* lora_img, float* token_logprobs, float* score, void* ws, long ws_bytes,
+                           hipStream_t st) {
+  if (!score_shape_ok(w, B, R, T) || !ids || !len || !len_host || !clip_of || !pos0 || !kcache || !vcache || !pmask || !logits ||
+      !token_logprobs || !score || !ws)
+    return TA_ERR_ARG;
+  const int grp = w->kv_heads > 0 && w->heads % w->kv_heads == 0 ? w->heads / w->kv_heads : 0;
+  if (w->head_dim != 128 || w->hidden % 128 || w->ffn % 64 || w->vocab_pad % 128 || w->vocab > w->vocab_pad || w->vocab < 1 ||
+      (grp != 1 && grp != 2 && grp != 4) || Lp < 1 || (long)Lp + T > w->max_pos)
+    return TA_ERR_ARG;
+  if (w->lora_rank > 0 && !lora_img) return TA_ERR_ARG;
+  long n_lab = 0;
+  for (int r = 0; r < R; ++r) {
+    if (len_host[r] < 1 || len_host[r] > T) return TA_ERR_ARG;
+    n_lab += len_host[r] - 1;
+  }
+  ScoreWs q = score_ws(w, B, R, T, ws);
+  if ((long)q.bytes > ws_bytes) return TA_ERR_ARG;
+  const LmDims d = lm_dims(w, R, T);
+  const int M = (int)d.M;
+  ta_i_lora_layer_imgs imgs[MAX_LM_LAYERS];
+  if (w->lora_rank > 0) lora_imgs_carve(w, (void*)lora_img, imgs);
+  RC(ta_i_score_prep(ids, len, clip_of, pos0, B, R, T, Lp, w->vocab, q.ids_clean, q.pos, q.off, q.label_rows, q.label_targets, st));
+  RC(ta_i_score_lse(logits, w->vocab_pad, w->vocab, B, q.lse, st));                       // token 0: once per clip, not per candidate
+  if (n_lab > 0) {
+    float* x0 = q.p.layer[0].x_in;
+    if (lm_res_bf16(w)) RC(ta_embed_scatter(q.ids_clean, nullptr, w->embed_f32, nullptr, nullptr, x0, M, d.D, w->vocab, st));
+    else RC(ta_embed_scatter(q.ids_clean, nullptr, w->embed_f32, nullptr, x0, nullptr, M, d.D, w->vocab, st));
+    const LmExtend xt{(const bf16_t*)kcache, (const bf16_t*)vcache, pmask, clip_of, len, B, Lp};
+    RC(lm_layers_forward(w, d, R, T, nullptr, q.pos, q.p.layer, true, q.p.t.x_final, q.p.s, w->lora_rank > 0 ? imgs : nullptr, nullptr,
+                         nullptr, 0, st, nullptr, nullptr, &xt));
+    if (lm_res_bf16(w)) RC(ta_rmsnorm_fwd_bf16(q.p.t.x_final, w->norm_w, q.p.t.hn, nullptr, q.p.t.r_f, M, d.D, w->eps, st));
+    else RC(ta_rmsnorm_fwd(q.p.t.x_final, w->norm_w, q.p.t.hn, nullptr, q.p.t.r_f, M, d.D, w->eps, 0, st));
+    for (long c0 = 0; c0 < n_lab; c0 += q.chunk) {                                        // rows (r, t) with t + 1 < len[r] only
+      const int n = (int)std::min((long)q.chunk, n_lab - c0);
+      RC(ta_gather_rows_bf16(q.p.t.hn, q.label_rows + c0, q.p.s.hl, n, d.D, st));
+      RC(gemm(q.p.s.hl, w->embed_bf16, q.p.s.logits, n, w->vocab_pad, d.D, nullptr, nullptr, 0, 0, st));
+      RC(ta_cross_entropy(q.p.s.logits, 0, w->vocab_pad, nullptr, q.label_targets + c0, n, w->vocab, 1.0f, q.nll + c0, nullptr, nullptr, 0, st));
+    }
+  }
+  RC(ta_i_score_finish(logits, w->vocab_pad, q.lse, q.ids_clean, len, clip_of, q.off, q.nll, B, R, T, token_logprobs, score, st));
   return TA_OK;
 }
 

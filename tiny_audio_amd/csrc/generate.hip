@@ -1110,3 +1110,106 @@ extern "C" int ta_greedy_advance(const long* amax, const long* eos_ids, int n_eo
   TA_CHECK_LAUNCH();
   return TA_OK;
 }
+
+// ---------------------------------------------------------------------------- candidate scoring: the row-local pieces of ta_lm_score (api.hip)
+// off[r] = number of label rows (positions t with t + 1 < len) of the rows before r, off[R] = their total; R <= 1024, one workgroup
+__global__ __launch_bounds__(256) void score_offsets_kernel(const int* __restrict__ len, int R, int T, int* __restrict__ off) {
+  __shared__ int part[257];
+  const int tid = threadIdx.x, per = (R + 255) / 256, r0 = tid * per;
+  int s = 0;
+  for (int r = r0; r < min(r0 + per, R); ++r) s += max(min(len[r], T) - 1, 0);
+  part[tid + 1] = s;
+  __syncthreads();
+  if (tid == 0) { part[0] = 0; for (int i = 1; i <= 256; ++i) part[i] += part[i - 1]; }
+  __syncthreads();
+  s = part[tid];
+  for (int r = r0; r < min(r0 + per, R); ++r) { off[r] = s; s += max(min(len[r], T) - 1, 0); }
+  if (tid == 255) off[R] = part[256];
+}
+// per (row, position): the id the embedding reads (0 behind the row's end, so nothing there depends on the caller's padding), its RoPE
+// position, and for positions with a successor the label row / target of the cross-entropy
+__global__ __launch_bounds__(256) void score_prep_kernel(const long* __restrict__ ids, const int* __restrict__ len,
+                                                         const int* __restrict__ clip_of, const int* __restrict__ pos0,
+                                                         const int* __restrict__ off, int B, int R, int T, int Lp, long vocab,
+                                                         long* __restrict__ ids_clean, int* __restrict__ pos,
+                                                         int* __restrict__ label_rows, long* __restrict__ label_targets) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= R * T) return;
+  const int r = i / T, t = i % T, n = min(max(len[r], 0), T);
+  const int clip = min(max(clip_of[r], 0), B - 1);
+  const long id = t < n ? ids[i] : 0;
+  ids_clean[i] = (id >= 0 && id < vocab) ? id : 0;
+  pos[i] = min(max(pos0[clip], 0), Lp) + t;
+  if (t + 1 < n) {
+    const int k = off[r] + t;
+    const long nx = ids[i + 1];
+    label_rows[k] = i;
+    label_targets[k] = (nx >= 0 && nx < vocab) ? nx : -1;
+  }
+}
+// log-sum-exp of the prefill's last-row logits, once per clip
+__global__ __launch_bounds__(1024) void score_lse_kernel(const float* __restrict__ logits, long ld, int V, float* __restrict__ lse) {
+  __shared__ float red[16];
+  const float* row = logits + (long)blockIdx.x * ld;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float m = -INFINITY;
+  for (int j = tid; j < V; j += 1024) m = fmaxf(m, row[j]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = red[0];
+  for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
+  __syncthreads();
+  float s = 0.f;
+  for (int j = tid; j < V; j += 1024) s += __expf(row[j] - m);
+  s = wave_sum(s);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    s = 0.f;
+    for (int i = 0; i < 16; ++i) s += red[i];
+    lse[blockIdx.x] = m + logf(s);
+  }
+}
+// one thread per row: lp[r, 0] = z[clip, c_0] - lse[clip], lp[r, t] = -nll of label row (r, t - 1), exact 0 behind the end; the score is
+// their sum in index order
+__global__ __launch_bounds__(64) void score_finish_kernel(const float* __restrict__ logits, long ld, const float* __restrict__ lse,
+                                                          const long* __restrict__ ids_clean, const int* __restrict__ len,
+                                                          const int* __restrict__ clip_of, const int* __restrict__ off,
+                                                          const float* __restrict__ nll, int B, int R, int T,
+                                                          float* __restrict__ token_logprobs, float* __restrict__ score) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= R) return;
+  const int n = min(max(len[r], 0), T), clip = min(max(clip_of[r], 0), B - 1);
+  float* lp = token_logprobs + (long)r * T;
+  float s = 0.f;
+  for (int t = 0; t < T; ++t) {
+    float v = 0.f;
+    if (t == 0 && n > 0) v = logits[(long)clip * ld + ids_clean[(long)r * T]] - lse[clip];
+    else if (t < n) v = -nll[off[r] + t - 1];
+    lp[t] = v;
+    s += v;
+  }
+  score[r] = s;
+}
+int ta_i_score_prep(const long* ids, const int* len, const int* clip_of, const int* pos0, int B, int R, int T, int Lp, long vocab,
+                    long* ids_clean, int* pos, int* off, int* label_rows, long* label_targets, hipStream_t st) {
+  TA_LAUNCH(score_offsets_kernel, dim3(1), dim3(256), 0, st, len, R, T, off);
+  TA_CHECK_LAUNCH();
+  TA_LAUNCH(score_prep_kernel, dim3(ta_cdiv((long)R * T, 256)), dim3(256), 0, st, ids, len, clip_of, pos0, off, B, R, T, Lp, vocab,
+            ids_clean, pos, label_rows, label_targets);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+int ta_i_score_lse(const float* logits, long ld, int V, int B, float* lse, hipStream_t st) {
+  TA_LAUNCH(score_lse_kernel, dim3(B), dim3(1024), 0, st, logits, ld, V, lse);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}
+int ta_i_score_finish(const float* logits, long ld, const float* lse, const long* ids_clean, const int* len, const int* clip_of,
+                      const int* off, const float* nll, int B, int R, int T, float* token_logprobs, float* score, hipStream_t st) {
+  TA_LAUNCH(score_finish_kernel, dim3(ta_cdiv(R, 64)), dim3(64), 0, st, logits, ld, lse, ids_clean, len, clip_of, off, nll, B, R, T,
+            token_logprobs, score);
+  TA_CHECK_LAUNCH();
+  return TA_OK;
+}

@@ -58,6 +58,16 @@ int ta_i_dec_attn(const void* qkv0, const float* qn_w, const float* kn_w, const 
 int ta_i_dec_embed(const long* ids, const float* emb, float* xblk, int B, int D, long vocab, hipStream_t st);
 int ta_i_dec_final_norm(const float* xblk, const float* w, void* y, int B, int D, float eps, hipStream_t st);
 
+// candidate scoring (api.hip ta_lm_score; kernels in generate.hip).  prep: off int [R + 1] = label rows before each row, the ids the
+// embedding reads (0 behind a row's end), RoPE positions, and the label rows / targets (row (r, t) with t + 1 < len[r] -> target
+// ids[r, t + 1]); lse: log-sum-exp over V columns of B logits rows; finish: token_logprobs [R, T] and score [R] from the prefill's
+// logits (token 0) and the cross-entropy's nll (tokens 1 ..)
+int ta_i_score_prep(const long* ids, const int* len, const int* clip_of, const int* pos0, int B, int R, int T, int Lp, long vocab,
+                    long* ids_clean, int* pos, int* off, int* label_rows, long* label_targets, hipStream_t st);
+int ta_i_score_lse(const float* logits, long ld, int V, int B, float* lse, hipStream_t st);
+int ta_i_score_finish(const float* logits, long ld, const float* lse, const long* ids_clean, const int* len, const int* clip_of,
+                      const int* off, const float* nll, int B, int R, int T, float* token_logprobs, float* score, hipStream_t st);
+
 // ragged encoder (api.hip enc_forward_ragged; kernels in elementwise.hip).  The two stem kernels take the clips' mel lengths from
 // the HOST array, RAGGED_CHUNK of them per launch as a by-value kernel argument; the others read the device table cu [B + 1].
 constexpr int RAGGED_CHUNK = 128;

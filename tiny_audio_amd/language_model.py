@@ -626,6 +626,75 @@ class Qwen3MI355X(torch.nn.Module):
             pass
         return out
 
+    # ------------------------------------------------------------------ candidate scoring (include/ta355.h ta_lm_score)
+    @torch.no_grad()
+    def score_candidates(self, input_ids, src_row, audio, attention_mask, token_ids, n_tokens, candidate_clip, chunks=None):
+        """Log-probability of given continuations of the prompts: the prompt pass runs ONCE over the B clips (as in ``greedy_decode``),
+        then ``ta_lm_score`` appends every candidate's tokens to the cache of its clip.  ``token_ids`` int64 [R, T] (entries behind a
+        row's end are ignored), ``n_tokens`` [R] (each within [1, T]), ``candidate_clip`` [R] (within [0, B)): the table of
+        ``scoring.build_candidate_table``; ``chunks``: its row ranges (default: ``scoring.chunk_rows`` under the C limits), one
+        ``ta_lm_score`` call each.  -> (token_logprobs f32 [R, T], exact 0 behind a row's end; scores f32 [R]) on the device.  Raw logits:
+        no processor, no temperature; candidate token t sits at RoPE position (valid prompt tokens of its clip) + t."""
+        from . import scoring
+        if self._w is None:
+            raise _lib.Ta355Error("LM weights not loaded")
+        L_ = _lib.lib()
+        c, dev = self.config, self.device_
+        B, L = input_ids.shape
+        i32, i64 = torch.int32, torch.int64
+        token_ids = torch.as_tensor(token_ids, dtype=i64)
+        n_host = [int(v) for v in torch.as_tensor(n_tokens).tolist()]
+        clip_host = [int(v) for v in torch.as_tensor(candidate_clip).tolist()]
+        R, T = token_ids.shape
+        if len(n_host) != R or len(clip_host) != R:
+            raise ValueError(f"n_tokens / candidate_clip must have one entry per row of token_ids ({R})")
+        if any(not 1 <= n <= T for n in n_host) or any(not 0 <= b < B for b in clip_host):
+            raise ValueError("n_tokens must lie within [1, T] and candidate_clip within [0, B)")
+        if L + T > c.max_position_embeddings:
+            raise ValueError(f"prompt ({L}) + candidate tokens ({T}) exceeds max_position_embeddings")
+        token_lp = torch.zeros((R, T), dtype=F32, device=dev)
+        scores = torch.zeros(R, dtype=F32, device=dev)
+        if R == 0:
+            return token_lp, scores
+        if chunks is None:
+            chunks = scoring.chunk_rows(n_host, *scoring.limits())
+        att = torch.ones((B, L), dtype=i32, device=dev) if attention_mask is None else attention_mask.to(device=dev, dtype=i32).contiguous()
+        pos_full = (att.cumsum(-1) - 1).clamp(min=0).to(i32).contiguous()
+        pos0 = att.sum(-1).to(i32).contiguous()
+        idx = torch.arange(L, device=dev, dtype=i32)[None, :].expand(B, L)
+        last_rows = (torch.arange(B, device=dev, dtype=i32) * L + (idx * att).max(dim=-1).values.to(i32)).contiguous()
+        shape = (c.num_hidden_layers, B, c.num_key_value_heads, L, c.head_dim)          # Lmax = L: nothing is appended to the cache
+        kc, vc = torch.empty(shape, dtype=BF16, device=dev), torch.empty(shape, dtype=BF16, device=dev)
+        lora_img = None
+        if self.train_base:
+            self._bind_ft()
+        if self.lora_rank:
+            self._bind_lora()
+            lora_img = torch.empty(L_.ta_lm_lora_image_bytes(C.byref(self._w)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(L_.ta_lm_prefill_workspace_bytes(C.byref(self._w), B, L), dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, self.vocab_pad), dtype=F32, device=dev)
+        ids = input_ids.to(device=dev, dtype=i64).contiguous()
+        a = None if audio is None else audio.detach().to(F32).contiguous()
+        _lib.check(L_.ta_lm_prefill(C.byref(self._w), ptr(ids), ptr(src_row), ptr(a), ptr(att), ptr(pos_full), B, L, ptr(kc), ptr(vc), L,
+                                    ptr(last_rows), ptr(logits), ptr(lora_img), ptr(ws), ws.numel(), stream()), "ta_lm_prefill")
+        del ws
+        for r0, r1 in chunks:
+            n, Tc = r1 - r0, max(n_host[r0:r1])
+            need = L_.ta_lm_score_workspace_bytes(C.byref(self._w), B, n, Tc)
+            if need < 0:
+                raise ValueError(f"{n} rows x {Tc} tokens is outside one scoring call's limits {scoring.limits()}")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            cid = token_ids[r0:r1, :Tc].to(device=dev).contiguous()
+            lens = torch.tensor(n_host[r0:r1], dtype=i32, device=dev)
+            lens_host = (C.c_int * n)(*n_host[r0:r1])
+            clip = torch.tensor(clip_host[r0:r1], dtype=i32, device=dev)
+            lp = torch.empty((n, Tc), dtype=F32, device=dev)
+            _lib.check(L_.ta_lm_score(C.byref(self._w), ptr(cid), ptr(lens), lens_host, ptr(clip), ptr(pos0), B, n, Tc, ptr(kc), ptr(vc), L,
+                                      ptr(att), ptr(logits), ptr(lora_img), ptr(lp), ptr(scores[r0:r1]), ptr(ws), ws.numel(), stream()),
+                       "ta_lm_score")
+            token_lp[r0:r1, :Tc] = lp
+        return token_lp, scores
+
     def greedy_decode_iter(self, input_ids, src_row, audio, attention_mask=None, max_new_tokens=128, eos_ids=(), pad_id=0,
                            sync_every=8, use_graph=True, per_token=True, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
                            processors_see_prompt=True, sampling=None, token_scores=False, top_logprobs=0, sequence_bias=None,

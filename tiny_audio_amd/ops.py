@@ -253,6 +253,25 @@ def attention_fwd_seg(Q, K, VT, L, scale, kmask=None, seg=None, want_lse=True, o
     return O, lse
 
 
+def attention_extend(Q, Kn, Vn, Kc, Vc, pmask, clip_of, lens, scale, want_lse=True, out=None):
+    """ta_attention_extend: R rows of T given positions behind the prompt cache of their clips.  Q [R,Hq,T,128], Kn / Vn [R,Hkv,T,128]
+    bf16 (the row's own keys, ``lens`` int32 [R] of them valid), Kc / Vc [B,Hkv,Lmax,128] bf16 = one layer of the prompt cache, read in
+    place through ``clip_of`` int32 [R]; pmask int32 [B, Lp], Lp <= Lmax -> O [R*T, Hq*128] bf16 (exact 0 at t >= lens[r]), LSE
+    [R,Hq,T] or None.  ``out``: the tensor to write O into."""
+    R, Hq, T, hd = Q.shape
+    B, Hkv, Lmax, _ = Kc.shape
+    assert hd == 128 and Kn.shape == (R, Hkv, T, hd) and Vn.shape == Kn.shape and Vc.shape == Kc.shape
+    assert pmask.dtype == torch.int32 and pmask.dim() == 2 and pmask.shape[0] == B
+    assert clip_of.dtype == torch.int32 and clip_of.numel() == R and lens.dtype == torch.int32 and lens.numel() == R
+    for t in (Q, Kn, Vn, Kc, Vc, pmask, clip_of, lens):
+        _req(t)
+    O = _out(out, (R * T, Hq * hd), Q.device)
+    lse = torch.empty((R, Hq, T), device=Q.device, dtype=F32) if want_lse else None
+    check(lib().ta_attention_extend(ptr(Q), ptr(Kn), ptr(Vn), ptr(Kc), ptr(Vc), ptr(pmask), ptr(clip_of), ptr(lens), ptr(O), ptr(lse),
+                                    B, R, Hq, Hkv, T, pmask.shape[1], Lmax, scale, stream()), "ta_attention_extend")
+    return O, lse
+
+
 def attention_bwd_seg(Q, K, V, dO, lse, delta, L, scale, kmask=None, seg=None, out=None):
     """ta_attention_bwd_seg: the causal head_dim-128 backward over packed rows (``seg`` None = the plain causal call).
     ``out``: (dQ, dK, dV) to write into."""
