@@ -1120,6 +1120,72 @@ int ta_w2v_pos_conv(const void* x, int x_f32, const void* wp, const float* bias,
 int ta_w2v_head_logsoftmax(const float* logits, long ld, const float* bias, int n_classes, float* out, int rows,
                            hipStream_t st);
 
+/* ---- the "layer-norm / stable" wav2vec2 family (wav2vec2-large-960h-lv60(-self), XLSR-53 and XLS-R 300M fine-tunes, MMS 300M /
+ * torchaudio's MMS_FA): Wav2Vec2ForCTC.forward with feat_extract_norm="layer", conv_bias=True, do_stable_layer_norm=True, eager
+ * attention, no attention mask, optional input normalisation; inference only, every clip as if alone.  Against the base model:
+ * every conv layer is conv + bias -> LayerNorm over the CHANNELS of a frame (affine, nn.LayerNorm's default eps 1e-5, NOT ln_eps) ->
+ * exact GELU (Wav2Vec2LayerNormConvLayer); the encoder adds the positional conv with no LayerNorm behind it, runs pre-LN layers
+ * x += out_proj(attn(layer_norm(x))), x += ffn(final_layer_norm(x)) (Wav2Vec2EncoderLayerStableLayerNorm) and applies
+ * encoder.layer_norm behind the last one (Wav2Vec2EncoderStableLayerNorm).  Contract: DESIGN.md section 3, "wav2vec2 acoustic model:
+ * the layer-norm / stable family", defined by tests/wav2vec2_sln_ref.py.  ta_enc_layer as for ta_wav2vec2_weights (ln1_* =
+ * layer_norm, now IN FRONT of the attention; ln2_* = final_layer_norm, in front of the feed-forward).
+ * Not built, refused with TA_ERR_ARG: conv_dim other than 64 / 128 / 256 / 512, head_dim != 64 (XLS-R 1B / 2B), more than
+ * TA_W2V_HEAD_PAD classes; adapter layers (MMS adapter_attn_dim) and the two mixed configurations have no field here at all. */
+typedef struct {
+  int hidden, ffn, n_layers, heads, conv_dim, n_classes;   /* as ta_wav2vec2_weights; conv_dim in {64, 128, 256, 512} */
+  float ln_eps;                /* feature_projection.layer_norm, the layers' norms and encoder.layer_norm */
+  float input_norm_eps;        /* > 0: each clip's samples become (x - mean) / sqrt(var + eps), biased variance over the clip's own
+                                  samples (1e-7: Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm; 1e-5: torchaudio's
+                                  layer_norm(waveform, waveform.shape)); 0: the raw waveform goes in */
+  const float* conv0_w;        /* f32 [C, 10]: conv_layers.0.conv.weight */
+  const float* conv_b[7];      /* [C]: conv_layers.l.conv.bias */
+  const float *conv_ln_w[7], *conv_ln_b[7];   /* [C]: conv_layers.l.layer_norm */
+  const void* conv_w[6];       /* conv_layers.1 .. 6: bf16 [C, k*C], column = tap*C + cin */
+  const float *fp_ln_w, *fp_ln_b;
+  const void* fp_w;            /* bf16 [H, C] */
+  const float* fp_b;
+  const void* pos_w;           /* the packed image of ta_wav2vec2_weights.pos_w */
+  const float* pos_b;
+  const float *enc_ln_w, *enc_ln_b; /* encoder.layer_norm (behind the LAST layer) */
+  const ta_enc_layer* layers;  /* host array [n_layers] */
+  const void* head_w;          /* bf16 [TA_W2V_HEAD_PAD, H], rows >= n_classes ZERO */
+  const float* head_b;         /* [n_classes] */
+  int res_f32;
+} ta_wav2vec2_sln_weights;
+
+/* Same arguments, layouts and workspace tail (the lm_head GEMM's f32 output) as ta_wav2vec2_forward.  Replaces
+ * TF:models/wav2vec2/modeling_wav2vec2.py Wav2Vec2LayerNormConvLayer.forward, Wav2Vec2EncoderStableLayerNorm.forward,
+ * Wav2Vec2EncoderLayerStableLayerNorm.forward and lm_head; with input_norm_eps > 0 also
+ * feature_extraction_wav2vec2.py zero_mean_unit_var_norm on each unpadded clip. */
+long ta_wav2vec2_sln_workspace_bytes(const ta_wav2vec2_sln_weights* w, int B, int Ls, long rows);
+int ta_wav2vec2_sln_forward(const ta_wav2vec2_sln_weights* w, const float* wav, const int* lens_host, const int* lens_dev,
+                            const int* cu_frames_dev, int B, int Ls, float* emissions, void* ws, long ws_bytes, hipStream_t st);
+/* For the per-stage tests: byte offsets inside that workspace of (feat) the feature extractor's output on the compact rows, bf16
+ * [rows, conv_dim], and (stream) the residual stream behind the last layer, [rows, hidden] in the stream's dtype -- behind the
+ * positional-conv add when n_layers = 0.  HOST pointers; no launch. */
+int ta_wav2vec2_sln_ws_offsets(const ta_wav2vec2_sln_weights* w, int B, int Ls, long rows, long* feat_off, long* stream_off);
+
+/* Its new kernels, exported for the tests.
+ * Input normalisation: out[b, i] = (wav[b, i] - mean_b) / sqrt(var_b + eps) for i < lens[b] (clipped to Ls), statistics over the
+ * clip's own samples with the biased variance; samples behind a clip's end are neither read nor written; out may be wav.  Per
+ * 4096-sample chunk (mean, sum of squared deviations from it) in f32, merged pairwise in f64 -- never E[x^2] - E[x]^2.  A silent
+ * clip gives zeros.  wav, out f32 [B, Ls]; ws: ta_w2v_input_norm_ws_bytes(B, Ls) bytes; eps > 0. */
+long ta_w2v_input_norm_ws_bytes(int B, int Ls);
+int ta_w2v_input_norm(const float* wav, const int* lens_dev, int B, int Ls, float eps, float* out, void* ws, long ws_bytes,
+                      hipStream_t st);
+/* Conv layer 0 (k 10, stride 5) + bias + LayerNorm over the C channels of each frame (biased variance, eps) + exact GELU in ONE
+ * kernel: replaces Wav2Vec2LayerNormConvLayer.forward for layer 0.  Same output contract as ta_w2v_conv0_gn_gelu: out bf16
+ * time-major, clip b's frame t at row b * out_rpb + t (out_rpb >= (Ls - 10) / 5 + 1), rows t >= T0_b not written.  One wave per
+ * frame, a lane owning C / 64 contiguous channels; mean first, then squared deviations from it; no workspace.
+ * C in {64, 128, 256, 512} (TA_ERR_ARG otherwise). */
+int ta_w2v_conv0_ln_gelu(const float* wav, const int* lens_dev, int B, int Ls, const float* w, const float* bias, const float* ln_w,
+                         const float* ln_b, int C, float eps, void* out_bf16, long out_rpb, hipStream_t st);
+/* y = gelu(LayerNorm(x)) row by row, bf16 [M, H] -> bf16 [M, H], y != x: ta_layernorm_bf16's kernels with exact-erf GELU as their
+ * output activation -- the LayerNorm + GELU behind conv layers 1 .. 6 (Wav2Vec2LayerNormConvLayer.forward) as one pass over the rows.
+ * A row of NaN stays in its row.  H as ta_layernorm_bf16 takes it. */
+int ta_layernorm_gelu_bf16(const void* x_bf16, const float* w, const float* b, void* y_bf16, int M, int H, float eps,
+                           hipStream_t st);
+
 /* ---- frozen ECAPA-TDNN speaker-embedding model: the hot path of speaker diarization (tiny_audio_amd/csrc/ecapa.hip).  Replaces the
  * loop of the reference's LocalSpeakerDiarizer._extract_embeddings, which reflect-pads every 0.75 s window and pushes it through
  * SpeechBrain's spkrec-ecapa-voxceleb encode_batch ONE WINDOW PER CALL (tiny_audio/diarization.py:457-517; the call itself :490-502).

@@ -62,6 +62,17 @@ class Wav2Vec2Weights(C.Structure):
                 ("layers", C.POINTER(EncLayer)), ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("res_f32", C.c_int)]
 
 
+class Wav2Vec2SlnWeights(C.Structure):
+    """ta_wav2vec2_sln_weights (include/ta355.h): the layer-norm / stable family; reuses EncLayer."""
+    _fields_ = [("hidden", C.c_int), ("ffn", C.c_int), ("n_layers", C.c_int), ("heads", C.c_int), ("conv_dim", C.c_int),
+                ("n_classes", C.c_int), ("ln_eps", C.c_float), ("input_norm_eps", C.c_float),
+                ("conv0_w", C.c_void_p), ("conv_b", C.c_void_p * 7), ("conv_ln_w", C.c_void_p * 7), ("conv_ln_b", C.c_void_p * 7),
+                ("conv_w", C.c_void_p * 6),
+                ("fp_ln_w", C.c_void_p), ("fp_ln_b", C.c_void_p), ("fp_w", C.c_void_p), ("fp_b", C.c_void_p),
+                ("pos_w", C.c_void_p), ("pos_b", C.c_void_p), ("enc_ln_w", C.c_void_p), ("enc_ln_b", C.c_void_p),
+                ("layers", C.POINTER(EncLayer)), ("head_w", C.c_void_p), ("head_b", C.c_void_p), ("res_f32", C.c_int)]
+
+
 class EcapaBlock(C.Structure):
     """ta_ecapa_block (include/ta355.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "bn1_s", "bn1_t", "res_w", "res_b", "res_s", "res_t", "w2", "b2", "bn2_s", "bn2_t",

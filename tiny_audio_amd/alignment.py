@@ -192,14 +192,36 @@ def _spans(tokens: Sequence[int], frames: Sequence[int], failed: bool, num_frame
     return [(tokens[i], float(frames[i]), float(frames[i]) + 1.0) for i in range(len(tokens))]
 
 
-def _tokenize(text: str, dictionary: dict) -> list[int]:
+def _tokenize(text: str, dictionary: dict, as_written: bool = False) -> list[int]:
+    """Characters -> class ids; a character the dictionary lacks is dropped, a space becomes the word separator.  ``as_written``
+    (an acoustic model's own vocabulary, ``Wav2Vec2CtcMI355X.set_vocab``): a character is looked up as written, then upper-cased,
+    then lower-cased -- HF vocabularies are lower-case, ``LABELS`` is upper-case -- instead of the whole text being upper-cased."""
     tokens = []
+    if as_written:
+        for char in text:
+            for form in (char, char.upper(), char.lower()):
+                if form in dictionary:
+                    tokens.append(dictionary[form])
+                    break
+            else:
+                if char == " ":
+                    tokens.append(dictionary.get("|", dictionary.get(" ", 0)))
+        return tokens
     for char in text.upper():
         if char in dictionary:
             tokens.append(dictionary[char])
         elif char == " ":
             tokens.append(dictionary.get("|", dictionary.get(" ", 0)))
     return tokens
+
+
+def _vocab_of(acoustic_model, default_dictionary: dict, blank_id):
+    """-> (dictionary, blank id, as_written): the acoustic model's own vocabulary when it carries one (``set_vocab``), else
+    ``default_dictionary`` and blank 0 as ever.  An explicit ``blank_id`` wins."""
+    d = getattr(acoustic_model, "dictionary", None)
+    if d is None:
+        return default_dictionary, (0 if blank_id is None else int(blank_id)), False
+    return d, (int(acoustic_model.blank_id) if blank_id is None else int(blank_id)), True
 
 
 def _group_words(text: str, spans, dictionary: dict, frame_duration: float, start_offset: float, end_offset: float) -> list[dict]:
@@ -314,19 +336,20 @@ class ForcedAligner:
         return cls.align_batch([emission], [text], log_softmax=log_softmax, _dictionary=dictionary, _frame_duration=frame_duration)[0]
 
     @classmethod
-    def align_audio_batch(cls, audios: Sequence, texts: Sequence[str], acoustic_model, *, blank_id: int = 0) -> list[list[dict]]:
+    def align_audio_batch(cls, audios: Sequence, texts: Sequence[str], acoustic_model, *, blank_id: int | None = None) -> list[list[dict]]:
         """Waveforms -> words for a batch: ``acoustic_model`` (``wav2vec2.Wav2Vec2CtcMI355X``) turns the 16 kHz clips ``audios``
         (1-D arrays or tensors of any lengths >= 400 samples) into emissions in ONE call, and the trellis kernel reads them where
-        they are: the emissions never visit the host.  Same words as ``align`` per clip."""
+        they are: the emissions never visit the host.  Same words as ``align`` per clip.  A model that carries a vocabulary
+        (``set_vocab``) is tokenised against it with its own blank id; otherwise ``LABELS`` and blank 0 (``blank_id`` overrides)."""
         if len(audios) != len(texts):
             raise ValueError(f"{len(audios)} clips but {len(texts)} texts")
-        dictionary = cls._dict()
+        dictionary, blank_id, as_written = _vocab_of(acoustic_model, cls._dict(), blank_id)
         out: list[list[dict]] = [[] for _ in texts]
         if not len(texts):
             return out
         if len(texts) > ALIGN_LIMITS["clips"]:
             raise ValueError(f"{len(texts)} clips: the alignment kernel takes at most {ALIGN_LIMITS['clips']} clips per launch")
-        tokens = [_tokenize(t, dictionary) for t in texts]
+        tokens = [_tokenize(t, dictionary, as_written) for t in texts]
         em, Ts = acoustic_model(list(audios))
         for n, tk in enumerate(tokens):
             _check_clip(em[:Ts[n]], tk, blank_id)
@@ -362,16 +385,17 @@ class ForcedAligner:
 
     # ------------------------------------------------------------------ long form
     @classmethod
-    def align_long_batch(cls, emissions: Sequence[torch.Tensor], texts: Sequence[str], *, log_softmax: bool = False, blank_id: int = 0,
-                         col_block: int = 0, frame_block: int = 0) -> list[list[dict]]:
+    def align_long_batch(cls, emissions: Sequence[torch.Tensor], texts: Sequence[str], *, log_softmax: bool = False, blank_id: int | None = None,
+                         col_block: int = 0, frame_block: int = 0, acoustic_model=None) -> list[list[dict]]:
         """``align_batch`` beyond its envelope: up to 64 clips of up to 1 048 576 frames against up to 262 144 characters each, in one
         call of ``torch.ops.ta355.ctc_align_long``.  Same word lists (the reference's two quirks of ``_group_words`` included);
-        ``col_block`` x ``frame_block`` is the trellis tile (0 = the default) and does not change the result."""
+        ``col_block`` x ``frame_block`` is the trellis tile (0 = the default) and does not change the result.  ``acoustic_model``: the
+        model the emissions came from; only its vocabulary and blank id are read (``set_vocab``), it is not run."""
         if len(emissions) != len(texts):
             raise ValueError(f"{len(emissions)} emission matrices but {len(texts)} texts")
         _check_tile(int(col_block), int(frame_block))
-        dictionary = cls._dict()
-        tokens = [_tokenize(t, dictionary) for t in texts]
+        dictionary, blank_id, as_written = _vocab_of(acoustic_model, cls._dict(), blank_id)
+        tokens = [_tokenize(t, dictionary, as_written) for t in texts]
         live = [n for n, tk in enumerate(tokens) if tk]
         out: list[list[dict]] = [[] for _ in texts]
         if not live:
@@ -399,9 +423,11 @@ class ForcedAligner:
                 raise ValueError("align_long needs emission=... or acoustic_model=...")
             if sample_rate != SAMPLE_RATE:
                 raise ValueError(f"acoustic_model takes {SAMPLE_RATE} Hz audio, got sample_rate={sample_rate}: resample first")
-            n_tokens = len(_tokenize(text, cls._dict()))
+            dictionary, _, as_written = _vocab_of(acoustic_model, cls._dict(), None)
+            n_tokens = len(_tokenize(text, dictionary, as_written))
             if n_tokens > ALIGN_LONG_LIMITS["tokens"]:                                  # before the acoustic model runs for nothing
                 raise ValueError(f"{n_tokens} tokens: the long alignment kernel takes at most {ALIGN_LONG_LIMITS['tokens']} tokens "
                                  "per clip")
             emission = acoustic_model.emissions_long(audio, window_s=window_s, context_s=context_s)
+            return cls.align_long_batch([emission], [text], acoustic_model=acoustic_model)[0]
         return cls.align_long_batch([emission], [text])[0]

@@ -74,7 +74,9 @@ __device__ __forceinline__ uint4 pack8bf(const float* o) {
 
 // ----------------------------------------------------------------------------- LayerNorm
 // IN_BF16: the row is read as bf16 (the encoder's bf16 residual stream, as the reference's bf16 model keeps it)
-template <int MAXV, bool OUT_BF16, bool OUT_F32, bool IN_BF16 = false>
+// ACT: what is applied to the normalised row before it is stored -- 0 nothing, 1 exact-erf GELU (wav2vec2's LayerNorm conv layers:
+// LayerNorm over the channels, then GELU, as one pass over the rows)
+template <int MAXV, bool OUT_BF16, bool OUT_F32, bool IN_BF16 = false, int ACT = 0>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         const float* __restrict__ b, bf16_t* __restrict__ yb,
                                                         float* __restrict__ yf, const float* __restrict__ rowscale,
@@ -117,6 +119,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       o.y = ((v[i].y - mean) * rstd * ww.y + bb.y) * rs;
       o.z = ((v[i].z - mean) * rstd * ww.z + bb.z) * rs;
       o.w = ((v[i].w - mean) * rstd * ww.w + bb.w) * rs;
+      if constexpr (ACT == 1) { o.x = gelu_erf(o.x); o.y = gelu_erf(o.y); o.z = gelu_erf(o.z); o.w = gelu_erf(o.w); }
       if (OUT_F32) ((float4*)(yf + (long)row * H))[c] = o;
       if (OUT_BF16) {
         uint2 p; p.x = pack2bf(o.x, o.y); p.y = pack2bf(o.z, o.w);
@@ -137,7 +140,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // T = float is the fp32-stream mode of the encoder (round 6): two 16-byte loads and one 16-byte store per chunk and lane.  The generic
 // wave-per-row kernel it replaces there re-read gamma and beta (10 KB) for every 5-KB row: 24.4 us per launch at B = 32 (123 MB:
 // 5.0 TB/s).
-template <typename T, int NCH, int ROWS>
+// ACT: as layernorm_kernel's.
+template <typename T, int NCH, int ROWS, int ACT = 0>
 __global__ __launch_bounds__(256) void layernorm_x8_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ b, bf16_t* __restrict__ y,
                                                            const float* __restrict__ rowscale, int M, float eps) {
@@ -199,6 +203,10 @@ __global__ __launch_bounds__(256) void layernorm_x8_kernel(const T* __restrict__
       float o[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = ((v[i][j] - mean) * rstd * ww[i][j] + bb[i][j]) * rs;
+      if constexpr (ACT == 1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = gelu_erf(o[j]);
+      }
       yr[l + i * 32] = pack8bf(o);
     }
   }
@@ -497,11 +505,13 @@ static bool norm_bad_H(int H) { return (H & 3) || H > 64 * 4 * MAXV_LIMIT; }
 // the half-wave-per-row (*_x8) kernels take H a multiple of 256 up to 2048; other shapes: the wave-per-row kernels
 static bool half_wave_H(int H) { return (H % 256) == 0 && H <= 2048; }
 
-template <typename T>
+// ACT = 1 (GELU behind the norm) exists for bf16 rows with bf16 as the only output (wav2vec2's conv layers)
+template <typename T, int ACT = 0>
 static int layernorm_dispatch(const T* x, const float* w, const float* b, void* y_bf16, float* y_f32, const float* rowscale, int M, int H,
                               float eps, hipStream_t st) {
   if (M <= 0) return TA_OK;
   if (norm_bad_H(H) || (!y_bf16 && !y_f32)) return TA_ERR_ARG;
+  if (ACT != 0 && (!y_bf16 || y_f32)) return TA_ERR_ARG;
   bf16_t* yb = (bf16_t*)y_bf16;
   const dim3 blk(256);
   if (y_bf16 && !y_f32 && half_wave_H(H)) {              // bf16 is the only output
@@ -511,7 +521,7 @@ static int layernorm_dispatch(const T* x, const float* w, const float* b, void* 
     const dim3 g8(ta_cdiv(M, 8 * rows));
     with_nch(H, [&](auto nch) {
       with_const<4, 2, 1>(rows, [&](auto r) {
-        TA_LAUNCH((layernorm_x8_kernel<T, decltype(nch)::value, decltype(r)::value>), g8, blk, 0, st, x, w, b, yb, rowscale, M, eps);
+        TA_LAUNCH((layernorm_x8_kernel<T, decltype(nch)::value, decltype(r)::value, ACT>), g8, blk, 0, st, x, w, b, yb, rowscale, M, eps);
       });
     });
     TA_CHECK_LAUNCH();
@@ -522,6 +532,7 @@ static int layernorm_dispatch(const T* x, const float* w, const float* b, void* 
   const float* xf = (const float*)x;
   with_maxv(H, [&](auto maxv) {
     constexpr int V = decltype(maxv)::value;
+    if constexpr (ACT != 0) { TA_LAUNCH((layernorm_kernel<V, true, false, IN_BF16, ACT>), grid, blk, 0, st, xf, w, b, yb, y_f32, rowscale, M, H, eps); return; }
     if (y_bf16 && y_f32) TA_LAUNCH((layernorm_kernel<V, true, true, IN_BF16>), grid, blk, 0, st, xf, w, b, yb, y_f32, rowscale, M, H, eps);
     else if (y_bf16) TA_LAUNCH((layernorm_kernel<V, true, false, IN_BF16>), grid, blk, 0, st, xf, w, b, yb, y_f32, rowscale, M, H, eps);
     else TA_LAUNCH((layernorm_kernel<V, false, true, IN_BF16>), grid, blk, 0, st, xf, w, b, yb, y_f32, rowscale, M, H, eps);
@@ -533,6 +544,12 @@ static int layernorm_dispatch(const T* x, const float* w, const float* b, void* 
 extern "C" int ta_layernorm_bf16(const void* x_bf16, const float* w, const float* b, void* y_bf16, float* y_f32,
                                  const float* rowscale, int M, int H, float eps, hipStream_t st) {
   return layernorm_dispatch((const bf16_t*)x_bf16, w, b, y_bf16, y_f32, rowscale, M, H, eps, st);
+}
+
+extern "C" int ta_layernorm_gelu_bf16(const void* x_bf16, const float* w, const float* b, void* y_bf16, int M, int H, float eps,
+                                      hipStream_t st) {
+  if (M > 0 && (!x_bf16 || !w || !b || !y_bf16 || x_bf16 == y_bf16)) return TA_ERR_ARG;
+  return layernorm_dispatch<bf16_t, 1>((const bf16_t*)x_bf16, w, b, y_bf16, nullptr, nullptr, M, H, eps, st);
 }
 
 extern "C" int ta_layernorm_f32(const float* x, const float* w, const float* b, void* y_bf16, float* y_f32,

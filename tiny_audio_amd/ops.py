@@ -1295,6 +1295,54 @@ def w2v_head_logsoftmax(logits, bias, n_classes, out=None):
     return out
 
 
+def w2v_input_norm(wav, lens, eps, out=None):
+    """ta_w2v_input_norm: out[b, i] = (wav[b, i] - mean_b) / sqrt(var_b + eps) over each clip's own first ``lens[b]`` samples (biased
+    variance; 1e-7: transformers' ``zero_mean_unit_var_norm``, 1e-5: torchaudio's ``layer_norm(waveform, waveform.shape)``).
+    ``wav`` f32 [B, Ls], ``lens`` int32 [B] on the device -> f32 [B, Ls]; samples behind a clip's end are not written."""
+    _req(wav, F32)
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.device == wav.device
+    B, Ls = wav.shape
+    assert lens.shape == (B,)
+    if out is None:
+        out = torch.empty_like(wav)
+    assert out.dtype == F32 and out.is_contiguous() and out.shape == wav.shape
+    ws = torch.empty(max(lib().ta_w2v_input_norm_ws_bytes(B, Ls), 8), device=wav.device, dtype=torch.uint8)
+    check(lib().ta_w2v_input_norm(ptr(wav), ptr(lens), B, Ls, float(eps), ptr(out), ptr(ws), ws.numel(), stream()), "ta_w2v_input_norm")
+    return out
+
+
+def w2v_conv0_ln_gelu(wav, lens, w, bias, ln_w, ln_b, eps=1e-5, out=None, out_rpb=None):
+    """ta_w2v_conv0_ln_gelu: conv layer 0 (k 10, stride 5) + bias + LayerNorm over each frame's channels + exact GELU in one kernel.
+    ``wav`` f32 [B, Ls], ``lens`` int32 [B] on the device, ``w`` f32 [C, 10], C in {64, 128, 256, 512} -> bf16 [B, out_rpb, C]
+    time-major; clip b's rows t >= (lens[b] - 10) // 5 + 1 are not written (``out``: a tensor to write into)."""
+    _req(wav, F32), _req(w, F32), _req(bias, F32), _req(ln_w, F32), _req(ln_b, F32)
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.device == wav.device
+    B, Ls = wav.shape
+    Cd = w.shape[0]
+    assert w.shape == (Cd, 10) and bias.shape == (Cd,) and ln_w.shape == (Cd,) and ln_b.shape == (Cd,) and lens.shape == (B,)
+    T0 = (Ls - 10) // 5 + 1
+    rpb = T0 if out_rpb is None else int(out_rpb)
+    if out is None:
+        out = torch.empty((B, rpb, Cd), device=wav.device, dtype=BF16)
+    assert out.dtype == BF16 and out.is_contiguous() and out.numel() >= B * rpb * Cd
+    check(lib().ta_w2v_conv0_ln_gelu(ptr(wav), ptr(lens), B, Ls, ptr(w), ptr(bias), ptr(ln_w), ptr(ln_b), Cd, float(eps), ptr(out), rpb,
+                                     stream()), "ta_w2v_conv0_ln_gelu")
+    return out
+
+
+def layernorm_gelu(x, w, b, eps=1e-5, out=None):
+    """ta_layernorm_gelu_bf16: gelu(LayerNorm(x)) row by row, bf16 [M, H] -> bf16 [M, H] (the LayerNorm kernels with GELU as their
+    output activation: wav2vec2's LayerNorm conv layers 1 .. 6)."""
+    _req(x, BF16), _req(w, F32), _req(b, F32)
+    M, H = x.shape
+    assert w.shape == (H,) and b.shape == (H,)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == BF16 and out.is_contiguous() and out.shape == x.shape and out.data_ptr() != x.data_ptr()
+    check(lib().ta_layernorm_gelu_bf16(ptr(x), ptr(w), ptr(b), ptr(out), M, H, float(eps), stream()), "ta_layernorm_gelu_bf16")
+    return out
+
+
 # ----------------------------------------------------------------------------- ECAPA-TDNN kernels (csrc/ecapa.hip)
 def ecapa_fbank(audio, starts, lens, window_samples, tables):
     """ta_ecapa_fbank: ``audio`` f32 [n], ``starts`` / ``lens`` int32 [N] on the device, ``tables`` = (window, twiddle, mel, ranges)

@@ -13,6 +13,8 @@ reference has no FFI; its seams are nn.Module boundaries,
     ta355::wave_cut_cost, cut_plan, wave_windows   long-form transcription: where to cut a recording and the cut itself; the reference
                                keeps the first chunk only   tiny_audio/asr_pipeline.py:243-245
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
+    ta355::wav2vec2_sln_emissions  the same seam with a layer-norm / stable wav2vec2 (large-lv60, XLSR-53, XLS-R 300M, MMS 300M), which
+                               the reference's align(..., _language=...) placeholder stands for   tiny_audio/alignment.py:182-211
     ta355::ecapa_embeddings    SpeechBrain ECAPA-TDNN encode_batch, one call per window   tiny_audio/diarization.py:457-517
     ta355::spk_affinity        SpectralCluster.get_sim_mat / p_pruning / get_laplacian   tiny_audio/diarization.py:49-89
     ta355::spk_laplacian_matmul, spk_panel_gram / _update / _combine   the products scipy.linalg.eigh is replaced by
@@ -410,6 +412,21 @@ def wav2vec2_emissions(waveforms: Tensor, lengths: List[int], handle: int) -> Te
 
 @wav2vec2_emissions.register_fake
 def _(waveforms, lengths, handle):
+    from .wav2vec2 import frames_of
+    return waveforms.new_empty((sum(frames_of(n) for n in lengths), module_of(handle).config.n_classes), dtype=F32)
+
+
+@torch.library.custom_op("ta355::wav2vec2_sln_emissions", mutates_args=())
+def wav2vec2_sln_emissions(waveforms: Tensor, lengths: List[int], normalized: bool, handle: int) -> Tensor:
+    """``wav2vec2_emissions`` for the layer-norm / stable family (``Wav2Vec2CtcMI355X`` with ``feat_extract_norm="layer"``:
+    wav2vec2-large-lv60, XLSR-53, XLS-R 300M, MMS 300M).  ``normalized``: the waveforms already have zero mean and unit variance,
+    so a ``normalize_input`` model skips that step (``emissions_long`` applies the whole recording's statistics once).  Replaces
+    ``Wav2Vec2ForCTC.forward`` of that configuration + ``log_softmax``.  No autograd."""
+    return module_of(handle)._forward_impl(waveforms, lengths, None, normalized)
+
+
+@wav2vec2_sln_emissions.register_fake
+def _(waveforms, lengths, normalized, handle):
     from .wav2vec2 import frames_of
     return waveforms.new_empty((sum(frames_of(n) for n in lengths), module_of(handle).config.n_classes), dtype=F32)
 
@@ -825,4 +842,5 @@ OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backwa
              "lm_forward_loss", "lm_backward", "whisper_encoder_forward", "wave_augment", "wave_augment_chain", "encoder_forward_ragged", "ctc_align",
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
              "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long", "beam_logprobs", "beam_topk",
-             "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows", "text_align")
+             "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows", "text_align",
+             "wav2vec2_sln_emissions")
