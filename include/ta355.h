@@ -1374,6 +1374,48 @@ int ta_cut_plan_f32(const float* cost, long ld, const long* offsets, int R, long
 int ta_wave_windows_f32(const float* wav, long total, const long* start, const int* len, int W, int Ls, float* out, long* lens,
                         hipStream_t st);
 
+/* ---- voice activity detection: per-frame speech decisions of whole recordings, model-free (tiny_audio_amd/csrc/vad.hip; driven by
+ * tiny_audio_amd/vad.py).  The reference takes its decisions from TEN-VAD, a compiled third-party library
+ * (tiny_audio/diarization.py:370-387); this is a statistical detector of its own, not a restatement of that model.  Contract: DESIGN.md
+ * section 3, "Voice activity detection", defined by tests/vad_ref.py.  The ragged layout of the segmentation block: R recordings in one
+ * flat f32 buffer `wav`, recording r at samples offsets[r] .. offsets[r + 1] (device long[R + 1]), starting at any sample; x[k] = 0
+ * outside [0, n) of a recording, whatever lies beside it.  The grid is the diarizer's: frame i for every i >= 0 with
+ * TA_VAD_HOP i < n - TA_VAD_HOP, F = ta_vad_frames(n) = (n - 1) / TA_VAD_HOP of them, 0 for n <= TA_VAD_HOP (which is legal).
+ * With h = smooth, W = noise_window, beta = noise_bias, theta = threshold, e0 = floor:
+ *   y[m]    = w[m] x[256 i - 72 + m], m = 0 .. 399          w the periodic Hann window of 400: the window is centred on the frame
+ *   P[i][f] = |DFT400(y)[f]|^2 / 400^2                       f = 2 .. 97
+ *   E[i][b] = sum_{f = 2 + 6 b}^{7 + 6 b} P[i][f]            b = 0 .. 15: 16 bands of 240 Hz, 80 Hz .. 3.92 kHz
+ *   S[i][b] = mean of E[j][b] over max(0, i - h) <= j <= min(F - 1, i + h)        the divisor counts the frames inside the grid
+ *   N[i][b] = min of S[j][b] over max(0, i - W) <= j <= min(F - 1, i + W)
+ *   g = (S + e0) / (beta N + e0),  t = g - 1 - ln g where g > 1, else 0,  L[i] = (1 / 16) sum_b t[i][b],  flag[i] = L[i] > theta
+ * in f32 and in a fixed order: the 6 bins of a band ascending (scaled by 1 / 400^2 after the sum), the at most 2 h + 1 frames of S
+ * ascending, (g - 1) - ln g, the 16 bands ascending.  No atomics, no workgroup waits for another; two runs give the same bits and a
+ * recording gives the same bits alone as inside a batch.  Zeros give L = 0 exactly.  A non-finite sample makes L NaN (flag 0) on every
+ * frame within W + h frames of one whose window holds it (or of the frame 2 j / 2 j + 1 that shares its transform): a NaN wins the
+ * minimum.
+ * Outputs: stat f32 [R, ld] = L, flags unsigned char [R, ld], ld >= ta_vad_frames(max_n); positions >= F of a row are not written.
+ * n_frames int [R] = F; a recording with n < 0 or n > max_n is refused: n_frames -1 and its rows are not written.
+ * Limits (TA_ERR_ARG beyond them): R <= TA_CUT_MAX_RECORDINGS, 1 <= max_n <= TA_CUT_HOP * TA_CUT_MAX_POSITIONS (2.9 h),
+ * 0 <= smooth <= TA_VAD_MAX_SMOOTH, 1 <= noise_window <= TA_VAD_MAX_NOISE_WINDOW, noise_bias >= 1, threshold > 0, floor > 0, all finite.
+ * ws: ta_vad_workspace_bytes(R, max_n) bytes (E, 64 bytes per frame), no initial contents required; 0 for arguments that would be
+ * refused, and for max_n <= TA_VAD_HOP, where ws, stat and flags may be NULL.  Two launches: the band energies (TA_VAD_ENERGY_FRAMES
+ * frames per workgroup, two real frames per complex transform) and the fused statistic (TA_VAD_TILE frames per workgroup plus a halo of
+ * W + h frames per side). */
+#define TA_VAD_HOP 256
+#define TA_VAD_LEAD 72
+#define TA_VAD_BANDS 16
+#define TA_VAD_BAND_BINS 6
+#define TA_VAD_FIRST_BIN 2
+#define TA_VAD_MAX_SMOOTH 8
+#define TA_VAD_MAX_NOISE_WINDOW 1024
+#define TA_VAD_ENERGY_FRAMES 32
+#define TA_VAD_TILE 256
+typedef struct { int smooth; int noise_window; float noise_bias; float threshold; float floor; } ta_vad_options;
+long ta_vad_frames(long n);
+long ta_vad_workspace_bytes(int R, long max_n);
+int ta_vad_f32(const float* wav, const long* offsets, int R, long max_n, const ta_vad_options* opt, float* stat, unsigned char* flags,
+               long ld, int* n_frames, void* ws, long ws_bytes, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ HEADER = os.path.join(ROOT, "include", "ta355.h")
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "libta355.so")
 SOURCES = ["gemm.hip", "gemm_tn.hip", "norm.hip", "attention.hip", "attention_extend.hip", "attention_enc.hip", "qkv_post.hip", "elementwise.hip", "loss.hip",
-           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "beam.hip", "decode_fused.hip", "augment.hip", "align.hip", "align_long.hip", "text_align.hip", "wav2vec2.hip", "ecapa.hip", "cluster.hip", "segment.hip", "api.hip"]
+           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "beam.hip", "decode_fused.hip", "augment.hip", "align.hip", "align_long.hip", "text_align.hip", "wav2vec2.hip", "ecapa.hip", "cluster.hip", "segment.hip", "vad.hip", "api.hip"]
 
 
 class Ta355Error(RuntimeError):
@@ -140,6 +140,11 @@ class CeOptions(C.Structure):
     _fields_ = [("eps", C.c_float), ("zc", C.c_float), ("obj", C.c_void_p)]
 
 
+class VadOptions(C.Structure):
+    """ta_vad_options (include/ta355.h): smoothing half-width, noise window, noise bias, threshold, floor."""
+    _fields_ = [("smooth", C.c_int), ("noise_window", C.c_int), ("noise_bias", C.c_float), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
 class LmLayerWgrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dwqkv", "dwo", "dwgu", "dwd", "dln_in", "dln_post", "dqn", "dkn")]
 
@@ -242,7 +247,7 @@ class _DryLib:
 
     def __getattr__(self, name):
         fn = getattr(self._h, name)
-        if name.endswith(("_bytes", "_floats")) or name == "ta_version":      # host-only calls (sizes, the ABI version)
+        if name.endswith(("_bytes", "_floats")) or name in ("ta_version", "ta_vad_frames"):      # host-only calls (sizes, counts, the ABI version)
             return fn
 
         def stub(*args):

@@ -872,7 +872,7 @@ class ASRModel(nn.Module):
     @torch.no_grad()
     def transcribe_long(self, audio, sample_rate: int = 16000, *, max_window_s: float = 28.0, min_window_s: float = 10.0,
                         batch_size: int = 32, return_timestamps: bool = False, acoustic_model=None,
-                        system_prompt: Optional[str] = None, **generate_kwargs):
+                        system_prompt: Optional[str] = None, vad=None, min_speech_s: float = 0.0, **generate_kwargs):
         """A whole 16 kHz recording -> ``{"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}`` (``audio``: a 1-D array or
         tensor; a list of them returns a list of results).  The reference keeps a long recording's first chunk only
         (tiny_audio/asr_pipeline.py:243-245); this transcribes all of it, up to 2.9 h per recording (``tiny_audio_amd/longform.py``).
@@ -888,14 +888,18 @@ class ASRModel(nn.Module):
 
         ``return_timestamps=True`` adds ``"words"`` [{'word', 'start', 'end'}]: ``ForcedAligner.align_audio_batch`` with
         ``acoustic_model`` (a ``wav2vec2.Wav2Vec2CtcMI355X``, required) on the same windows in the same groups, shifted by each
-        window's start; a window shorter than one acoustic frame (400 samples) or with no text has no words."""
+        window's start; a window shorter than one acoustic frame (400 samples) or with no text has no words.
+
+        ``vad=`` (a ``vad.DeviceVAD``; opt-in, None changes nothing): the detector runs on the uploaded buffer, the diarizer's hysteresis
+        turns its flags into speech segments, every chunk gains ``"speech_s"`` (the seconds of those segments inside the window), and a
+        window with ``speech_s <= min_speech_s`` is neither gathered nor decoded nor aligned: its text is ``""`` and it has no words."""
         from .longform import transcribe_long
         was_training = self.training
         self.eval()
         try:
             return transcribe_long(self, audio, sample_rate, max_window_s=max_window_s, min_window_s=min_window_s, batch_size=batch_size,
                                    return_timestamps=return_timestamps, acoustic_model=acoustic_model, system_prompt=system_prompt,
-                                   **generate_kwargs)
+                                   vad=vad, min_speech_s=min_speech_s, **generate_kwargs)
         finally:
             self.train(was_training)
 

@@ -1,5 +1,5 @@
-"""Speaker diarization: who spoke when.  TEN-VAD speech segments -> ECAPA-TDNN embeddings of sliding windows -> spectral clustering
--> frame-level voting -> merged speaker segments.
+"""Speaker diarization: who spoke when.  Speech segments from a VAD (TEN-VAD, or ``vad.DeviceVAD`` on the device) -> ECAPA-TDNN
+embeddings of sliding windows -> spectral clustering -> frame-level voting -> merged speaker segments.
 
 This is the counterpart of the reference's ``tiny_audio/diarization.py`` (the module behind ``ASRPipeline(return_speakers=True)``,
 tiny_audio/asr_pipeline.py:133-152): the same class names, class constants, arguments, return values and quirks, restated.  What
@@ -12,9 +12,11 @@ reference has them.  Spectral clustering is not: ``SpectralCluster`` restates th
 hour.  It stays the default; ``cluster_device=`` (``SpeakerClusterer(device=...)``) moves the affinity, the Laplacian and the few
 eigenpairs that are read onto the device (``tiny_audio_amd/spectral.py``) and leaves the eigengap rule, k-means and merging here.
 
-Third-party pieces that are not rebuilt: the VAD (``ten_vad``, a compiled library; pass ``speech_frames=`` or ``vad=`` to do without
+Third-party pieces that are not rebuilt: TEN-VAD itself (``ten_vad``, a compiled library and the default; ``vad=DeviceVAD()`` -- the
+model-free detector of ``tiny_audio_amd/vad.py``, whose constants are not validated on real speech -- or ``speech_frames=`` do without
 it), file reading and resampling (``librosa``), and -- only without ``speaker_model`` -- SpeechBrain.  Each raises ``ImportError``
-where it is needed and absent.
+where it is needed and absent.  With ``vad=DeviceVAD()``, ``speaker_model=`` and ``cluster_device=`` a waveform array is diarized with
+nothing third-party on the hot path.
 """
 from __future__ import annotations
 
@@ -209,7 +211,8 @@ class LocalSpeakerDiarizer:
         speaker_model: an ``EcapaTdnnMI355X``; every window of every segment goes through one ``embed_windows`` call.  Without it
             SpeechBrain runs through PyTorch one window per call, as in the reference.
         speech_frames: the VAD's decisions, one per 256 samples, instead of running a VAD.
-        vad: an object with TEN-VAD's ``process(int16 frame) -> (probability, flag)`` instead of the process-wide TEN-VAD."""
+        vad: an object with TEN-VAD's ``process(int16 frame) -> (probability, flag)`` instead of the process-wide TEN-VAD; or one with
+            ``speech_frames(audio) -> one decision per 256 samples`` (a ``vad.DeviceVAD``), which is called once on the whole array."""
         if isinstance(audio, str):
             import librosa
             audio, sample_rate = librosa.load(audio, sr=16000)
@@ -232,6 +235,10 @@ class LocalSpeakerDiarizer:
     def _get_speech_segments(cls, audio_array: np.ndarray, sample_rate: int = 16000, *, speech_frames=None, vad=None):
         """-> (speech segments after hysteresis, the raw per-frame decisions).  Frames start every 256 samples while a whole frame
         AND at least one further sample remain, as the reference's loop has it."""
+        if speech_frames is None and vad is not None and hasattr(vad, "speech_frames"):     # a whole-recording detector: one call, no frame loop
+            from .vad import segments_from_flags
+            flags = np.asarray(vad.speech_frames(audio_array)).astype(bool).reshape(-1)
+            return segments_from_flags(flags, sample_rate), flags.tolist()
         if speech_frames is not None:
             frames = [bool(f) for f in speech_frames]
         else:

@@ -6,7 +6,8 @@ position (smoothed short-time power, plus a small share of the recording's mean 
 ones), ``ta_cut_plan_f32`` picks the cheapest cuts that keep every window between ``min_window_s`` and ``max_window_s``, and
 ``ta_wave_windows_f32`` gathers the windows, longest first, into the padded batches that the unchanged feature extractor, encoder,
 decode loop and aligner take (csrc/segment.hip; DESIGN.md section 3, "Long-form transcription").  Only the cut table (a few integers
-per window) visits the host: the prompts are built from it.
+per window) visits the host: the prompts are built from it.  With ``vad=`` (a ``vad.DeviceVAD``) the detector runs on the same
+uploaded buffer, its flags are the one further read-back, and a window without speech is neither gathered nor decoded nor aligned.
 """
 from __future__ import annotations
 
@@ -148,7 +149,8 @@ def join_texts(texts: Sequence[str]) -> str:
 
 
 def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: float = 28.0, min_window_s: float = 10.0, batch_size: int = 32,
-                    return_timestamps: bool = False, acoustic_model=None, system_prompt=None, **generate_kwargs):
+                    return_timestamps: bool = False, acoustic_model=None, system_prompt=None, vad=None, min_speech_s: float = 0.0,
+                    **generate_kwargs):
     """``ASRModel.transcribe_long`` (documented there)."""
     from .asr_processing import ASRProcessor
     from .eval_text import postprocess_tokens
@@ -159,6 +161,13 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
     if return_timestamps and acoustic_model is None:
         raise ValueError("return_timestamps=True needs acoustic_model=... (a wav2vec2.Wav2Vec2CtcMI355X): word times come from forced "
                          "alignment of every window")
+    min_speech_s = float(min_speech_s)
+    if not 0.0 <= min_speech_s < float("inf"):
+        raise ValueError(f"min_speech_s must be finite and >= 0; got {min_speech_s}")
+    if vad is None and min_speech_s > 0.0:
+        raise ValueError("min_speech_s needs vad=... (a vad.DeviceVAD): without one no window's speech is known")
+    if vad is not None and not hasattr(vad, "run_uploaded"):
+        raise ValueError("vad must have run_uploaded(flat, offsets, lens), as a vad.DeviceVAD has: the detector runs on the uploaded buffer")
     enc_cfg = model.audio_tower.config
     frames_cap = 2 * int(getattr(enc_cfg, "max_source_positions", None) or enc_cfg.max_position_embeddings)
     if int(np.floor(POSITIONS_PER_SECOND * float(max_window_s) + 1e-9)) > frames_cap:
@@ -173,6 +182,11 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
     plans = plan_uploaded(flat, offsets, lens, min_len, max_len)
     off_h = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     win = [(r, i, int(off_h[r]) + s, n) for r, p in enumerate(plans) for i, (s, n) in enumerate(zip(p.starts, p.lengths))]
+    speech = None                                       # seconds of speech per window; a window at or below min_speech_s is not decoded
+    if vad is not None:
+        from .vad import window_speech_seconds
+        speech = window_speech_seconds(vad, flat, offsets, lens, [(w[0], w[2] - int(off_h[w[0]]), w[3]) for w in win])
+    keep = list(range(len(win))) if speech is None else [k for k in range(len(win)) if speech[k] > min_speech_s]
     dev = flat.device
     fe = model.feature_extractor
     kw = dict(generate_kwargs)
@@ -185,7 +199,8 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
     sys_prompt = system_prompt or model.system_prompt
     prompt_cache: dict = {}
     texts, words = [""] * len(win), [[] for _ in win]
-    for group in group_windows([w[3] for w in win], int(batch_size)):
+    for group in group_windows([win[k][3] for k in keep], int(batch_size)):
+        group = [keep[j] for j in group]
         g_len = [win[k][3] for k in group]
         start = torch.tensor([win[k][2] for k in group], dtype=torch.int64).to(dev)
         length = torch.tensor(g_len, dtype=torch.int32).to(dev)
@@ -220,6 +235,9 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
         ks = [k for k, w in enumerate(win) if w[0] == r]
         t0 = int(off_h[r])
         chunks = [{"text": texts[k], "timestamp": ((win[k][2] - t0) / SAMPLE_RATE, (win[k][2] - t0 + win[k][3]) / SAMPLE_RATE)} for k in ks]
+        if speech is not None:
+            for c, k in zip(chunks, ks):
+                c["speech_s"] = speech[k]
         res = {"text": join_texts([texts[k] for k in ks]), "chunks": chunks}
         if return_timestamps:
             res["words"] = [w for k in ks for w in words[k]]

@@ -890,6 +890,79 @@ def wave_windows(wav, start, length, Ls, out=None):
     return out, lens
 
 
+# ----------------------------------------------------------------------------- voice activity detection (csrc/vad.hip)
+VAD_LIMITS = {"recordings": 64, "samples": 160 * 1048576, "smooth": 8, "noise_window": 1024}      # TA_CUT_* / TA_VAD_* of include/ta355.h
+VAD_HOP = 256
+VAD_TILE = 256                 # frames per workgroup of the statistic kernel (TA_VAD_TILE)
+VAD_ENERGY_FRAMES = 32         # frames per workgroup of the band-energy kernel (TA_VAD_ENERGY_FRAMES)
+
+
+def vad_frames(n: int) -> int:
+    """ta_vad_frames: the frames i >= 0 with 256 i < n - 256 -- ``len(range(0, n - 256, 256))``, the diarizer's loop count."""
+    n = int(n)
+    return 0 if n <= VAD_HOP else (n - 1) // VAD_HOP
+
+
+def check_vad_options(smooth, noise_window, noise_bias, threshold, floor):
+    """The ranges of ``ta_vad_options`` -> (h, W, beta, theta, e0) or ``ValueError``."""
+    import math
+    h, W, beta, theta, e0 = int(smooth), int(noise_window), float(noise_bias), float(threshold), float(floor)
+    if not 0 <= h <= VAD_LIMITS["smooth"]:
+        raise ValueError(f"vad: smooth must be within [0, {VAD_LIMITS['smooth']}] frames; got {smooth}")
+    if not 1 <= W <= VAD_LIMITS["noise_window"]:
+        raise ValueError(f"vad: noise_window must be within [1, {VAD_LIMITS['noise_window']}] frames; got {noise_window}")
+    if not (math.isfinite(beta) and beta >= 1.0):
+        raise ValueError(f"vad: noise_bias must be finite and >= 1; got {noise_bias}")
+    if not (math.isfinite(theta) and theta > 0.0):
+        raise ValueError(f"vad: threshold must be finite and > 0; got {threshold}")
+    if not (math.isfinite(e0) and e0 > 0.0 and float(torch.tensor(e0, dtype=F32)) > 0.0):
+        raise ValueError(f"vad: floor must be finite and > 0 in f32; got {floor}")
+    return h, W, beta, theta, e0
+
+
+def vad(wav, offsets, max_samples, smooth=2, noise_window=94, noise_bias=2.0, threshold=0.15, floor=1e-12, stat=None, flags=None):
+    """ta_vad_f32: ``wav`` flat f32 (device), ``offsets`` int64 [R + 1] (device; recording r is wav[offsets[r]:offsets[r + 1]], at any
+    sample offset), ``max_samples`` >= every recording's length -> (stat f32 [R, ld] = the likelihood-ratio statistic L, flags uint8
+    [R, ld] = L > threshold, n_frames int32 [R]) with ld = vad_frames(max_samples); row r is written for its own
+    ``vad_frames(n_r)`` frames, the rest keeps its zeros.  ``stat`` / ``flags`` may be passed in ([R, ld >= vad_frames(max_samples)],
+    contiguous): positions the kernel does not write keep what they held."""
+    if not (wav.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("vad needs the recordings on a HIP device: there is no CPU path")
+    if wav.dim() != 1 or offsets.dim() != 1:
+        raise ValueError(f"vad: wav must be one flat 1-D buffer and offsets 1-D; got {tuple(wav.shape)} and {tuple(offsets.shape)}")
+    assert wav.dtype == F32 and wav.is_contiguous(), "wav: one flat contiguous f32 buffer"
+    assert offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.device == wav.device
+    R, max_samples = offsets.numel() - 1, int(max_samples)
+    if R < 0 or R > VAD_LIMITS["recordings"]:
+        raise ValueError(f"vad: {R} recordings, the kernels take at most {VAD_LIMITS['recordings']} per call")
+    if max_samples < 1:
+        raise ValueError("vad: max_samples must be at least 1")
+    if max_samples > VAD_LIMITS["samples"]:
+        raise ValueError(f"vad: {max_samples} samples are beyond the kernel's limit of {VAD_LIMITS['samples']} "
+                         f"({VAD_LIMITS['samples'] / 16000 / 3600:.1f} h at 16 kHz)")
+    h, W, beta, theta, e0 = check_vad_options(smooth, noise_window, noise_bias, threshold, floor)
+    dev, maxF = wav.device, vad_frames(max_samples)
+    if stat is None:
+        stat = torch.zeros((R, maxF), device=dev, dtype=F32)
+    if flags is None:
+        flags = torch.zeros((R, stat.shape[1] if stat.dim() == 2 else maxF), device=dev, dtype=torch.uint8)
+    if stat.dim() != 2 or stat.shape[0] != R or stat.shape[1] < maxF or flags.shape != stat.shape:
+        raise ValueError(f"vad: stat is {tuple(stat.shape)} and flags {tuple(flags.shape)}: {R} recordings of up to {maxF} frames need "
+                         f"two [{R}, ld >= {maxF}] buffers of one shape")
+    assert stat.dtype == F32 and flags.dtype == torch.uint8 and stat.is_contiguous() and flags.is_contiguous()
+    assert stat.device == dev and flags.device == dev
+    n_frames = torch.zeros(R, device=dev, dtype=torch.int32)
+    if R == 0:
+        return stat, flags, n_frames
+    L = lib()
+    ws_bytes = L.ta_vad_workspace_bytes(R, max_samples)
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    opt = _lib.VadOptions(h, W, beta, theta, e0)
+    check(L.ta_vad_f32(ptr(wav), ptr(offsets), R, max_samples, C.byref(opt), ptr(stat), ptr(flags), stat.shape[1], ptr(n_frames),
+                       ptr(ws), ws_bytes, stream()), "ta_vad_f32")
+    return stat, flags, n_frames
+
+
 # ----------------------------------------------------------------------------- decoding scores (csrc/generate.hip)
 MAX_TOP_LOGPROBS = 8      # the per-lane candidate list of token_scores_kernel
 

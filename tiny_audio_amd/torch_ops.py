@@ -12,6 +12,8 @@ reference has no FFI; its seams are nn.Module boundaries,
                                scripts/eval/evaluators/base.py:114,150, scripts/eval/evaluators/alignment.py:12-79
     ta355::wave_cut_cost, cut_plan, wave_windows   long-form transcription: where to cut a recording and the cut itself; the reference
                                keeps the first chunk only   tiny_audio/asr_pipeline.py:243-245
+    ta355::vad                 TenVad.process, one 256-sample frame per call (a statistical detector of this project's own, not that
+                               model)   tiny_audio/diarization.py:370-387
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
     ta355::wav2vec2_sln_emissions  the same seam with a layer-norm / stable wav2vec2 (large-lv60, XLSR-53, XLS-R 300M, MMS 300M), which
                                the reference's align(..., _language=...) placeholder stands for   tiny_audio/alignment.py:182-211
@@ -254,6 +256,24 @@ def wave_windows(wav: Tensor, start: Tensor, length: Tensor, Ls: int) -> Tuple[T
 def _(wav, start, length, Ls):
     W = start.shape[0]
     return wav.new_empty((W, Ls)), start.new_empty((W,))
+
+
+# ============================================================================ voice activity detection
+@torch.library.custom_op("ta355::vad", mutates_args=())
+def vad(wav: Tensor, offsets: Tensor, max_samples: int, smooth: int, noise_window: int, noise_bias: float, threshold: float,
+        floor: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """wav flat f32, offsets i64 [R + 1] -> (stat f32 [R, F_max] = the band-wise likelihood-ratio statistic of every 256-sample frame
+    against a minimum-statistics noise floor, flags u8 [R, F_max] = stat > threshold, n_frames i32 [R]) with F_max =
+    (max_samples - 1) // 256 (0 up to 256 samples); zeros beyond a recording's own frames (``ops.vad``).  No autograd: the waveform
+    is data."""
+    from . import ops
+    return ops.vad(wav, offsets, max_samples, smooth, noise_window, noise_bias, threshold, floor)
+
+
+@vad.register_fake
+def _(wav, offsets, max_samples, smooth, noise_window, noise_bias, threshold, floor):
+    R, F = offsets.shape[0] - 1, (0 if max_samples <= 256 else (max_samples - 1) // 256)
+    return wav.new_empty((R, F)), wav.new_empty((R, F), dtype=torch.uint8), wav.new_empty((R,), dtype=torch.int32)
 
 
 # ============================================================================ decoding scores
@@ -843,4 +863,4 @@ OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backwa
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
              "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long", "beam_logprobs", "beam_topk",
              "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows", "text_align",
-             "wav2vec2_sln_emissions")
+             "wav2vec2_sln_emissions", "vad")
