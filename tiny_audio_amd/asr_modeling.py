@@ -10,6 +10,7 @@ There is no CPU path: without libta355.so / a GPU every entry point raises.
 """
 from __future__ import annotations
 
+import contextlib
 from collections.abc import Mapping
 from typing import Iterator, Optional
 
@@ -18,11 +19,23 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .asr_config import ASRConfig, WhisperEncoderConfig, compute_encoder_output_length
+from .decoding import check_decay_window
 from .encoder import GlmAsrEncoderMI355X
 from .whisper_encoder import WhisperEncoderMI355X
 from .language_model import NO_NORM_FULL_FT, FrozenLMLoss, Qwen3MI355X, check_loss_options
 from .ops import F32
 from .projectors import PROJECTOR_CLASSES
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """``model.eval()`` inside the block; the mode it had comes back on every way out (a generator closed early included)."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
 
 
 class CausalLMOutput(dict):
@@ -735,9 +748,7 @@ class ASRModel(nn.Module):
         if decay is not None and eos_ids:
             if not isinstance(decay, (tuple, list)) or len(decay) != 2:
                 raise ValueError(f"`exponential_decay_length_penalty` has to be a (start_index, decay_factor) pair, but is {decay}")
-            if min_new > int(decay[0]):
-                raise ValueError(f"min_new_tokens ({min_new}) > exponential_decay_length_penalty start ({decay[0]}): HF forms "
-                                 "-inf + inf = NaN on the eos scores in that window; refused")
+            check_decay_window(min_new, decay)
             ops.id_list(eos_ids, V, "eos_token_id")
             out["exponential_decay_length_penalty"] = (int(decay[0]), float(decay[1]))
         for name in ("suppress_tokens", "begin_suppress_tokens"):
@@ -771,17 +782,13 @@ class ASRModel(nn.Module):
         processors and warpers), and the k most probable alternatives of every step -- computed by one more row kernel inside the
         decode step; the [B, V] rows themselves are never kept."""
         top_k = self._check_top_logprobs(top_logprobs)
-        was_training = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             args = self._prepare_generation(input_ids, input_features, audio_attention_mask, attention_mask, system_prompt,
                                             dict(generate_kwargs))
             if not (return_token_scores or top_k):
                 return self.language_model.greedy_decode(**args)
             seq, sc = self.language_model.greedy_decode(**args, token_scores=True, top_logprobs=top_k)
             return GenerationOutput(sequences=seq, **sc)
-        finally:
-            self.train(was_training)
 
     @torch.no_grad()
     def generate_beams(self, input_ids: Optional[torch.Tensor] = None, input_features: Optional[torch.Tensor] = None,
@@ -818,9 +825,7 @@ class ASRModel(nn.Module):
             v = kw.pop(name, None)
             if v is not None and v != 1:
                 raise ValueError(f"{name}: group and constrained beam search are not built")
-        was_training = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             args = self._prepare_generation(input_ids, input_features, audio_attention_mask, attention_mask, system_prompt, kw, beams=True)
             if len(args["eos_ids"]) > ops.MAX_BEAM_EOS:
                 raise ValueError(f"beam search takes at most {ops.MAX_BEAM_EOS} eos ids; got {args['eos_ids']}")
@@ -829,8 +834,6 @@ class ASRModel(nn.Module):
                                                   use_graph=use_graph, return_trace=bool(return_beam_trace))
             res = GenerationOutput(sequences=out[0], sequences_scores=out[1])
             return (res, out[2]) if return_beam_trace else res
-        finally:
-            self.train(was_training)
 
     @torch.no_grad()
     def score(self, input_features: Optional[torch.Tensor] = None, audio_attention_mask: Optional[torch.Tensor] = None, candidates=None, *,
@@ -854,17 +857,13 @@ class ASRModel(nn.Module):
             raise ValueError(f"{len(candidates)} candidate lists for {B} clips")
         V = int(self.language_model.config.vocab_size)
         tab = scoring.build_candidate_table(candidates, self.tokenizer, self.config.eos_token_id, append_eos, vocab_size=V)
-        was_training = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             args = self._prepare_generation(input_ids, input_features, audio_attention_mask, attention_mask, system_prompt, {})
             L, T = args["input_ids"].shape[1], tab["token_ids"].shape[1]
             if L + T > self.language_model.config.max_position_embeddings:
                 raise ValueError(f"prompt ({L}) + candidate tokens ({T}) exceeds max_position_embeddings")
             lp, scores = self.language_model.score_candidates(args["input_ids"], args["src_row"], args["audio"], args["attention_mask"],
                                                               tab["token_ids"], tab["n_tokens"], tab["candidate_clip"], tab["chunks"])
-        finally:
-            self.train(was_training)
         return ScoreOutput(scores=scores, candidate_clip=tab["candidate_clip"], n_tokens=tab["n_tokens"],
                            token_ids=tab["token_ids"] if return_token_scores else None,
                            token_logprobs=lp if return_token_scores else None, n_clips=B)
@@ -894,14 +893,10 @@ class ASRModel(nn.Module):
         turns its flags into speech segments, every chunk gains ``"speech_s"`` (the seconds of those segments inside the window), and a
         window with ``speech_s <= min_speech_s`` is neither gathered nor decoded nor aligned: its text is ``""`` and it has no words."""
         from .longform import transcribe_long
-        was_training = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             return transcribe_long(self, audio, sample_rate, max_window_s=max_window_s, min_window_s=min_window_s, batch_size=batch_size,
                                    return_timestamps=return_timestamps, acoustic_model=acoustic_model, system_prompt=system_prompt,
                                    vad=vad, min_speech_s=min_speech_s, **generate_kwargs)
-        finally:
-            self.train(was_training)
 
     def generate_streaming(self, input_features: torch.Tensor, audio_attention_mask: torch.Tensor,
                            system_prompt: Optional[str] = None, input_ids: Optional[torch.Tensor] = None,
@@ -924,9 +919,7 @@ class ASRModel(nn.Module):
             raise ValueError("generate_streaming needs a tokenizer to produce text (or return_token_ids=True)")
         if int(self._generation_setting("num_beams", 1, {"num_beams": generate_kwargs.get("num_beams")})) != 1:
             raise ValueError("generate_streaming does not take num_beams > 1 (HF: a streamer cannot follow beam search); use generate_beams")
-        was_training = self.training
-        self.eval()
-        try:
+        with _eval_mode(self):
             with torch.no_grad():
                 args = self._prepare_generation(input_ids, input_features, audio_attention_mask, None, system_prompt,
                                                 dict(generate_kwargs))
@@ -960,5 +953,3 @@ class ASRModel(nn.Module):
                 tail = gate.flush()
                 if tail:
                     yield tail
-        finally:
-            self.train(was_training)
