@@ -1416,6 +1416,60 @@ long ta_vad_workspace_bytes(int R, long max_n);
 int ta_vad_f32(const float* wav, const long* offsets, int R, long max_n, const ta_vad_options* opt, float* stat, unsigned char* flags,
                long ld, int* n_frames, void* ws, long ws_bytes, hipStream_t st);
 
+/* ---- speaker turns: window labels -> frame votes -> runs -> merged turns, and words -> turns, for R recordings per call
+ * (tiny_audio_amd/csrc/speaker_post.hip; driven by tiny_audio_amd/diarization.py).  The reference does this stage in Python loops on the
+ * host: one loop over the 10 ms voting grid, one over the runs, one over words x segments.  Contract: DESIGN.md section 3, "Speaker
+ * turns"; the definition is the host functions of tiny_audio_amd/diarization.py (pinned on tests/golden/diarization.json), restated in
+ * integer frames by tests/speaker_post_ref.py.  Every time of the reference's output is f * voting_rate for an integer frame f, so runs
+ * and turns are (speaker, f0, f1) in int32 and the caller forms f * voting_rate; the votes are exact integers; the VAD index and the merge
+ * rules are float64 evaluated as Python evaluates them (a * r - b * r with two roundings, an IEEE divide, truncation toward zero):
+ * the source is compiled without contraction and without fast-math, and takes no integer shortcut.
+ * Ragged layout: item k of recording r lies at cu[r] + k of the flat arrays, cu int32 [R + 1] on the device.
+ *
+ * ta_spk_vote_i32 (tiny_audio/diarization.py:520-537 _resample_vad, tiny_audio/diarization.py:539-614 _postprocess_segments): windows
+ *   first / last / label int32 [sum_windows] (cu_win; label in [0, S) after the caller's rank mapping) vote on the frames
+ *   [first, min(last, n_frames[r])) of recording r when first < last; any order, overlapping, empty or beyond the grid.  The owner of
+ *   frame f is -1 when its largest count is 0 or flags[clip((long)((f * voting_rate) / vad_frame_s), 0, n_vad[r] - 1)] is 0 (vad
+ *   unsigned char [R, ld_vad] as ta_vad_f32 writes it; n_vad[r] <= 0 silences the recording), else the lowest speaker among the largest
+ *   counts.  A run is a maximal stretch of one owner != -1, f1 the first frame of the next owner or n_frames[r].  Runs in ascending time
+ *   at run_spk / run_f0 / run_f1 [cu_cap[r] ..), n_runs[r] of them; positions beyond n_runs[r] are not written.  status[r]: 0, or 1 when
+ *   the runs do not fit cu_cap[r + 1] - cu_cap[r] (the first that fit are written, nothing beyond), or 2 for n_frames[r] outside
+ *   [0, max_frames] (no runs) or a window with first < 0 or a label outside [0, S) (that window does not vote; the reference's slice would
+ *   wrap a negative start around: a documented divergence, refused by the Python layer).  2 sum_windows + VAD transitions + 2 runs always fit.
+ *   One memset and three launches (integer atomics on a difference array per speaker, whose order cannot change the result; a scan
+ *   fused with the arg-max, the VAD read and the boundary flags, TA_SPK_FRAME_TILE frames per workgroup; a compaction).
+ * ta_spk_merge_i32 (tiny_audio/diarization.py:616-643 _merge_short_segments): for every run in order, start = f0 * voting_rate,
+ *   end = f1 * voting_rate, short = (end - start) < min_segment_s, near = short ? short_gap_s : same_gap_s; a run of the last kept turn's
+ *   speaker with start - that turn's end < near extends it, any other run that is not short is appended, a short one is dropped.  Turns at
+ *   seg_* [cu_run[r] ..) (at most as many as runs), n_seg[r]; the runs need not come from ta_spk_vote_i32.  Recording r has
+ *   cu_run[r + 1] - cu_run[r] runs, or with n_run (int32 [R], may be NULL) the first n_run[r] of that range: ta_spk_vote_i32's n_runs
+ *   and cu_cap go in as they are, without a visit to the host in between.  One workgroup per recording, runs staged through LDS, one
+ *   lane walks them.
+ * ta_spk_words_f64 (tiny_audio/diarization.py:645-682 assign_speakers_to_words): mid = (word_start + word_end) / 2; out[w] = the lowest
+ *   segment index g of the recording (counted from cu_seg[r]) with seg_start[g] <= mid <= seg_end[g], else the lowest g that minimises
+ *   fabs(mid - (seg_start[g] + seg_end[g]) / 2), else -1 (no segments).  Segments in any order, overlapping allowed.  Brute force:
+ *   16 lanes per word, segments staged through LDS TA_SPK_SEG_TILE at a time.  max_words bounds every recording's word count.
+ * Limits (TA_ERR_ARG beyond them): R <= TA_SPK_MAX_RECORDINGS, 1 <= S <= TA_SPK_MAX_SPEAKERS, max_frames <= TA_SPK_MAX_FRAMES (the voting
+ * grid of 2.9 h), sum_windows and max_words <= TA_SPK_MAX_ITEMS, every option finite and > 0.  Values that live on the device (labels,
+ * first, word and segment times) are checked by the Python layer before they are uploaded.
+ * ws: ta_spk_post_workspace_bytes(R, S, max_frames, sum_windows) bytes, no initial contents required; -1 for sizes that are refused. */
+#define TA_SPK_MAX_RECORDINGS 64
+#define TA_SPK_MAX_SPEAKERS 16
+#define TA_SPK_MAX_FRAMES 1048577
+#define TA_SPK_MAX_ITEMS 1048576
+#define TA_SPK_FRAME_TILE 1024
+#define TA_SPK_SEG_TILE 1024
+typedef struct { double voting_rate, vad_frame_s, min_segment_s, short_gap_s, same_gap_s; } ta_spk_post_options;
+long ta_spk_post_workspace_bytes(int R, int S, long max_frames, long sum_windows);
+int ta_spk_vote_i32(const int* first, const int* last, const int* label, const int* cu_win, long sum_windows, int R, int S,
+                    const int* n_frames, long max_frames, const unsigned char* vad, long ld_vad, const int* n_vad,
+                    const ta_spk_post_options* opt, const int* cu_cap, int* run_spk, int* run_f0, int* run_f1, int* n_runs, int* status,
+                    void* ws, long ws_bytes, hipStream_t st);
+int ta_spk_merge_i32(const int* run_spk, const int* run_f0, const int* run_f1, const int* cu_run, const int* n_run, int R,
+                     const ta_spk_post_options* opt, int* seg_spk, int* seg_f0, int* seg_f1, int* n_seg, hipStream_t st);
+int ta_spk_words_f64(const double* word_start, const double* word_end, const int* cu_word, const double* seg_start, const double* seg_end,
+                     const int* cu_seg, int R, long max_words, int* out, hipStream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ HEADER = os.path.join(ROOT, "include", "ta355.h")
 CSRC = os.path.join(HERE, "csrc")
 SO_PATH = os.path.join(HERE, "libta355.so")
 SOURCES = ["gemm.hip", "gemm_tn.hip", "norm.hip", "attention.hip", "attention_extend.hip", "attention_enc.hip", "qkv_post.hip", "elementwise.hip", "loss.hip",
-           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "beam.hip", "decode_fused.hip", "augment.hip", "align.hip", "align_long.hip", "text_align.hip", "wav2vec2.hip", "ecapa.hip", "cluster.hip", "segment.hip", "vad.hip", "api.hip"]
+           "logmel.hip", "optim.hip", "moe.hip", "lora.hip", "nn_prims.hip", "generate.hip", "beam.hip", "decode_fused.hip", "augment.hip", "align.hip", "align_long.hip", "text_align.hip", "wav2vec2.hip", "ecapa.hip", "cluster.hip", "segment.hip", "vad.hip", "speaker_post.hip", "api.hip"]
 
 
 class Ta355Error(RuntimeError):
@@ -143,6 +143,11 @@ class CeOptions(C.Structure):
 class VadOptions(C.Structure):
     """ta_vad_options (include/ta355.h): smoothing half-width, noise window, noise bias, threshold, floor."""
     _fields_ = [("smooth", C.c_int), ("noise_window", C.c_int), ("noise_bias", C.c_float), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
+class SpkPostOptions(C.Structure):
+    """ta_spk_post_options (include/ta355.h): the voting grid, the VAD frame, and the three merge thresholds, in seconds."""
+    _fields_ = [(n, C.c_double) for n in ("voting_rate", "vad_frame_s", "min_segment_s", "short_gap_s", "same_gap_s")]
 
 
 class LmLayerWgrads(C.Structure):

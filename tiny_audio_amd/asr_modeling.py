@@ -871,7 +871,9 @@ class ASRModel(nn.Module):
     @torch.no_grad()
     def transcribe_long(self, audio, sample_rate: int = 16000, *, max_window_s: float = 28.0, min_window_s: float = 10.0,
                         batch_size: int = 32, return_timestamps: bool = False, acoustic_model=None,
-                        system_prompt: Optional[str] = None, vad=None, min_speech_s: float = 0.0, **generate_kwargs):
+                        system_prompt: Optional[str] = None, vad=None, min_speech_s: float = 0.0, return_speakers: bool = False,
+                        speaker_model=None, num_speakers: Optional[int] = None, min_speakers: Optional[int] = None,
+                        max_speakers: Optional[int] = None, cluster_device=None, **generate_kwargs):
         """A whole 16 kHz recording -> ``{"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}`` (``audio``: a 1-D array or
         tensor; a list of them returns a list of results).  The reference keeps a long recording's first chunk only
         (tiny_audio/asr_pipeline.py:243-245); this transcribes all of it, up to 2.9 h per recording (``tiny_audio_amd/longform.py``).
@@ -891,12 +893,21 @@ class ASRModel(nn.Module):
 
         ``vad=`` (a ``vad.DeviceVAD``; opt-in, None changes nothing): the detector runs on the uploaded buffer, the diarizer's hysteresis
         turns its flags into speech segments, every chunk gains ``"speech_s"`` (the seconds of those segments inside the window), and a
-        window with ``speech_s <= min_speech_s`` is neither gathered nor decoded nor aligned: its text is ``""`` and it has no words."""
+        window with ``speech_s <= min_speech_s`` is neither gathered nor decoded nor aligned: its text is ``""`` and it has no words.
+
+        ``return_speakers=True`` (implies ``return_timestamps=True``, as tiny_audio/asr_pipeline.py:100-101; needs ``acoustic_model``,
+        ``speaker_model`` -- an ``ecapa.EcapaTdnnMI355X`` -- and ``vad``, each a ``ValueError`` when missing): the same flags feed the
+        diarizer on the uploaded buffer (``num_speakers`` / ``min_speakers`` / ``max_speakers`` / ``cluster_device`` as
+        ``SpeakerDiarizer.diarize`` takes them), every result gains ``"speaker_segments"`` [{'speaker', 'start', 'end'}] (``[]`` for a
+        recording without speech) and every word ``"speaker"`` (None without segments); voting, merging and the words' speakers are one
+        launch each for all recordings (``spk_vote``, ``spk_merge``, ``spk_words``)."""
         from .longform import transcribe_long
         with _eval_mode(self):
             return transcribe_long(self, audio, sample_rate, max_window_s=max_window_s, min_window_s=min_window_s, batch_size=batch_size,
                                    return_timestamps=return_timestamps, acoustic_model=acoustic_model, system_prompt=system_prompt,
-                                   vad=vad, min_speech_s=min_speech_s, **generate_kwargs)
+                                   vad=vad, min_speech_s=min_speech_s, return_speakers=return_speakers, speaker_model=speaker_model,
+                                   num_speakers=num_speakers, min_speakers=min_speakers, max_speakers=max_speakers,
+                                   cluster_device=cluster_device, **generate_kwargs)
 
     def generate_streaming(self, input_features: torch.Tensor, audio_attention_mask: torch.Tensor,
                            system_prompt: Optional[str] = None, input_ids: Optional[torch.Tensor] = None,

@@ -6,8 +6,9 @@ tiny_audio/asr_pipeline.py:133-152): the same class names, class constants, argu
 differs is the hot path.  The reference pushes every 0.75 s window through SpeechBrain's ``encode_batch`` one window per call
 (tiny_audio/diarization.py:490-502); with ``speaker_model=`` (an ``EcapaTdnnMI355X``) every window of every segment goes through ONE
 ``embed_windows`` call on the device -- the audio is uploaded once and the windows are cut and reflect-padded by the feature kernel.
-Voting and merging behind the ``[N, 192]`` embeddings are O(N) host arithmetic and stay in numpy, scipy and scikit-learn exactly as the
-reference has them.  Spectral clustering is not: ``SpectralCluster`` restates the reference's dense float64 affinity, Laplacian and full
+Voting and merging behind the ``[N, 192]`` embeddings are host loops in numpy and plain Python exactly as the reference has them --
+fine for a 30 s clip, a million interpreted steps at the long-form cap; ``post_device=`` (and ``device=`` of the three functions) runs
+the same rules as HIP kernels for ragged batches of recordings, with the same lists as result (csrc/speaker_post.hip).  Spectral clustering is not: ``SpectralCluster`` restates the reference's dense float64 affinity, Laplacian and full
 ``scipy.linalg.eigh`` -- O(N^2) memory and O(N^3) time, seconds at N = 4 000 windows (10 minutes of speech) and tens of minutes at an
 hour.  It stays the default; ``cluster_device=`` (``SpeakerClusterer(device=...)``) moves the affinity, the Laplacian and the few
 eigenpairs that are read onto the device (``tiny_audio_amd/spectral.py``) and leaves the eigengap rule, k-means and merging here.
@@ -203,10 +204,12 @@ class LocalSpeakerDiarizer:
     # ------------------------------------------------------------------ the pipeline
     @classmethod
     def diarize(cls, audio, sample_rate: int = 16000, num_speakers: int | None = None, min_speakers: int = 2, max_speakers: int = 10,
-                *, speaker_model=None, speech_frames=None, vad=None, cluster_device=None, **_kwargs) -> list[dict]:
+                *, speaker_model=None, speech_frames=None, vad=None, cluster_device=None, post_device=None, **_kwargs) -> list[dict]:
         """audio: a waveform array or the path of an audio file -> ``[{"speaker": "SPEAKER_k", "start": s, "end": s}, ...]``.
 
         cluster_device: a torch device for the spectral clustering (``SpeakerClusterer(device=...)``); None keeps it on the host.
+        post_device: a torch device for the voting and the merging behind the labels (``spk_vote``, ``spk_merge``; the same lists);
+            None keeps the reference's loops here.  With a ``vad.DeviceVAD`` its decisions stay on the device for the voting.
 
         speaker_model: an ``EcapaTdnnMI355X``; every window of every segment goes through one ``embed_windows`` call.  Without it
             SpeechBrain runs through PyTorch one window per call, as in the reference.
@@ -221,6 +224,10 @@ class LocalSpeakerDiarizer:
             audio = librosa.resample(audio, orig_sr=sample_rate, target_sr=16000)
             sample_rate = 16000
         audio = audio.astype(np.float32)
+        if post_device is not None:
+            return cls.diarize_batch([audio], sample_rate, num_speakers, min_speakers, max_speakers, speaker_model=speaker_model,
+                                     speech_frames=None if speech_frames is None else [speech_frames], vad=vad,
+                                     cluster_device=cluster_device, post_device=post_device)[0]
         total_duration = len(audio) / sample_rate
         segments, vad_frames = cls._get_speech_segments(audio, sample_rate, speech_frames=speech_frames, vad=vad)
         if not segments:
@@ -230,6 +237,45 @@ class LocalSpeakerDiarizer:
             return []
         labels = SpeakerClusterer(min_num_spks=min_speakers, max_num_spks=max_speakers, device=cluster_device)(embeddings, num_speakers)
         return cls._postprocess_segments(window_segments, labels, total_duration, vad_frames)
+
+    @classmethod
+    def diarize_batch(cls, audios, sample_rate: int = 16000, num_speakers: int | None = None, min_speakers: int = 2, max_speakers: int = 10,
+                      *, speaker_model=None, speech_frames=None, vad=None, cluster_device=None, post_device=None) -> list[list[dict]]:
+        """``diarize`` of several 16 kHz waveform arrays -> one list of turns per recording.  VAD, embeddings and clustering run per
+        recording as in ``diarize``; with ``post_device`` the voting and merging of ALL recordings is one ``spk_vote`` and one
+        ``spk_merge`` launch, and a ``vad.DeviceVAD`` runs once on one upload of all recordings, its decisions staying on the device
+        for the voting.  speech_frames: None, or one list of decisions per recording."""
+        if sample_rate != 16000:
+            raise ValueError(f"diarize_batch takes 16 kHz arrays, got sample_rate={sample_rate}: resample first")
+        audios = [np.asarray(a).astype(np.float32) for a in audios]
+        if speech_frames is not None and len(speech_frames) != len(audios):
+            raise ValueError(f"speech_frames holds {len(speech_frames)} lists for {len(audios)} recordings")
+        vad_device, flags_h = None, None
+        if post_device is not None and speech_frames is None and vad is not None and hasattr(vad, "speech_frames_uploaded") and audios:
+            from .longform import upload
+            flat, offsets, lens = upload(audios, post_device)
+            flags_h, flags_d, n_vad = vad.speech_frames_uploaded(flat, offsets, lens)
+            vad_device = (flags_d, n_vad)
+        items = []
+        for r, audio in enumerate(audios):
+            total_duration = len(audio) / sample_rate
+            if flags_h is not None:
+                from .vad import segments_from_flags
+                segments, vad_frames = segments_from_flags(flags_h[r], sample_rate), flags_h[r].tolist()
+            else:
+                segments, vad_frames = cls._get_speech_segments(audio, sample_rate, vad=vad,
+                                                                speech_frames=None if speech_frames is None else speech_frames[r])
+            windows, labels = [], []
+            if segments:
+                embeddings, window_segments = cls._extract_embeddings(audio, segments, sample_rate, speaker_model=speaker_model)
+                if len(embeddings):
+                    labels = SpeakerClusterer(min_num_spks=min_speakers, max_num_spks=max_speakers, device=cluster_device)(embeddings,
+                                                                                                                          num_speakers)
+                    windows = window_segments
+            items.append((windows, labels, total_duration, vad_frames))
+        if post_device is None:
+            return [cls._postprocess_segments(*it) for it in items]
+        return cls.postprocess_batch(items, post_device, vad_device=vad_device)
 
     @classmethod
     def _get_speech_segments(cls, audio_array: np.ndarray, sample_rate: int = 16000, *, speech_frames=None, vad=None):
@@ -342,6 +388,47 @@ class LocalSpeakerDiarizer:
         return speaker_model.embed_windows(buf, starts, lengths, window).cpu().numpy()
 
     @classmethod
+    def extract_embeddings_uploaded(cls, flat, offsets, lens, segments_per_recording, speaker_model, sample_rate: int = 16000):
+        """``_extract_embeddings`` of several recordings that lie in one uploaded buffer (``longform.upload``: recording r at
+        ``flat[offsets[r] : offsets[r] + lens[r]]``) -> per recording (row-normalised embeddings [N, D], the kept windows).  Every
+        window the feature kernel can reflect by itself is read from ``flat`` in ONE ``embed_windows`` call; the few chunks too short
+        for a single reflection are fetched, padded here as ``np.pad`` pads them, and go through a second call."""
+        from sklearn.preprocessing import normalize
+        spans_of, where, starts, lengths, extra, window = [], [], [], [], [], int(cls.WINDOW_SIZE * sample_rate)
+        for r, segs in enumerate(segments_per_recording):
+            window, spans = cls._window_positions(segs, sample_rate)
+            base, n = int(offsets[r]), int(lens[r])
+            spans_of.append(spans)
+            for lo, hi in spans:
+                if lo < 0:
+                    raise ValueError(f"recording {r}: a window starts at sample {lo}")
+                have = max(0, min(hi, n) - lo)
+                if window - have <= have - 1:
+                    where.append((0, len(starts)))
+                    starts.append(base + lo), lengths.append(have)
+                else:
+                    chunk = flat[base + lo:base + lo + have].detach().cpu().numpy()
+                    where.append((1, len(extra)))
+                    extra.append(np.pad(chunk, (0, window - len(chunk)), mode="reflect"))
+        raw = [None, None]
+        if starts:
+            raw[0] = speaker_model.embed_windows(flat, starts, lengths, window).cpu().numpy()
+        if extra:
+            raw[1] = speaker_model.embed_windows(np.concatenate(extra), [i * window for i in range(len(extra))], [window] * len(extra),
+                                                 window).cpu().numpy()
+        out, k = [], 0
+        for spans in spans_of:
+            embeddings, windows = [], []
+            for lo, hi in spans:
+                e = raw[where[k][0]][where[k][1]]
+                k += 1
+                if np.isfinite(e).all() and np.linalg.norm(e) > 1e-8:
+                    embeddings.append(e)
+                    windows.append({"start": lo / sample_rate, "end": hi / sample_rate})
+            out.append((normalize(np.array(embeddings)), windows) if embeddings else (np.array([]), []))
+        return out
+
+    @classmethod
     def _resample_vad(cls, vad_frames: list[bool], num_frames: int) -> np.ndarray:
         """The 16 ms VAD decisions on the VOTING_RATE grid: voting frame f takes VAD frame ``int(f * VOTING_RATE / 0.016)``, clipped."""
         if not vad_frames:
@@ -351,9 +438,13 @@ class LocalSpeakerDiarizer:
         return decisions[at]
 
     @classmethod
-    def _postprocess_segments(cls, window_segments: list[dict], labels: np.ndarray, total_duration: float, vad_frames: list[bool]):
+    def _postprocess_segments(cls, window_segments: list[dict], labels: np.ndarray, total_duration: float, vad_frames: list[bool],
+                              device=None):
         """Frame-level voting: every window votes for its speaker on the frames it covers; a frame without votes or without speech
-        is silence; runs of one speaker become segments."""
+        is silence; runs of one speaker become segments.  ``device``: a torch device -- the same lists from ``spk_vote`` and
+        ``spk_merge`` (``postprocess_batch``); None -- the reference's loops over the frames and the runs, here."""
+        if device is not None:
+            return cls.postprocess_batch([(window_segments, labels, total_duration, vad_frames)], device)[0]
         if not window_segments or len(labels) == 0:
             return []
         speakers = np.unique(labels)
@@ -380,9 +471,13 @@ class LocalSpeakerDiarizer:
         return cls._merge_short_segments(out)
 
     @classmethod
-    def _merge_short_segments(cls, segments: list[dict]) -> list[dict]:
+    def _merge_short_segments(cls, segments: list[dict], device=None) -> list[dict]:
         """A segment under MIN_SEGMENT_DURATION extends a same-speaker predecessor closer than SHORT_SEGMENT_GAP or is dropped; any
-        other segment extends a same-speaker predecessor closer than SAME_SPEAKER_GAP or starts a new entry."""
+        other segment extends a same-speaker predecessor closer than SAME_SPEAKER_GAP or starts a new entry.  ``device``: ``spk_merge``
+        on that device, which takes turns on the voting grid (what ``_postprocess_segments`` makes): every time is snapped to its
+        frame f and stands for ``f * VOTING_RATE``; one further than a microsecond from the grid is a ``ValueError``."""
+        if device is not None:
+            return cls._merge_on_device(segments, device)
         if not segments:
             return []
         out: list[dict] = []
@@ -396,9 +491,11 @@ class LocalSpeakerDiarizer:
         return out
 
     @classmethod
-    def assign_speakers_to_words(cls, words: list[dict], speaker_segments: list[dict]) -> list[dict]:
+    def assign_speakers_to_words(cls, words: list[dict], speaker_segments: list[dict], device=None) -> list[dict]:
         """Adds ``"speaker"`` to every word: the first segment that contains the word's midpoint, else the segment whose midpoint is
-        nearest (the first of equals), else None."""
+        nearest (the first of equals), else None.  ``device``: one ``spk_words`` launch instead of words x segments steps here."""
+        if device is not None:
+            return cls.assign_speakers_batch([(words, speaker_segments)], device)[0]
         for word in words:
             mid = (word["start"] + word["end"]) / 2
             speaker = next((s["speaker"] for s in speaker_segments if s["start"] <= mid <= s["end"]), None)
@@ -406,6 +503,155 @@ class LocalSpeakerDiarizer:
                 speaker = min(speaker_segments, key=lambda s: abs(mid - (s["start"] + s["end"]) / 2))["speaker"]
             word["speaker"] = speaker
         return words
+
+    # ------------------------------------------------------------------ the same stage on the device (csrc/speaker_post.hip)
+    @classmethod
+    def spk_options(cls) -> tuple:
+        """``ta_spk_post_options`` from the class attributes, so that a subclass that overrides them is honoured."""
+        return (cls.VOTING_RATE, VAD_HOP / 16000, cls.MIN_SEGMENT_DURATION, cls.SHORT_SEGMENT_GAP, cls.SAME_SPEAKER_GAP)
+
+    @classmethod
+    def turns_from_frames(cls, spk, f0, f1, names) -> list[dict]:
+        """Integer frames -> the reference's dicts: every time is ``f * VOTING_RATE``, formed here exactly as the frame loop forms it."""
+        return [{"speaker": names[int(k)], "start": int(a) * cls.VOTING_RATE, "end": int(b) * cls.VOTING_RATE}
+                for k, a, b in zip(spk, f0, f1)]
+
+    @classmethod
+    def vote_inputs(cls, window_segments, labels, total_duration):
+        """One recording's windows on the voting grid -> (first int32 [Nw], last int32 [Nw], rank int32 [Nw], names, num_frames): the
+        host's share of ``_postprocess_segments`` as one numpy expression each -- ``int(start / VOTING_RATE)``,
+        ``min(int(end / VOTING_RATE), num_frames)`` and the rank of every label among ``np.unique(labels)``."""
+        from .ops import SPK_LIMITS
+        labels = np.asarray(labels)
+        speakers = np.unique(labels)
+        n = min(len(window_segments), len(labels))                  # zip() stops at the shorter
+        num_frames = int(np.ceil(total_duration / cls.VOTING_RATE)) + 1
+        if not 1 <= num_frames <= SPK_LIMITS["frames"]:
+            raise ValueError(f"{total_duration} s are {num_frames} voting frames, beyond the limit of {SPK_LIMITS['frames']} per recording")
+        if len(speakers) > SPK_LIMITS["speakers"]:
+            raise ValueError(f"{len(speakers)} speakers, the voting kernel takes at most {SPK_LIMITS['speakers']}")
+        start = np.array([w["start"] for w in window_segments[:n]], np.float64)
+        end = np.array([w["end"] for w in window_segments[:n]], np.float64)
+        if not (np.isfinite(start).all() and np.isfinite(end).all()):
+            raise ValueError("a window's start or end is not finite")
+        first = (start / cls.VOTING_RATE).astype(np.int64)
+        last = np.minimum((end / cls.VOTING_RATE).astype(np.int64), num_frames)
+        if (first < 0).any():
+            raise ValueError("a window starts before 0 (first >= 0 is required: the reference's slice would wrap a negative start around "
+                             "the grid, which is not rebuilt on the device)")
+        first = np.minimum(first, num_frames)                       # a window beyond the grid votes nowhere; its start fits int32 this way
+        last = np.maximum(last, -1)
+        rank = np.searchsorted(speakers, labels[:n])
+        return first.astype(np.int32), last.astype(np.int32), rank.astype(np.int32), [f"SPEAKER_{k}" for k in range(len(speakers))], num_frames
+
+    @classmethod
+    def postprocess_batch(cls, items, device, vad_device=None, return_frames: bool = False):
+        """``_postprocess_segments`` of several recordings in ONE ``spk_vote`` and ONE ``spk_merge`` launch, and one read-back.
+        items: per recording ``(window_segments, labels, total_duration, vad_frames)``.  vad_device: ``(flags uint8 [R, ld], n_vad
+        int32 [R])`` already on the device, row r for items[r] (what ``DeviceVAD.run_uploaded`` returned): then ``vad_frames`` is read
+        on the host only to bound the number of runs, and nothing is uploaded a second time.  -> the turns per recording (with
+        ``return_frames`` the integer triples ``(spk, f0, f1)`` beside them)."""
+        import torch
+        from . import torch_ops  # noqa: F401  (registers torch.ops.ta355.spk_*)
+        R = len(items)
+        out = [[] for _ in range(R)]
+        frames = [(np.zeros(0, np.int32),) * 3 for _ in range(R)]
+        firsts, lasts, ranks, names, n_frames, n_win, caps, vads = [], [], [], [], [], [], [], []
+        for wins, labels, total_duration, vad_frames in items:
+            live = bool(wins) and len(labels) > 0
+            f, l, k, nm, nf = cls.vote_inputs(wins if live else [], labels if live else [], total_duration)
+            v = np.asarray(vad_frames if vad_frames is not None else [], dtype=bool).reshape(-1)
+            firsts.append(f), lasts.append(l), ranks.append(k), names.append(nm), n_frames.append(nf), n_win.append(len(f)), vads.append(v)
+            # an owner changes only where a window begins or ends or the VAD's decision changes: a bound on the runs, and never more than frames
+            caps.append(0 if not live else min(2 * len(f) + int(np.count_nonzero(v[1:] != v[:-1])) + 2, nf))
+        if R == 0 or not any(n_win):
+            return (out, frames) if return_frames else out
+        dev = torch.device(device)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+        cu = lambda c: i32(np.concatenate([[0], np.cumsum(c)]))  # noqa: E731
+        if vad_device is None:
+            ld = max(1, max(len(v) for v in vads))
+            flags_h = np.zeros((R, ld), np.uint8)
+            for r, v in enumerate(vads):
+                flags_h[r, :len(v)] = v
+            flags, n_vad = torch.from_numpy(flags_h).to(dev), i32([len(v) for v in vads])
+        else:
+            flags, n_vad = vad_device
+            flags = flags if flags.shape[1] > 0 else flags.new_zeros((R, 1))
+        S = max(1, max(len(nm) for nm in names))
+        opts = cls.spk_options()
+        cap, cu_cap = int(sum(caps)), cu(caps)
+        run_spk, run_f0, run_f1, n_runs, status = torch.ops.ta355.spk_vote(
+            i32(np.concatenate(firsts)), i32(np.concatenate(lasts)), i32(np.concatenate(ranks)), cu(n_win), S, i32(n_frames),
+            int(max(n_frames)), flags.contiguous(), n_vad.to(torch.int32).contiguous(), cu_cap, cap, *opts)
+        seg_spk, seg_f0, seg_f1, n_seg = torch.ops.ta355.spk_merge(run_spk, run_f0, run_f1, cu_cap, n_runs, *opts)
+        back = torch.cat([seg_spk, seg_f0, seg_f1, n_seg, status]).cpu().numpy()      # the one read-back
+        spk_h, f0_h, f1_h, n_seg_h, status_h = back[:cap], back[cap:2 * cap], back[2 * cap:3 * cap], back[3 * cap:3 * cap + R], back[3 * cap + R:]
+        if not _dry_run() and status_h.any():
+            raise RuntimeError(f"spk_vote reported status {status_h.tolist()}: the runs did not fit their bound")
+        o = np.concatenate([[0], np.cumsum(caps)])
+        for r in range(R):
+            sl = slice(int(o[r]), int(o[r]) + int(n_seg_h[r]))
+            frames[r] = (spk_h[sl].copy(), f0_h[sl].copy(), f1_h[sl].copy())
+            out[r] = cls.turns_from_frames(*frames[r], names[r])
+        return (out, frames) if return_frames else out
+
+    @classmethod
+    def _merge_on_device(cls, segments: list[dict], device) -> list[dict]:
+        import torch
+        from . import torch_ops  # noqa: F401
+        if not segments:
+            return []
+        names = list(dict.fromkeys(s["speaker"] for s in segments))
+        t = np.array([[s["start"], s["end"]] for s in segments], np.float64)
+        f = np.rint(t / cls.VOTING_RATE)
+        if not np.isfinite(t).all() or (np.abs(f * cls.VOTING_RATE - t) > 1e-6).any() or (f < 0).any() or (f > 2 ** 31 - 1).any():
+            raise ValueError("the device path merges turns on the voting grid: a start or an end lies more than a microsecond from a "
+                             f"multiple of VOTING_RATE = {cls.VOTING_RATE}, or outside int32 frames")
+        dev = torch.device(device)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+        spk = i32([names.index(s["speaker"]) for s in segments])
+        seg_spk, seg_f0, seg_f1, n_seg = torch.ops.ta355.spk_merge(spk, i32(f[:, 0]), i32(f[:, 1]), i32([0, len(segments)]), None,
+                                                                   *cls.spk_options())
+        n = int(n_seg.cpu()[0])
+        return cls.turns_from_frames(seg_spk[:n].cpu().numpy(), seg_f0[:n].cpu().numpy(), seg_f1[:n].cpu().numpy(), names)
+
+    @classmethod
+    def assign_speakers_batch(cls, items, device) -> list:
+        """``assign_speakers_to_words`` of several recordings in ONE ``spk_words`` launch.  items: per recording
+        ``(words, speaker_segments)``; every word gains ``"speaker"`` in place, as the host function does it."""
+        import torch
+        from . import torch_ops  # noqa: F401
+        from .ops import SPK_LIMITS
+        ws = np.array([[w["start"], w["end"]] for words, _ in items for w in words], np.float64).reshape(-1, 2)
+        ss = np.array([[s["start"], s["end"]] for _, segs in items for s in segs], np.float64).reshape(-1, 2)
+        if not (np.isfinite(ws).all() and np.isfinite(ws.sum(1)).all()):
+            raise ValueError("a word's start or end is not finite")
+        if not (np.isfinite(ss).all() and np.isfinite(ss.sum(1)).all()):
+            raise ValueError("a segment's start or end is not finite")
+        for what, n in (("words", len(ws)), ("segments", len(ss))):
+            if n > SPK_LIMITS["items"]:
+                raise ValueError(f"{n} {what}, the kernel takes at most {SPK_LIMITS['items']} per call")
+        if len(items) > SPK_LIMITS["recordings"]:
+            raise ValueError(f"{len(items)} recordings, the kernel takes at most {SPK_LIMITS['recordings']} per call")
+        if len(ws):
+            dev = torch.device(device)
+            f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            cu = lambda c: torch.from_numpy(np.concatenate([[0], np.cumsum(c)]).astype(np.int32)).to(dev)  # noqa: E731
+            idx = torch.ops.ta355.spk_words(f64(ws[:, 0]), f64(ws[:, 1]), cu([len(w) for w, _ in items]), f64(ss[:, 0]), f64(ss[:, 1]),
+                                            cu([len(s) for _, s in items])).cpu().tolist()
+        k = 0
+        for words, segs in items:
+            for w in words:
+                g = idx[k] if segs else -1
+                w["speaker"] = segs[g]["speaker"] if 0 <= g < len(segs) else None
+                k += 1
+        return [words for words, _ in items]
+
+
+def _dry_run() -> bool:
+    from . import _lib
+    return _lib.DRY_RUN
 
 
 class SpeakerDiarizer:
@@ -418,11 +664,16 @@ class SpeakerDiarizer:
     @classmethod
     def diarize(cls, audio, sample_rate: int = 16000, num_speakers: int | None = None, min_speakers: int | None = None,
                 max_speakers: int | None = None, *, speaker_model=None, speech_frames=None, vad=None, cluster_device=None,
-                **_kwargs) -> list[dict]:
+                post_device=None, **_kwargs) -> list[dict]:
         return LocalSpeakerDiarizer.diarize(audio, sample_rate=sample_rate, num_speakers=num_speakers, min_speakers=min_speakers or 2,
                                             max_speakers=max_speakers or 10, speaker_model=speaker_model, speech_frames=speech_frames,
-                                            vad=vad, cluster_device=cluster_device)
+                                            vad=vad, cluster_device=cluster_device, post_device=post_device)
 
     @classmethod
-    def assign_speakers_to_words(cls, words: list[dict], speaker_segments: list[dict]) -> list[dict]:
-        return LocalSpeakerDiarizer.assign_speakers_to_words(words, speaker_segments)
+    def diarize_batch(cls, audios, sample_rate: int = 16000, num_speakers: int | None = None, min_speakers: int | None = None,
+                      max_speakers: int | None = None, **kwargs) -> list[list[dict]]:
+        return LocalSpeakerDiarizer.diarize_batch(audios, sample_rate, num_speakers, min_speakers or 2, max_speakers or 10, **kwargs)
+
+    @classmethod
+    def assign_speakers_to_words(cls, words: list[dict], speaker_segments: list[dict], device=None) -> list[dict]:
+        return LocalSpeakerDiarizer.assign_speakers_to_words(words, speaker_segments, device=device)

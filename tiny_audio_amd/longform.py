@@ -8,6 +8,9 @@ ones), ``ta_cut_plan_f32`` picks the cheapest cuts that keep every window betwee
 decode loop and aligner take (csrc/segment.hip; DESIGN.md section 3, "Long-form transcription").  Only the cut table (a few integers
 per window) visits the host: the prompts are built from it.  With ``vad=`` (a ``vad.DeviceVAD``) the detector runs on the same
 uploaded buffer, its flags are the one further read-back, and a window without speech is neither gathered nor decoded nor aligned.
+With ``return_speakers=True`` the same flags feed the diarizer: the windows' embeddings are read from the uploaded buffer, and the
+voting, the merging and the words' speakers of all recordings are one launch each (csrc/speaker_post.hip; DESIGN.md section 3,
+"Speaker turns").
 """
 from __future__ import annotations
 
@@ -150,7 +153,8 @@ def join_texts(texts: Sequence[str]) -> str:
 
 def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: float = 28.0, min_window_s: float = 10.0, batch_size: int = 32,
                     return_timestamps: bool = False, acoustic_model=None, system_prompt=None, vad=None, min_speech_s: float = 0.0,
-                    **generate_kwargs):
+                    return_speakers: bool = False, speaker_model=None, num_speakers=None, min_speakers=None, max_speakers=None,
+                    cluster_device=None, **generate_kwargs):
     """``ASRModel.transcribe_long`` (documented there)."""
     from .asr_processing import ASRProcessor
     from .eval_text import postprocess_tokens
@@ -158,6 +162,17 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
         raise ValueError(f"transcribe_long takes {SAMPLE_RATE} Hz audio, got sample_rate={sample_rate}: resample first")
     if int(batch_size) < 1:
         raise ValueError(f"batch_size must be at least 1; got {batch_size}")
+    if return_speakers:
+        if acoustic_model is None:
+            raise ValueError("return_speakers=True needs acoustic_model=... (a wav2vec2.Wav2Vec2CtcMI355X): speakers are assigned to "
+                             "words, and word times come from forced alignment of every window")
+        if speaker_model is None or not hasattr(speaker_model, "embed_windows"):
+            raise ValueError("return_speakers=True needs speaker_model=... (an ecapa.EcapaTdnnMI355X): the windows' embeddings are read "
+                             "from the uploaded buffer by its embed_windows")
+        if vad is None:
+            raise ValueError("return_speakers=True needs vad=... (a detector with run_uploaded, such as vad.DeviceVAD()): no default "
+                             "detector is claimed")
+        return_timestamps = True                        # as the reference's pipeline has it (tiny_audio/asr_pipeline.py:100-101)
     if return_timestamps and acoustic_model is None:
         raise ValueError("return_timestamps=True needs acoustic_model=... (a wav2vec2.Wav2Vec2CtcMI355X): word times come from forced "
                          "alignment of every window")
@@ -183,9 +198,11 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
     off_h = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     win = [(r, i, int(off_h[r]) + s, n) for r, p in enumerate(plans) for i, (s, n) in enumerate(zip(p.starts, p.lengths))]
     speech = None                                       # seconds of speech per window; a window at or below min_speech_s is not decoded
-    if vad is not None:
-        from .vad import window_speech_seconds
-        speech = window_speech_seconds(vad, flat, offsets, lens, [(w[0], w[2] - int(off_h[w[0]]), w[3]) for w in win])
+    if vad is not None:                                 # the detector runs once: its flags serve speech_s, the skipping and the diarizer
+        from .vad import speech_seconds_from_flags
+        _stat, flags_d, n_vad_d = vad.run_uploaded(flat, offsets, lens)
+        flags_h = flags_d.cpu().numpy() if isinstance(flags_d, torch.Tensor) else np.asarray(flags_d)
+        speech = speech_seconds_from_flags(flags_h, lens, [(w[0], w[2] - int(off_h[w[0]]), w[3]) for w in win])
     keep = list(range(len(win))) if speech is None else [k for k in range(len(win)) if speech[k] > min_speech_s]
     dev = flat.device
     fe = model.feature_extractor
@@ -242,4 +259,33 @@ def transcribe_long(model, audio, sample_rate: int = 16000, *, max_window_s: flo
         if return_timestamps:
             res["words"] = [w for k in ks for w in words[k]]
         results.append(res)
+    if return_speakers:
+        _add_speakers(results, flat, off_h, lens, flags_h, flags_d, n_vad_d, speaker_model, num_speakers, min_speakers, max_speakers,
+                      cluster_device)
     return results[0] if single else results
+
+
+def _add_speakers(results, flat, off_h, lens, flags_h, flags_d, n_vad_d, speaker_model, num_speakers, min_speakers, max_speakers,
+                  cluster_device):
+    """``"speaker_segments"`` for every result and ``"speaker"`` for every word: the diarizer on the uploaded buffer and the detector's
+    flags; one ``embed_windows`` call for all recordings' windows, clustering per recording as ``diarize`` does it, then one ``spk_vote``,
+    one ``spk_merge`` and one ``spk_words`` launch for the whole call."""
+    from .diarization import LocalSpeakerDiarizer, SpeakerClusterer
+    from .ops import vad_frames
+    from .vad import segments_from_flags
+    dev = flat.device
+    decisions = [np.asarray(flags_h[r, :vad_frames(n)]).astype(bool) for r, n in enumerate(lens)]
+    embedded = LocalSpeakerDiarizer.extract_embeddings_uploaded(flat, off_h, lens, [segments_from_flags(f) for f in decisions], speaker_model)
+    items = []
+    for r, (embeddings, windows) in enumerate(embedded):
+        labels = []
+        if len(embeddings):
+            labels = SpeakerClusterer(min_num_spks=min_speakers or 2, max_num_spks=max_speakers or 10, device=cluster_device)(embeddings,
+                                                                                                                          num_speakers)
+        items.append((windows if len(labels) else [], labels, lens[r] / SAMPLE_RATE, decisions[r].tolist()))
+    if not isinstance(flags_d, torch.Tensor):
+        flags_d, n_vad_d = torch.from_numpy(np.ascontiguousarray(flags_d, dtype=np.uint8)), torch.as_tensor(n_vad_d, dtype=torch.int32)
+    turns = LocalSpeakerDiarizer.postprocess_batch(items, dev, vad_device=(flags_d.to(dev), n_vad_d.to(dev)))
+    for res, t in zip(results, turns):
+        res["speaker_segments"] = t
+    LocalSpeakerDiarizer.assign_speakers_batch([(res["words"], res["speaker_segments"]) for res in results], dev)

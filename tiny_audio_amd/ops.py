@@ -963,8 +963,175 @@ def vad(wav, offsets, max_samples, smooth=2, noise_window=94, noise_bias=2.0, th
     return stat, flags, n_frames
 
 
+# ----------------------------------------------------------------------------- speaker turns (csrc/speaker_post.hip)
+SPK_LIMITS = {"recordings": 64, "speakers": 16, "frames": 1048577, "items": 1048576}      # TA_SPK_MAX_* of include/ta355.h
+SPK_FRAME_TILE = 1024          # frames per workgroup of the owner and compaction kernels (TA_SPK_FRAME_TILE)
+SPK_SEG_TILE = 1024            # segments staged through LDS at a time by the words kernel (TA_SPK_SEG_TILE)
+SPK_OPTION_NAMES = ("voting_rate", "vad_frame_s", "min_segment_s", "short_gap_s", "same_gap_s")
+I32 = torch.int32
+F64 = torch.float64
+
+
+def check_spk_options(options):
+    """The five ``ta_spk_post_options`` in seconds -> a tuple of floats, or ``ValueError`` naming the one that is not finite and > 0."""
+    import math
+    options = tuple(float(v) for v in options)
+    if len(options) != len(SPK_OPTION_NAMES):
+        raise ValueError(f"speaker turns: {len(SPK_OPTION_NAMES)} options are expected ({', '.join(SPK_OPTION_NAMES)}); got {len(options)}")
+    for name, v in zip(SPK_OPTION_NAMES, options):
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"speaker turns: {name} must be finite and > 0; got {v}")
+    return options
+
+
+def _spk_ragged(name, cu, *arrays, what):
+    """cu int32 [R + 1] and the flat arrays it indexes -> R, after the shape, dtype and count checks that need no read-back."""
+    dev = cu.device
+    if cu.dim() != 1 or cu.numel() < 1 or cu.dtype != I32:
+        raise ValueError(f"{name}: the offsets must be int32 [R + 1]; got {tuple(cu.shape)} {cu.dtype}")
+    R = cu.numel() - 1
+    if R > SPK_LIMITS["recordings"]:
+        raise ValueError(f"{name}: {R} recordings, the kernels take at most {SPK_LIMITS['recordings']} per call")
+    n = arrays[0].numel()
+    if n > SPK_LIMITS["items"]:
+        raise ValueError(f"{name}: {n} {what}, the kernels take at most {SPK_LIMITS['items']} per call")
+    for a in arrays:
+        if a.dim() != 1 or a.numel() != n or a.dtype != arrays[0].dtype or a.device != dev or not a.is_contiguous():
+            raise ValueError(f"{name}: the {what} must be flat contiguous arrays of one length, dtype and device")
+    assert cu.is_contiguous()
+    return R
+
+
+def _spk_check_cu(name, cu, n, what):
+    """One read-back of the offsets: ascending from 0 to n (n None: to anything)."""
+    c = cu.cpu().tolist()
+    n = c[-1] if n is None else n
+    if c[0] != 0 or c[-1] != n or any(b < a for a, b in zip(c, c[1:])):
+        raise ValueError(f"{name}: the offsets of the {what} must ascend from 0 to their count {n}; got {c[:4]} .. {c[-1]}")
+    return c
+
+
+def spk_vote(first, last, label, cu_win, S, n_frames, max_frames, vad, n_vad, cu_cap, options, out=None, capacity=None):
+    """ta_spk_vote_i32: windows ``first`` / ``last`` / ``label`` int32 [sum Nw] of R recordings (``cu_win`` int32 [R + 1]; labels in
+    [0, S)) vote on the frames they cover of grids of ``n_frames`` int32 [R] frames (each <= ``max_frames``); ``vad`` uint8 [R, ld] with
+    ``n_vad`` int32 [R] decisions per row, as ``ops.vad`` returns them -> (run_spk, run_f0, run_f1 int32 [cu_cap[R]], n_runs int32 [R],
+    status int32 [R]): recording r's runs of one speaker in ascending time at ``cu_cap[r]`` ..; status 1 where they did not fit.
+    ``out``: the three run buffers (positions beyond a recording's count keep what they held)."""
+    if not (first.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("spk_vote needs its inputs on a HIP device: there is no CPU path")
+    opts = check_spk_options(options)
+    R = _spk_ragged("spk_vote", cu_win, first, last, label, what="windows")
+    S, max_frames, dev = int(S), int(max_frames), first.device
+    if first.dtype != I32:
+        raise ValueError(f"spk_vote: first, last and label must be int32; got {first.dtype}")
+    if not 1 <= S <= SPK_LIMITS["speakers"]:
+        raise ValueError(f"spk_vote: {S} speakers, the kernels take 1 to {SPK_LIMITS['speakers']}")
+    if not 0 <= max_frames <= SPK_LIMITS["frames"]:
+        raise ValueError(f"spk_vote: {max_frames} voting frames are beyond the limit of {SPK_LIMITS['frames']} per recording (2.9 h of 10 ms)")
+    for name, t in (("n_frames", n_frames), ("n_vad", n_vad)):
+        if t.dtype != I32 or t.shape != (R,) or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"spk_vote: {name} must be int32 [{R}] on the windows' device; got {tuple(t.shape)} {t.dtype}")
+    if cu_cap.dtype != I32 or cu_cap.shape != (R + 1,) or cu_cap.device != dev:
+        raise ValueError(f"spk_vote: cu_cap must be int32 [{R + 1}] on the windows' device")
+    if vad.dtype != torch.uint8 or vad.dim() != 2 or vad.shape[0] != R or vad.device != dev or not vad.is_contiguous():
+        raise ValueError(f"spk_vote: vad must be contiguous uint8 [{R}, ld] on the windows' device; got {tuple(vad.shape)} {vad.dtype}")
+    n_win = first.numel()
+    _spk_check_cu("spk_vote", cu_win, n_win, "windows")
+    cap = _spk_check_cu("spk_vote", cu_cap, None if capacity is None else int(capacity), "run capacities")[-1]
+    # the values the kernels index with: one read-back of four flags
+    bad = torch.stack([(first < 0).any(), ((label < 0) | (label >= S)).any(), ((n_frames < 0) | (n_frames > max_frames)).any(),
+                       (n_vad > vad.shape[1]).any()]).cpu().tolist()
+    if bad[0]:
+        raise ValueError("spk_vote: a window starts before 0 (first >= 0 is required: the reference's slice would wrap a negative start "
+                         "around the grid, which is not rebuilt)")
+    if bad[1]:
+        raise ValueError(f"spk_vote: a label lies outside [0, {S}): map the labels to their ranks first")
+    if bad[2]:
+        raise ValueError(f"spk_vote: n_frames must lie within [0, max_frames = {max_frames}]")
+    if bad[3]:
+        raise ValueError(f"spk_vote: n_vad exceeds the {vad.shape[1]} decisions a row of vad holds")
+    if out is None:
+        out = tuple(torch.zeros(cap, device=dev, dtype=I32) for _ in range(3))
+    for t in out:
+        if t.dtype != I32 or t.dim() != 1 or t.numel() < cap or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"spk_vote: the run buffers must be contiguous int32 [>= {cap}] on the windows' device")
+    n_runs, status = torch.zeros(R, device=dev, dtype=I32), torch.zeros(R, device=dev, dtype=I32)
+    if R == 0:
+        return (*out, n_runs, status)
+    L = lib()
+    ws_bytes = L.ta_spk_post_workspace_bytes(R, S, max_frames, n_win)
+    if ws_bytes < 0:
+        raise _lib.Ta355Error("ta_spk_post_workspace_bytes refused sizes the Python layer admitted")
+    ws = torch.empty(max(ws_bytes, 8), device=dev, dtype=torch.uint8)
+    opt = _lib.SpkPostOptions(*opts)
+    check(L.ta_spk_vote_i32(ptr(first), ptr(last), ptr(label), ptr(cu_win), n_win, R, S, ptr(n_frames), max_frames, ptr(vad), vad.shape[1],
+                            ptr(n_vad), C.byref(opt), ptr(cu_cap), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(n_runs), ptr(status),
+                            ptr(ws), ws_bytes, stream()), "ta_spk_vote_i32")
+    return (*out, n_runs, status)
+
+
+def spk_merge(run_spk, run_f0, run_f1, cu_run, options, out=None, n_run=None):
+    """ta_spk_merge_i32: runs (speaker, f0, f1) int32 [sum runs] of R recordings (``cu_run`` int32 [R + 1]), in time order per recording
+    -> (seg_spk, seg_f0, seg_f1 int32 [sum runs], n_seg int32 [R]): ``_merge_short_segments`` of every recording, its turns at
+    ``cu_run[r]`` ..; positions beyond ``n_seg[r]`` keep what they held (zeros, or the contents of ``out``).  ``n_run`` int32 [R]: only
+    the first ``n_run[r]`` positions of recording r's range hold runs (``spk_vote``'s ``n_runs`` beside its ``cu_cap``)."""
+    if not (run_spk.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("spk_merge needs its inputs on a HIP device: there is no CPU path")
+    opts = check_spk_options(options)
+    R = _spk_ragged("spk_merge", cu_run, run_spk, run_f0, run_f1, what="runs")
+    if run_spk.dtype != I32:
+        raise ValueError(f"spk_merge: the runs must be int32; got {run_spk.dtype}")
+    n, dev = run_spk.numel(), run_spk.device
+    _spk_check_cu("spk_merge", cu_run, n, "runs")
+    if n_run is not None and (n_run.dtype != I32 or n_run.shape != (R,) or n_run.device != dev or not n_run.is_contiguous()):
+        raise ValueError(f"spk_merge: n_run must be int32 [{R}] on the runs' device")
+    if out is None:
+        out = tuple(torch.zeros(n, device=dev, dtype=I32) for _ in range(3))
+    for t in out:
+        if t.dtype != I32 or t.dim() != 1 or t.numel() < n or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"spk_merge: the turn buffers must be contiguous int32 [>= {n}] on the runs' device")
+    n_seg = torch.zeros(R, device=dev, dtype=I32)
+    if R == 0:
+        return (*out, n_seg)
+    opt = _lib.SpkPostOptions(*opts)
+    check(lib().ta_spk_merge_i32(ptr(run_spk), ptr(run_f0), ptr(run_f1), ptr(cu_run), ptr(n_run), R, C.byref(opt), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                 ptr(n_seg), stream()), "ta_spk_merge_i32")
+    return (*out, n_seg)
+
+
+def spk_words(word_start, word_end, cu_word, seg_start, seg_end, cu_seg, out=None):
+    """ta_spk_words_f64: words and segments as float64 seconds, ragged over R recordings (``cu_word``, ``cu_seg`` int32 [R + 1]) ->
+    int32 [sum W]: for every word the index (within its recording) of the first segment that contains its midpoint, else of the first
+    among the segments whose midpoint is nearest, else -1.  Segments in any order, overlapping allowed."""
+    if not (word_start.is_cuda or _lib.DRY_RUN):
+        raise _lib.Ta355Error("spk_words needs its inputs on a HIP device: there is no CPU path")
+    R = _spk_ragged("spk_words", cu_word, word_start, word_end, what="words")
+    if _spk_ragged("spk_words", cu_seg, seg_start, seg_end, what="segments") != R:
+        raise ValueError(f"spk_words: cu_word stands for {R} recordings and cu_seg for {cu_seg.numel() - 1}")
+    if word_start.dtype != F64 or seg_start.dtype != F64 or seg_start.device != word_start.device:
+        raise ValueError(f"spk_words: the times must be float64 on one device; got {word_start.dtype} and {seg_start.dtype}")
+    n, dev = word_start.numel(), word_start.device
+    cw = _spk_check_cu("spk_words", cu_word, n, "words")
+    _spk_check_cu("spk_words", cu_seg, seg_start.numel(), "segments")
+    finite = torch.stack([torch.isfinite(word_start + word_end).all(), torch.isfinite(seg_start + seg_end).all()]).cpu().tolist()
+    if not finite[0]:
+        raise ValueError("spk_words: a word's start or end is not finite")
+    if not finite[1]:
+        raise ValueError("spk_words: a segment's start or end is not finite")
+    if out is None:
+        out = torch.zeros(n, device=dev, dtype=I32)
+    if out.dtype != I32 or out.dim() != 1 or out.numel() < n or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"spk_words: out must be contiguous int32 [>= {n}] on the words' device")
+    max_words = max((b - a for a, b in zip(cw, cw[1:])), default=0)
+    if R == 0 or max_words == 0:
+        return out
+    check(lib().ta_spk_words_f64(ptr(word_start), ptr(word_end), ptr(cu_word), ptr(seg_start), ptr(seg_end), ptr(cu_seg), R, max_words,
+                                 ptr(out), stream()), "ta_spk_words_f64")
+    return out
+
+
 # ----------------------------------------------------------------------------- decoding scores (csrc/generate.hip)
-MAX_TOP_LOGPROBS = 8      # the per-lane candidate list of token_scores_kernel
+MAX_TOP_LOGPROBS = 8     # the per-lane candidate list of token_scores_kernel
 
 
 def token_scores(logits, chosen, V, top_k=0):

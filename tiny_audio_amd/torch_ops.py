@@ -14,6 +14,8 @@ reference has no FFI; its seams are nn.Module boundaries,
                                keeps the first chunk only   tiny_audio/asr_pipeline.py:243-245
     ta355::vad                 TenVad.process, one 256-sample frame per call (a statistical detector of this project's own, not that
                                model)   tiny_audio/diarization.py:370-387
+    ta355::spk_vote, spk_merge, spk_words   LocalSpeakerDiarizer._resample_vad / _postprocess_segments / _merge_short_segments /
+                               assign_speakers_to_words, the host loops behind the cluster labels   tiny_audio/diarization.py:520-682
     ta355::wav2vec2_emissions  torchaudio WAV2VEC2_ASR_BASE_960H forward + log_softmax   tiny_audio/alignment.py:206-211
     ta355::wav2vec2_sln_emissions  the same seam with a layer-norm / stable wav2vec2 (large-lv60, XLSR-53, XLS-R 300M, MMS 300M), which
                                the reference's align(..., _language=...) placeholder stands for   tiny_audio/alignment.py:182-211
@@ -274,6 +276,56 @@ def vad(wav: Tensor, offsets: Tensor, max_samples: int, smooth: int, noise_windo
 def _(wav, offsets, max_samples, smooth, noise_window, noise_bias, threshold, floor):
     R, F = offsets.shape[0] - 1, (0 if max_samples <= 256 else (max_samples - 1) // 256)
     return wav.new_empty((R, F)), wav.new_empty((R, F), dtype=torch.uint8), wav.new_empty((R,), dtype=torch.int32)
+
+
+# ============================================================================ speaker turns
+@torch.library.custom_op("ta355::spk_vote", mutates_args=())
+def spk_vote(first: Tensor, last: Tensor, label: Tensor, cu_win: Tensor, S: int, n_frames: Tensor, max_frames: int, vad: Tensor,
+             n_vad: Tensor, cu_cap: Tensor, capacity: int, voting_rate: float, vad_frame_s: float, min_segment_s: float, short_gap_s: float,
+             same_gap_s: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Windows (first, last, label i32 [sum Nw], cu_win i32 [R + 1]) vote on the frames of R voting grids; vad u8 [R, ld] with n_vad
+    i32 [R] -> (run_spk, run_f0, run_f1 i32 [capacity] with recording r's runs at cu_cap[r] .., n_runs i32 [R], status i32 [R]);
+    ``capacity`` is cu_cap[R] (``ops.spk_vote``).  Integers only: no autograd."""
+    from . import ops
+    return ops.spk_vote(first, last, label, cu_win, S, n_frames, max_frames, vad, n_vad, cu_cap,
+                        (voting_rate, vad_frame_s, min_segment_s, short_gap_s, same_gap_s), capacity=capacity)
+
+
+@spk_vote.register_fake
+def _(first, last, label, cu_win, S, n_frames, max_frames, vad, n_vad, cu_cap, capacity, voting_rate, vad_frame_s, min_segment_s,
+      short_gap_s, same_gap_s):
+    R = cu_win.shape[0] - 1
+    return (first.new_empty((capacity,)), first.new_empty((capacity,)), first.new_empty((capacity,)), first.new_empty((R,)),
+            first.new_empty((R,)))
+
+
+@torch.library.custom_op("ta355::spk_merge", mutates_args=())
+def spk_merge(run_spk: Tensor, run_f0: Tensor, run_f1: Tensor, cu_run: Tensor, n_run: Optional[Tensor], voting_rate: float, vad_frame_s: float,
+              min_segment_s: float, short_gap_s: float, same_gap_s: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Runs (speaker, f0, f1) i32 [sum runs] of R recordings -> (seg_spk, seg_f0, seg_f1 i32 [sum runs], n_seg i32 [R]): every
+    recording's merged turns at cu_run[r] ..; n_run i32 [R] or None: how many positions of a recording's range hold runs
+    (``ops.spk_merge``)."""
+    from . import ops
+    return ops.spk_merge(run_spk, run_f0, run_f1, cu_run, (voting_rate, vad_frame_s, min_segment_s, short_gap_s, same_gap_s), n_run=n_run)
+
+
+@spk_merge.register_fake
+def _(run_spk, run_f0, run_f1, cu_run, n_run, voting_rate, vad_frame_s, min_segment_s, short_gap_s, same_gap_s):
+    return (run_spk.new_empty(run_spk.shape), run_spk.new_empty(run_spk.shape), run_spk.new_empty(run_spk.shape),
+            run_spk.new_empty((cu_run.shape[0] - 1,)))
+
+
+@torch.library.custom_op("ta355::spk_words", mutates_args=())
+def spk_words(word_start: Tensor, word_end: Tensor, cu_word: Tensor, seg_start: Tensor, seg_end: Tensor, cu_seg: Tensor) -> Tensor:
+    """Word and segment times f64, ragged over R recordings -> i32 [sum W]: every word's segment index within its recording, -1
+    without segments (``ops.spk_words``)."""
+    from . import ops
+    return ops.spk_words(word_start, word_end, cu_word, seg_start, seg_end, cu_seg)
+
+
+@spk_words.register_fake
+def _(word_start, word_end, cu_word, seg_start, seg_end, cu_seg):
+    return word_start.new_empty(word_start.shape, dtype=torch.int32)
 
 
 # ============================================================================ decoding scores
@@ -863,4 +915,4 @@ OPERATORS = ("logmel", "encoder_forward", "mlp_projector", "mlp_projector_backwa
              "token_scores", "wav2vec2_emissions", "ecapa_embeddings", "spk_affinity", "spk_laplacian_matmul", "spk_panel_gram",
              "spk_panel_update", "spk_panel_combine", "logits_sequence_bias", "logits_step_rules", "logits_warp_ext", "ctc_align_long", "beam_logprobs", "beam_topk",
              "beam_advance", "kv_beam_expand", "kv_beam_reorder", "wave_cut_cost", "cut_plan", "wave_windows", "text_align",
-             "wav2vec2_sln_emissions", "vad")
+             "wav2vec2_sln_emissions", "vad", "spk_vote", "spk_merge", "spk_words")

@@ -65,6 +65,19 @@ class DeviceVAD:
         recording r owns the first ``ops.vad_frames(lens[r])`` positions of its row."""
         return torch.ops.ta355.vad(flat, offsets, int(max(lens)), *self.options())
 
+    def speech_frames_uploaded(self, flat, offsets, lens):
+        """On a batch ``longform.upload`` made -> (the decisions per recording as host bool arrays, flags uint8 [R, F_max] and n_frames
+        int32 [R] on the device): one run, one read-back, and the device's copy kept for whoever reads it next (``spk_vote``)."""
+        stat, flags, n_frames = self.run_uploaded(flat, offsets, lens)
+        stat_h, flags_h = stat.cpu().numpy(), flags.cpu().numpy()
+        out = []
+        for r, n in enumerate(lens):
+            F = vad_frames(n)
+            if not np.isfinite(stat_h[r, :F]).all():
+                raise ValueError(f"recording {r} holds non-finite samples")
+            out.append(flags_h[r, :F].astype(bool))
+        return out, flags, n_frames
+
     def _run(self, waves):
         """-> (single, [(L f32 [F_r], flags bool [F_r]) per recording]): one upload, two launches, one read-back."""
         from .longform import upload
@@ -105,7 +118,11 @@ def window_speech_seconds(vad, flat, offsets, lens, windows) -> list[float]:
     """``vad.run_uploaded`` on an uploaded batch (no second upload; the flags are the one read-back) -> for every window
     ``(recording, start_sample, n_samples)`` the seconds of the recording's speech segments (after the diarizer's hysteresis) inside it."""
     _stat, flags, _nf = vad.run_uploaded(flat, offsets, lens)
-    flags_h = flags.cpu().numpy() if isinstance(flags, torch.Tensor) else np.asarray(flags)
+    return speech_seconds_from_flags(flags.cpu().numpy() if isinstance(flags, torch.Tensor) else np.asarray(flags), lens, windows)
+
+
+def speech_seconds_from_flags(flags_h, lens, windows) -> list[float]:
+    """``window_speech_seconds`` behind the read-back: flags_h [R, F_max] on the host."""
     spans = []
     for r, n in enumerate(lens):
         segs = segments_from_flags(flags_h[r, :vad_frames(n)])
